@@ -2,8 +2,13 @@
 """bench.py — images/sec of one full wgancls iteration (critic step + kt, then generator step; reference
 models/wgancls/trainer.py:97-102) at 64x64, batch 64 per GPU, fp32, synthetic inputs, random-init weights.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--no-cpu-baseline] [--instrument inline|after|off]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--dump-outputs DIR] [--full] [--no-cpu-baseline]
+                    [--instrument inline|after|off]
 
+A plain run sets up, runs W warm-up iterations, times ONE region of exactly K iterations, optionally writes what the last timed
+iteration computed (--dump-outputs) and prints the line.  --full adds everything else the benchmark measures or checks: more timed
+regions (median reported), the per-launch roofline pass, the config3_bf16 block, the b8_per_gpu / next_rows side rows, the CPU
+baselines and, with N > 1, the data-parallel preflight and the exchange statistics.
 N > 1 is launched by the driver as `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`
 (one rank per GPU over RCCL); the batch is per GPU (weak scaling) and gradients are all-reduced (dp.py).
 Rank 0 prints ONE JSON line.  See DESIGN.md §6 for how `roofline` and `cpu_baseline` are obtained.
@@ -138,6 +143,34 @@ def cpu_baseline(batch=16, timeout_s=180):
     except Exception as e:       # timeout / crash: say so instead of blocking or inventing a number
         return {'value': None, 'unit': 'images/sec', 'cores': effective_cpus(), 'kind': 'port',
                 'sample': 'not measured: %s' % type(e).__name__}
+
+
+BENCH_NOISE_SEED = 2                  # device generator seed of rank 0 (rank r: + r)
+DUMP_WEIGHT_SAMPLE = 1 << 20          # weights written per arena by --dump-outputs (a fixed, seeded sample: 4 MB each)
+
+
+def dump_outputs(path, out, model):
+    """--dump-outputs: what the last timed iteration handed its caller — every tensor of the critic step's and the generator step's
+    result dicts (loss scalars, G, D(x_hat), the gradient-penalty input gradients) — and the state it left behind: kt and a fixed,
+    seeded sample of the updated critic and generator weights.  float32 .npy files, ~17 MB at B = 64."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {}
+    for part in ('d', 'g'):
+        for k, v in sorted((out.get(part) or {}).items()):
+            if torch.is_tensor(v):
+                arrays['%s_%s' % (part, k)] = v.detach().float().cpu().numpy()
+    arrays['kt'] = model.kt.detach().float().cpu().numpy()
+    for name, arena in (('d_weights_sample', model.d_arena), ('g_weights_sample', model.g_arena)):
+        n = arena.flat.numel()
+        idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_WEIGHT_SAMPLE), replace=False))
+        arrays[name] = arena.flat.detach()[torch.from_numpy(idx).to(arena.flat.device)].float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, total
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+    sys.stderr.write('[bench] wrote %d arrays (%.1f MB) to %s\n' % (len(arrays), total / 2.0 ** 20, path))
 
 
 def _signature(model):
@@ -288,10 +321,14 @@ def run_config(args, math, device, rank, local_rank, world, use_dp, make_dp, hea
     dp, grad_dtype = make_dp(math)
     use_graphs = not args.no_graphs and args.instrument != 'inline' and not (use_dp and os.environ.get('T2I_DP_GRAPHS') == '0')
     preflight = None
-    if world > 1 and os.environ.get('T2I_PREFLIGHT', '1') != '0':
+    # (a check, not part of the headline: on with --full, or with T2I_PREFLIGHT=1 / strict)
+    if world > 1 and os.environ.get('T2I_PREFLIGHT', '1' if args.full else '0') != '0':
         preflight = dp_preflight(cfg, device, lambda: make_dp(math)[0], use_graphs, rank, world, args.batch, grad_dtype=grad_dtype, net_math=net_math)
         if rank == 0:
             sys.stderr.write('[bench] data-parallel preflight (%s) passed: %r\n' % (math, preflight))
+    # the conditioning-augmentation noise the iteration draws comes from the device's torch generator, whose default seed differs from
+    # process to process: seeded, so that the same arguments give the same inputs (and --dump-outputs the same outputs) in every run
+    torch.cuda.manual_seed(BENCH_NOISE_SEED + rank)
     model = WGanCls(cfg, device=device, seed=0, dp=dp)
     model.net_math = net_math
     if dp is not None:
@@ -363,6 +400,8 @@ def run_config(args, math, device, rank, local_rank, world, use_dp, make_dp, hea
     while len(regions) < want:
         regions.append(timed_region())
     dt = sorted(regions)[len(regions) // 2]     # median region
+    if headline and rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, trainer.last, model)
     exchange = None
     inst_steps = args.steps
     if args.instrument == 'after':          # same workload, immediately after the timed region, with per-launch events
@@ -407,7 +446,7 @@ def run_config(args, math, device, rank, local_rank, world, use_dp, make_dp, hea
             sys.stderr.write('[bench] replica sync check passed: %s\n' % sig.tolist())
     # the exchange itself, measured on 3 more iterations of the same schedule (events on the communication stream around every
     # collective, on the compute stream around every wait for them): bytes, ms in collectives, ms stalled, overlap fraction
-    if use_dp and dp is not None:
+    if use_dp and dp is not None and args.full:
         barrier()
         dp.begin_stats()
         for i in range(3):
@@ -571,8 +610,13 @@ def main():
     ap.add_argument('--batch', type=int, default=64, help='per-GPU batch')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-graphs', action='store_true', help='keep the step eager (default: hipGraph replay on 1 GPU)')
-    ap.add_argument('--instrument', choices=['inline', 'after', 'off'], default='after',
-                    help='where the per-launch HIP events for the roofline block are recorded')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beyond the headline (more timed regions, roofline pass, config3_bf16 block, '
+                         'side rows, CPU baselines; N > 1: data-parallel preflight and exchange statistics)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed iteration computed as DIR/<name>.npy (float32)')
+    ap.add_argument('--instrument', choices=['inline', 'after', 'off'], default=None,
+                    help='where the per-launch HIP events for the roofline block are recorded (default: after with --full, off otherwise)')
     ap.add_argument('--math', choices=['f32', 'bf16'], default='f32',
                     help="conv arithmetic: f32 = BASELINE config 2 (the headline metric); bf16 = config 3 (bf16 MFMA "
                          "operands, fp32 accumulation and fp32 tensors) -- reported with dtype 'bf16', never the default")
@@ -581,15 +625,23 @@ def main():
                          "(ABI v6, default); 'f32' = fp32 tensors with bf16 operand images beside them (round 2)")
     ap.add_argument('--side-stream', type=int, default=int(os.environ.get('T2I_SIDE_STREAM', '0')),
                     help='1: sunk filter gradients run on a second HIP stream, concurrently with the bwd-data chain')
-    ap.add_argument('--repeats', type=int, default=3,
-                    help='timed regions of --steps iterations each, every one bracketed by barrier + synchronize; the MEDIAN is reported')
-    ap.add_argument('--min-busy-s', type=float, default=3.0,
-                    help='keep adding timed regions (each exactly --steps iterations) until the GPU has been busy this long in total')
+    ap.add_argument('--repeats', type=int, default=None,
+                    help='timed regions of --steps iterations each, every one bracketed by barrier + synchronize; the MEDIAN is reported '
+                         '(default: 3 with --full, 1 otherwise)')
+    ap.add_argument('--min-busy-s', type=float, default=None,
+                    help='keep adding timed regions (each exactly --steps iterations) until the GPU has been busy this long in total '
+                         '(default: 3.0 with --full, 0 otherwise)')
     ap.add_argument('--no-config3', action='store_true', help='skip the config3_bf16 block (bf16 arithmetic) behind the fp32 headline')
     ap.add_argument('--no-side-rows', action='store_true', help='skip the b8_per_gpu and next_rows blocks')
     ap.add_argument('--side-budget-s', type=float, default=0.6, help='timed replay budget per side row')
     ap.add_argument('--cpu-baseline-only', type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.instrument is None:
+        args.instrument = 'after' if args.full else 'off'
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    if args.min_busy_s is None:
+        args.min_busy_s = 3.0 if args.full else 0.0
     if args.cpu_baseline_only:
         cpu_baseline_child(args.cpu_baseline_only)
         return
@@ -643,7 +695,7 @@ def main():
     out = run_config(args, args.math, device, rank, local_rank, world, use_dp, make_dp, headline=True)
     # BASELINE config 3 (bf16 MFMA operands, fp32 accumulate / master weights, bf16 gradient buckets under data parallelism) rides
     # on the SAME JSON line as a block of its own, so the driver's record holds it; the headline stays the fp32 metric.
-    if args.math == 'f32' and not args.no_config3 and os.environ.get('T2I_BENCH_CONFIG3', '1') != '0':
+    if args.full and args.math == 'f32' and not args.no_config3 and os.environ.get('T2I_BENCH_CONFIG3', '1') != '0':
         import copy
         a3 = copy.copy(args)
         a3.repeats = max(1, min(args.repeats, 3))
@@ -685,7 +737,7 @@ def main():
             out['config3_bf16'] = blk
     # SURVEY 8(d)'s strong-scaling share (global 64 = 8 per GPU = the yml's BATCH_SIZE) and the next rows (gancls, StackGAN, PGGAN):
     # short measured rows on the same line — images/s, algorithmic GFLOP/image, fraction of the matrix peak on the replayed clock
-    if (rank == 0 and world == 1 and args.math == 'f32' and not args.no_config3 and not args.no_side_rows and args.instrument != 'off' and
+    if (args.full and rank == 0 and world == 1 and args.math == 'f32' and not args.no_config3 and not args.no_side_rows and args.instrument != 'off' and
             os.environ.get('T2I_BENCH_SIDE_ROWS', '1') != '0'):      # only on the full default line (diagnostic invocations skip them)
         from tools.next_rows import measure_rows
         b8 = measure_rows(['wgancls_b8'], 'f32', args.side_budget_s, device) + measure_rows(['wgancls_b8'], 'bf16', args.side_budget_s, device, args.storage)
@@ -695,7 +747,7 @@ def main():
         rows += measure_rows(['stage2'], 'bf16', args.side_budget_s, device, 'f32')     # (fp32 activation tensors + bf16 operand images: the StackGAN graphs mix 3-channel joins into 64-multiples)
         out['next_rows'] = {'what': 'SURVEY 8(f) rows + the gancls variant at the reference\'s dimensions and batch sizes; algorithmic_gflop_per_image = '
                                     'direct-convolution FLOPs of the conv/deconv/dense calls one iteration launches / batch', 'rows': rows}
-    if rank == 0 and not args.no_cpu_baseline and world == 1:      # the CPU leg is reported at N=1 only (the other ranks would idle in the final barrier)
+    if args.full and rank == 0 and not args.no_cpu_baseline and world == 1:      # the CPU leg is reported at N=1 only (the other ranks would idle in the final barrier)
         out['cpu_baseline'] = cpu_baseline(16)              # BASELINE configs[0]
         out['cpu_baseline_b64'] = cpu_baseline(64)          # and the batch the metric is quoted on
     if use_dp:

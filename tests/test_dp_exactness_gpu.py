@@ -29,7 +29,7 @@ def _signature(cmd, env_extra):
 
 def _two_ranks(port, args, env_extra):
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-           '--master-port', str(port), 'bench.py', '--gpus', '2', '--instrument', 'off', '--no-cpu-baseline', '--repeats', '1', '--min-busy-s', '0', '--no-config3'] + args
+           '--master-port', str(port), 'bench.py', '--gpus', '2', '--full', '--instrument', 'off', '--no-cpu-baseline', '--repeats', '1', '--min-busy-s', '0', '--no-config3'] + args
     env = dict(T2I_SAME_DEVICE='1', T2I_DIST_BACKEND='gloo', T2I_CHECK_SYNC='1')
     env.update(env_extra)
     return _signature(cmd, env)
@@ -76,7 +76,7 @@ def test_bench_gpus_2_launches_itself_and_describes_the_exchange():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     env.update(T2I_SAME_DEVICE='1', T2I_DIST_BACKEND='gloo')
-    r = subprocess.run([sys.executable, 'bench.py', '--gpus', '2', '--steps', '2', '--warmup', '1', '--repeats', '1', '--min-busy-s', '0',
+    r = subprocess.run([sys.executable, 'bench.py', '--gpus', '2', '--full', '--steps', '2', '--warmup', '1', '--repeats', '1', '--min-busy-s', '0',
                         '--no-cpu-baseline', '--no-config3', '--instrument', 'off'], cwd=ROOT, env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
@@ -107,7 +107,7 @@ def _bench_gpus_3_preflight_holds_an_inexact_sum_to_rounding():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     env.update(T2I_SAME_DEVICE='1', T2I_DIST_BACKEND='gloo', OMP_NUM_THREADS='2')
-    r = subprocess.run([sys.executable, 'bench.py', '--gpus', '3', '--steps', '1', '--warmup', '1', '--repeats', '1', '--min-busy-s', '0',
+    r = subprocess.run([sys.executable, 'bench.py', '--gpus', '3', '--full', '--steps', '1', '--warmup', '1', '--repeats', '1', '--min-busy-s', '0',
                         '--no-cpu-baseline', '--no-config3', '--instrument', 'off'], cwd=ROOT, env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]

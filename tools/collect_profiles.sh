@@ -65,7 +65,7 @@ PY
   rm -rf "$OUT/kt_$row"
 done
 cd "$REPO"
-timeout 600 python bench.py 2>/dev/null | grep '"metric"' > "$OUT/bench_line.json"
+timeout 600 python bench.py --full 2>/dev/null | grep '"metric"' > "$OUT/bench_line.json"
 # drop the bulky raw traces, keep the per-pass counter csv of the MFMA pass for reference
 rm -rf "$OUT/ktrace" "$OUT/pmc_FETCH_SIZE" "$OUT/pmc_WRITE_SIZE" "$OUT/pmc_SQ_VALU_MFMA_BUSY_CYCLES"
 ls -la "$OUT"; cat "$OUT/pmc_summary.log" | tail -30; cat "$OUT/bench_line.json"

@@ -13,10 +13,10 @@ cd "$REPO"
 for n in $NS; do
   port=$((29500 + n))
   if [ "$n" = 1 ]; then
-    timeout 900 python bench.py --gpus 1 --steps "$STEPS" --warmup "$WARM" --no-cpu-baseline > "$OUT/n$n.out" 2> "$OUT/n$n.err"
+    timeout 900 python bench.py --gpus 1 --steps "$STEPS" --warmup "$WARM" --full --no-cpu-baseline > "$OUT/n$n.out" 2> "$OUT/n$n.err"
   else
     timeout 1800 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port "$port" \
-        bench.py --gpus "$n" --steps "$STEPS" --warmup "$WARM" --no-cpu-baseline > "$OUT/n$n.out" 2> "$OUT/n$n.err"
+        bench.py --gpus "$n" --steps "$STEPS" --warmup "$WARM" --full --no-cpu-baseline > "$OUT/n$n.out" 2> "$OUT/n$n.err"
   fi
   echo "N=$n rc=$?" >&2
   grep '"metric"' "$OUT/n$n.out" | tail -1 > "$OUT/n$n.json"
