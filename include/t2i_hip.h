@@ -72,7 +72,7 @@ typedef struct t2i_conv_desc {
 enum { T2I_MATH_F32 = 0, T2I_MATH_BF16 = 1 };
 
 /* ---- library ------------------------------------------------------------------------------------------------ */
-int t2i_version(void);            /* ABI version, currently 9 (v9: t2i_conv_opts gained xform_valid_rows / xform_plane_rows, t2i_bn_train_fwd_grouped gained moving_groups, t2i_trunc_normal and t2i_zero_ranges added; v8: t2i_sigmoid_ce_head, t2i_bn_train_fwd_grouped, t2i_bn_bwd_grouped, t2i_bn_grouped_workspace_bytes added — no existing signature changed; v7: v7: t2i_conv2d_bwd_pair, t2i_row_scale_div, t2i_stat, t2i_filter_cache_assume added, t2i_adam_tf takes m == NULL at beta1 == 0 — no existing signature changed; v2: t2i_conv_desc.math; v3: caller-owned filter-cache arena,
+int t2i_version(void);            /* ABI version, currently 10 (v10: t2i_nearest_images and t2i_nearest_images_workspace_bytes added — no existing signature changed; v9: t2i_conv_opts gained xform_valid_rows / xform_plane_rows, t2i_bn_train_fwd_grouped gained moving_groups, t2i_trunc_normal and t2i_zero_ranges added; v8: t2i_sigmoid_ce_head, t2i_bn_train_fwd_grouped, t2i_bn_bwd_grouped, t2i_bn_grouped_workspace_bytes added — no existing signature changed; v7: v7: t2i_conv2d_bwd_pair, t2i_row_scale_div, t2i_stat, t2i_filter_cache_assume added, t2i_adam_tf takes m == NULL at beta1 == 0 — no existing signature changed; v2: t2i_conv_desc.math; v3: caller-owned filter-cache arena,
                                    * t2i_tuning_set, t2i_kt_sgd; v4: t2i_filter_cache_refresh, bf16 operand images; v5: t2i_conv_opts
                                    * and explicit image arguments instead of thread-local one-shot hand-overs; v6: bf16 STORAGE —
                                    * activation tensors may be bf16 at this interface: t2i_dtype arguments, t2i_conv_opts.in_dtype /
@@ -445,6 +445,21 @@ int t2i_crop_flip_normalize(const uint8_t* src, int64_t N, int32_t S, const int3
  * order then division by k — bit-identical to np.mean(e[choice], axis=0). */
 int t2i_gather_mean(const float* emb, int64_t N, int32_t En, int32_t D, const int32_t* ids, const int32_t* choice, int32_t B,
                     int32_t k, float* out, t2i_stream_t stream);
+
+/* ---- caption visualiser: reference utils/visualize.py closest_image --------------------------------------------- */
+/* Closest training image of each of Q generated images.  For every query q and stored image n:
+ *   real[r,c,ch] = fl32(fl32(u8 * fl32(2/255)) - 1)   (no fused multiply-add: exactly t2i_crop_flip_normalize's value) of
+ *                  src[n, row0[q,n]+r, flip[q,n] ? col0[q,n]+out_size-1-c : col0[q,n]+c, ch]
+ *   fake         = min(max(queries[q], lo), hi)        in fp32 (the reference's np.clip(samples, -1, 1))
+ *   d2[q,n]      = sum ((double)fake - (double)real)^2 accumulated in fp64
+ * idx[q] = the smallest n with minimal d2[q,n], dist2[q] = that minimum.  src [N,S,S,3] uint8; queries [Q,out_size,out_size,3]
+ * float32; row0/col0/flip device int32 [Q,N] each, or all three NULL for the identity crop (then S == out_size); idx int32 [Q],
+ * dist2 double [Q].  The caller guarantees row0/col0 + out_size <= S.  N <= INT32_MAX.  Scratch: the workspace query (Q*N
+ * doubles).  No atomics: results are bitwise identical from call to call. */
+size_t t2i_nearest_images_workspace_bytes(int32_t Q, int64_t N);
+int t2i_nearest_images(const uint8_t* src, int64_t N, int32_t S, const int32_t* row0, const int32_t* col0, const int32_t* flip,
+                       const float* queries, int32_t Q, int32_t out_size, float lo, float hi, int32_t* idx, double* dist2,
+                       void* ws, size_t ws_bytes, t2i_stream_t stream);
 
 #ifdef __cplusplus
 }

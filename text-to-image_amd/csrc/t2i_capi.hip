@@ -51,6 +51,10 @@ hipError_t gp_slopes_launch(const void*, int, int64_t, float*, hipStream_t, bool
 hipError_t row_scale_launch(const void*, const float*, int, int64_t, void*, hipStream_t, bool bf16 = false, const float* den = nullptr);
 hipError_t crop_flip_normalize_launch(const uint8_t*, int, const int32_t*, const int32_t*, const int32_t*, const int32_t*, int, int, float*, hipStream_t);
 hipError_t gather_mean_launch(const float*, int, int, const int32_t*, const int32_t*, int, int, float*, hipStream_t);
+// implemented in t2i_nearest.hip
+size_t nearest_images_ws(int Q, int64_t N);
+hipError_t nearest_images_launch(const uint8_t*, int, int, const int32_t*, const int32_t*, const int32_t*, const float*, int, int, float,
+                                 float, int32_t*, double*, void*, hipStream_t);
 hipError_t resample2_launch(bool, const float*, int, int, int, int, float, float*, hipStream_t);
 hipError_t row_moments_launch(const float*, const float*, int, int64_t, float*, float*, void*, hipStream_t);
 size_t row_moments_ws(int B);
@@ -672,7 +676,7 @@ using namespace t2i;
 
 extern "C" {
 
-int t2i_version(void) { return 9; }
+int t2i_version(void) { return 10; }
 
 const char* t2i_last_error(void) { return g_err; }
 
@@ -1437,6 +1441,29 @@ int t2i_crop_flip_normalize(const uint8_t* src, int64_t N, int32_t S, const int3
   }
   return check(crop_flip_normalize_launch(src, S, ids, row0, col0, flip, B, out_size, out, (hipStream_t)stream),
                "t2i_crop_flip_normalize");
+}
+
+size_t t2i_nearest_images_workspace_bytes(int32_t Q, int64_t N) {
+  return (Q > 0 && N > 0 && N <= INT32_MAX) ? nearest_images_ws(Q, N) : 0;
+}
+
+int t2i_nearest_images(const uint8_t* src, int64_t N, int32_t S, const int32_t* row0, const int32_t* col0, const int32_t* flip,
+                       const float* queries, int32_t Q, int32_t out_size, float lo, float hi, int32_t* idx, double* dist2,
+                       void* ws, size_t ws_bytes, t2i_stream_t stream) {
+  const int tables = (row0 != nullptr) + (col0 != nullptr) + (flip != nullptr);
+  if (!src || !queries || !idx || !dist2 || N <= 0 || N > INT32_MAX || Q <= 0 || S <= 0 || out_size <= 0 || out_size > S ||
+      (tables != 0 && tables != 3) || (tables == 0 && out_size != S)) {
+    set_error("t2i_nearest_images: bad argument (N=%lld Q=%d S=%d out_size=%d, %d of 3 crop tables)", (long long)N, Q, S,
+              out_size, tables);
+    return T2I_ERR_INVALID;
+  }
+  if (!ws || ws_bytes < nearest_images_ws(Q, N) || !aligned16(ws)) {
+    set_error("t2i_nearest_images: workspace too small or misaligned (%zu bytes, need %zu)", ws_bytes, nearest_images_ws(Q, N));
+    return T2I_ERR_WORKSPACE;
+  }
+  return check(nearest_images_launch(src, (int)N, S, row0, col0, flip, queries, Q, out_size, lo, hi, idx, dist2, ws,
+                                     (hipStream_t)stream),
+               "t2i_nearest_images");
 }
 
 int t2i_gather_mean(const float* emb, int64_t N, int32_t En, int32_t D, const int32_t* ids, const int32_t* choice, int32_t B,

@@ -1098,6 +1098,34 @@ def crop_flip_normalize(src_u8, ids, row0, col0, flip, out_size):
     return out
 
 
+def nearest_images(src_u8, queries, row0=None, col0=None, flip=None, lo=-1.0, hi=1.0):
+    """Closest stored image of each query (reference utils/visualize.py closest_image, one launch for all of them).
+    src_u8 [N,S,S,3] uint8 (device); queries float32 [Q,out,out,3], clipped to [lo, hi] inside; row0/col0/flip int [Q,N]: the crop
+    of image n that query q is compared with (all None: the identity crop, S == out).  -> (idx int64 [Q], dist2 float64 [Q]):
+    the lowest index of minimal squared distance, accumulated in fp64."""
+    if src_u8.dtype != torch.uint8 or src_u8.dim() != 4 or src_u8.shape[3] != 3 or src_u8.shape[1] != src_u8.shape[2]:
+        raise ValueError('nearest_images expects a uint8 [N,S,S,3] store, got %s %s' % (src_u8.dtype, tuple(src_u8.shape)))
+    if queries.dtype != torch.float32 or queries.dim() != 4 or queries.shape[3] != 3 or queries.shape[1] != queries.shape[2]:
+        raise ValueError('nearest_images expects float32 [Q,out,out,3] queries, got %s %s' % (queries.dtype, tuple(queries.shape)))
+    N, S = src_u8.shape[0], src_u8.shape[1]
+    Q, out = queries.shape[0], queries.shape[1]
+    tables = (row0, col0, flip)
+    if any(t is None for t in tables) != all(t is None for t in tables):
+        raise ValueError('nearest_images: pass all three crop tables or none')
+    if row0 is None and out != S:
+        raise ValueError('nearest_images: without crop tables the queries must be %dx%d like the store, got %dx%d' % (S, S, out, out))
+    if row0 is not None and any(tuple(t.shape) != (Q, N) for t in tables):
+        raise ValueError('nearest_images: crop tables must be [Q, N] = [%d, %d], got %s' % (Q, N, [tuple(t.shape) for t in tables]))
+    idx = torch.empty(Q, dtype=torch.int32, device=src_u8.device)
+    dist2 = torch.empty(Q, dtype=torch.float64, device=src_u8.device)
+    if _live(src_u8):
+        tabs = [t.to(device=src_u8.device, dtype=torch.int32).contiguous() if t is not None else None for t in tables]
+        wsp, wsn = _ws_args(src_u8, int(lib.t2i_nearest_images_workspace_bytes(Q, N)))
+        check(lib.t2i_nearest_images(_ptr(src_u8.contiguous()), N, S, *[_ptr(t) for t in tabs], _ptr(queries.contiguous()), Q, out,
+                                     float(lo), float(hi), _ptr(idx), _ptr(dist2), wsp, wsn, _stream()), 't2i_nearest_images')
+    return idx.long(), dist2
+
+
 def gather_mean(emb, ids, choice):
     """emb [N,En,D] float32; ids int32 [B]; choice int32 [B,k] -> [B,D] mean of the chosen rows, in choice order."""
     _chk(emb, 'emb')

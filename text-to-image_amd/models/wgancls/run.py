@@ -1,14 +1,17 @@
 """Entry point of the wgancls model — reference models/wgancls/run.py:13-74.
 
-    python -m t2i_amd.models.wgancls.run --cfg <yaml> [--train] [--synthetic] [--steps N] [--batch B] [--graphs 0|1]
+    python -m t2i_amd.models.wgancls.run --cfg <yaml> [--train | --visualize [--interp N]] [--synthetic] [--steps N] [--batch B]
+                                         [--graphs 0|1]
 
 Behaviour of the reference's main(): read the config, create CHECKPOINT_DIR / SAMPLE_DIR / LOGS_DIR, load the pickled
 dataset from cfg.DATASET_DIR (`TextDataset(datadir, 64)`, splits `<datadir>/test` and `<datadir>/train`), then switch on
 the mode flags: EVAL.FLAG -> Inception-score evaluation, TRAIN.FLAG -> `WGanClsTrainer(...).train()` with its periodic
-side effects (captions, sample grids, checkpoints, resume), neither -> the caption visualiser.  Evaluation and
-visualisation are outside this build's scope and say so instead of silently doing something else.
+side effects (captions, sample grids, checkpoints, resume), neither -> the caption visualiser.  Evaluation is outside
+this build's scope and says so instead of silently doing something else.
 Additions that the reference does not have, all explicit: `--train` forces the training mode whatever the yml says (the
-shipped yml has TRAIN.FLAG: False); `--synthetic` replaces the pickled dataset by the on-device synthetic one
+shipped yml has TRAIN.FLAG: False); `--visualize` selects the caption visualiser (visualize_wgan.py) whatever TRAIN.FLAG
+says, with `--interp N` rounds of interpolation sheets (the reference runs none) — without it TRAIN.FLAG: False still
+raises, so that no run of the shipped yml starts something the caller did not ask for; `--synthetic` replaces the pickled dataset by the on-device synthetic one
 (t2i_amd.data) for machines without the data; `--steps` / `--batch` override TRAIN.MAX_STEPS / TRAIN.BATCH_SIZE."""
 import argparse
 import os
@@ -42,7 +45,11 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--cfg', default=os.path.join(os.path.dirname(os.path.abspath(__file__)), 'cfg', 'flowers.yml'),
                     help='Relative path to the config of the model')
-    ap.add_argument('--train', action='store_true', help='train even if the yml says TRAIN.FLAG: False')
+    mode = ap.add_mutually_exclusive_group()
+    mode.add_argument('--train', action='store_true', help='train even if the yml says TRAIN.FLAG: False')
+    mode.add_argument('--visualize', action='store_true', help='run the caption visualiser on the latest checkpoint (needs the '
+                      'pickled dataset)')
+    ap.add_argument('--interp', type=int, default=0, help='--visualize: rounds of interpolation / captioned sheets (default 0)')
     ap.add_argument('--synthetic', action='store_true', help='synthetic on-device dataset instead of cfg.DATASET_DIR')
     ap.add_argument('--steps', type=int, default=None, help='override TRAIN.MAX_STEPS')
     ap.add_argument('--batch', type=int, default=None, help='override TRAIN.BATCH_SIZE')
@@ -61,9 +68,17 @@ def main(argv=None):
     if cfg.EVAL.FLAG:
         raise NotImplementedError('EVAL.FLAG: Inception-score / FID evaluation (reference models/wgancls/eval_wgan.py) is '
                                   'outside the hot path this build covers; see DESIGN.md §7')
+    if args.visualize:
+        if args.synthetic:
+            raise ValueError('--visualize needs the pickled dataset (the neighbour search reads its uint8 image store); the '
+                             '--synthetic data set has none')
+        from t2i_amd.models.wgancls.visualize_wgan import WGanClsVisualizer
+        wgan = WGanCls(cfg, build_model=False)           # the visualiser creates and restores the generator's variables only
+        dataset = load_dataset(cfg, wgan.device)
+        return WGanClsVisualizer(sess=None, model=wgan, dataset=dataset, config=cfg).visualize(interp=args.interp)
     if not (cfg.TRAIN.FLAG or args.train):
-        raise NotImplementedError('TRAIN.FLAG is False: the reference would start its caption visualiser (visualize_wgan.py), '
-                                  'which is outside the hot path this build covers; pass --train or set TRAIN.FLAG: True')
+        raise NotImplementedError('TRAIN.FLAG is False: the reference would start its caption visualiser (visualize_wgan.py); '
+                                  'pass --visualize for it, or --train / TRAIN.FLAG: True to train')
 
     from t2i_amd import kernels as K
     K.filter_cache(os.environ.get('T2I_FILTER_CACHE', '1') != '0')     # weights change only through Adam / Saver here

@@ -30,6 +30,11 @@ def inverse_transform(images):
     return (np.asarray(images) + 1.) / 2.
 
 
+def denormalize_images(images):
+    """[-1,1] -> uint8 by truncation, ((x + 1) * 127.5).astype(uint8) (role of reference utils/utils.py denormalize_images)."""
+    return ((np.asarray(images) + 1.0) * 127.5).astype(np.uint8)
+
+
 def get_balanced_factorization(x):
     """(a, b) with a * b == x, a <= b and a as large as possible: the most square grid for x sample images (role of
     reference utils/utils.py:82-93)."""
