@@ -72,7 +72,7 @@ typedef struct t2i_conv_desc {
 enum { T2I_MATH_F32 = 0, T2I_MATH_BF16 = 1 };
 
 /* ---- library ------------------------------------------------------------------------------------------------ */
-int t2i_version(void);            /* ABI version, currently 10 (v10: t2i_nearest_images and t2i_nearest_images_workspace_bytes added — no existing signature changed; v9: t2i_conv_opts gained xform_valid_rows / xform_plane_rows, t2i_bn_train_fwd_grouped gained moving_groups, t2i_trunc_normal and t2i_zero_ranges added; v8: t2i_sigmoid_ce_head, t2i_bn_train_fwd_grouped, t2i_bn_bwd_grouped, t2i_bn_grouped_workspace_bytes added — no existing signature changed; v7: v7: t2i_conv2d_bwd_pair, t2i_row_scale_div, t2i_stat, t2i_filter_cache_assume added, t2i_adam_tf takes m == NULL at beta1 == 0 — no existing signature changed; v2: t2i_conv_desc.math; v3: caller-owned filter-cache arena,
+int t2i_version(void);            /* ABI version, currently 11 (v11: t2i_resample_bilinear, t2i_pool2d, t2i_channel_slice_copy, t2i_gram_accumulate and their workspace queries added — no existing signature changed; v10: t2i_nearest_images and t2i_nearest_images_workspace_bytes added — no existing signature changed; v9: t2i_conv_opts gained xform_valid_rows / xform_plane_rows, t2i_bn_train_fwd_grouped gained moving_groups, t2i_trunc_normal and t2i_zero_ranges added; v8: t2i_sigmoid_ce_head, t2i_bn_train_fwd_grouped, t2i_bn_bwd_grouped, t2i_bn_grouped_workspace_bytes added — no existing signature changed; v7: v7: t2i_conv2d_bwd_pair, t2i_row_scale_div, t2i_stat, t2i_filter_cache_assume added, t2i_adam_tf takes m == NULL at beta1 == 0 — no existing signature changed; v2: t2i_conv_desc.math; v3: caller-owned filter-cache arena,
                                    * t2i_tuning_set, t2i_kt_sgd; v4: t2i_filter_cache_refresh, bf16 operand images; v5: t2i_conv_opts
                                    * and explicit image arguments instead of thread-local one-shot hand-overs; v6: bf16 STORAGE —
                                    * activation tensors may be bf16 at this interface: t2i_dtype arguments, t2i_conv_opts.in_dtype /
@@ -460,6 +460,38 @@ size_t t2i_nearest_images_workspace_bytes(int32_t Q, int64_t N);
 int t2i_nearest_images(const uint8_t* src, int64_t N, int32_t S, const int32_t* row0, const int32_t* col0, const int32_t* flip,
                        const float* queries, int32_t Q, int32_t out_size, float lo, float hi, int32_t* idx, double* dist2,
                        void* ws, size_t ws_bytes, t2i_stream_t stream);
+
+/* ---- evaluator: Inception score and FID (reference evaluation/, utils/utils.py prep_incep_img) ------------------------- */
+/* Pillow's 8-bit bilinear Image.resize, bit for bit, of B images [Hi, Wi, 3] into [B, Ho, Wo, 3].  Image b is row rows[b] of
+ * the source store [N, Hi, Wi, 3] (rows == NULL: row b); a row outside [0, N) gives black.  src_f32 == 0: the store is uint8;
+ * src_f32 == 1: it is fp32 generator output in [-1, 1], read as ((x + 1) * 127.5).astype(uint8) (truncating, saturated to
+ * [0, 255]).  The filter tables are Pillow's precompute_coeffs + normalize_coeffs_8bpc for (Wi -> Wo) and (Hi -> Ho), made by
+ * the caller: xb int32 [Wo, 2] (first source column, tap count <= kx), xk int32 [Wo, kx] (22-bit fixed-point weights); yb / yk
+ * the same for rows.  Horizontal pass into a uint8 intermediate (workspace), then the vertical pass; every pass rounds with
+ * 2^21 and clips to [0, 255].  out_u8 == 0: y is fp32 u / 127.5 - 1; out_u8 == 1: y is the uint8 pixel. */
+size_t t2i_resample_bilinear_workspace_bytes(int32_t B, int32_t Hi, int32_t Wo);
+int t2i_resample_bilinear(const void* src, int32_t src_f32, int64_t N, int32_t Hi, int32_t Wi, const int32_t* rows, int32_t B,
+                          int32_t Ho, int32_t Wo, const int32_t* xb, const int32_t* xk, int32_t kx, const int32_t* yb,
+                          const int32_t* yk, int32_t ky, void* y, int32_t out_u8, void* ws, size_t ws_bytes, t2i_stream_t stream);
+
+/* TF max / average pooling of x [B, H, W, C] fp32 with a KH x KW window, strides SH, SW <= 4, TF SAME (same != 0) or VALID
+ * padding.  Output [B, Ho, Wo] pixels of C channels go to y[pixel * y_ld + y_c0 + c] (a channel slice of a concatenation
+ * buffer; y_c0 + C <= y_ld).  MAX ignores padded taps; AVG divides the fp32 sum of the in-bounds taps by their count, as TF
+ * does.  op: T2I_POOL_MAX or T2I_POOL_AVG. */
+enum { T2I_POOL_MAX = 0, T2I_POOL_AVG = 1 };
+int t2i_pool2d(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t KH, int32_t KW, int32_t SH, int32_t SW,
+               int32_t same, int32_t op, float* y, int32_t y_ld, int32_t y_c0, t2i_stream_t stream);
+
+/* y[r * y_ld + y_c0 + c] = x[r * C + c] for r < rows, c < C (y_c0 + C <= y_ld): one branch of a channel concatenation. */
+int t2i_channel_slice_copy(const float* x, int64_t rows, int32_t C, float* y, int32_t y_ld, int32_t y_c0, t2i_stream_t stream);
+
+/* FID statistics, streamed: for X fp32 [n, d] and a shift s fp32 [d], sum[j] += sum_k (double)(X[k][j] - s[j]) and
+ * G[i][j] += sum_k (X[k][i] - s[i]) (X[k][j] - s[j]) with sum fp64 [d] and G fp64 [d, d].  The products run on the fp32
+ * matrix pipe (exact fp32 fma chains over runs of 64 rows), the runs and the calls accumulate in fp64.  No atomics: results
+ * are bitwise identical from call to call.  The workspace query returns 0 (no scratch); ws may be NULL. */
+size_t t2i_gram_accumulate_workspace_bytes(int64_t n, int32_t d);
+int t2i_gram_accumulate(const float* X, int64_t n, int32_t d, const float* s, double* sum, double* G, void* ws, size_t ws_bytes,
+                        t2i_stream_t stream);
 
 #ifdef __cplusplus
 }

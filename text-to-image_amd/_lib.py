@@ -105,13 +105,20 @@ SIGNATURES = {
     't2i_gather_mean': (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _p, _i32, _i32, _p, _p]),
     't2i_nearest_images_workspace_bytes': (_sz, [_i32, _i64]),
     't2i_nearest_images': (ctypes.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _i32, _i32, _f, _f, _p, _p, _p, _sz, _p]),
+    't2i_resample_bilinear_workspace_bytes': (_sz, [_i32, _i32, _i32]),
+    't2i_resample_bilinear': (ctypes.c_int, [_p, _i32, _i64, _i32, _i32, _p, _i32, _i32, _i32, _p, _p, _i32, _p, _p, _i32, _p, _i32,
+                                             _p, _sz, _p]),
+    't2i_pool2d': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _p]),
+    't2i_channel_slice_copy': (ctypes.c_int, [_p, _i64, _i32, _p, _i32, _i32, _p]),
+    't2i_gram_accumulate_workspace_bytes': (_sz, [_i64, _i32]),
+    't2i_gram_accumulate': (ctypes.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _sz, _p]),
 }
 
 if not os.path.exists(LIB_PATH):
     raise ImportError('libt2i_hip.so not found at %s — build it with text-to-image_amd/csrc/build.sh '
                       '(or `python -c "import __graft_entry__ as g; g.build()"`); there is no CPU fallback' % LIB_PATH)
 
-ABI_VERSION = 10         # include/t2i_hip.h T2I_ABI_VERSION: argument lists changed in v5, v6 and v7 — symbols alone do not tell
+ABI_VERSION = 11         # include/t2i_hip.h T2I_ABI_VERSION: argument lists changed in v5, v6 and v7 — symbols alone do not tell
 
 lib = ctypes.CDLL(LIB_PATH)
 try:

@@ -55,6 +55,14 @@ hipError_t gather_mean_launch(const float*, int, int, const int32_t*, const int3
 size_t nearest_images_ws(int Q, int64_t N);
 hipError_t nearest_images_launch(const uint8_t*, int, int, const int32_t*, const int32_t*, const int32_t*, const float*, int, int, float,
                                  float, int32_t*, double*, void*, hipStream_t);
+// implemented in t2i_eval.hip
+size_t resample_bilinear_ws(int B, int Hi, int Wo);
+hipError_t resample_bilinear_launch(const void*, bool, int64_t, int, int, const int32_t*, int, int, int, const int32_t*,
+                                    const int32_t*, int, const int32_t*, const int32_t*, int, void*, bool, void*, hipStream_t);
+hipError_t pool2d_launch(const float*, int, int, int, int, int, int, int, int, int, int, int, int, bool, float*, int, int,
+                         hipStream_t);
+hipError_t channel_slice_copy_launch(const float*, int64_t, int, float*, int, int, hipStream_t);
+hipError_t gram_accumulate_launch(const float*, int, int, const float*, double*, double*, hipStream_t);
 hipError_t resample2_launch(bool, const float*, int, int, int, int, float, float*, hipStream_t);
 hipError_t row_moments_launch(const float*, const float*, int, int64_t, float*, float*, void*, hipStream_t);
 size_t row_moments_ws(int B);
@@ -676,7 +684,7 @@ using namespace t2i;
 
 extern "C" {
 
-int t2i_version(void) { return 10; }
+int t2i_version(void) { return 11; }
 
 const char* t2i_last_error(void) { return g_err; }
 
@@ -1464,6 +1472,76 @@ int t2i_nearest_images(const uint8_t* src, int64_t N, int32_t S, const int32_t* 
   return check(nearest_images_launch(src, (int)N, S, row0, col0, flip, queries, Q, out_size, lo, hi, idx, dist2, ws,
                                      (hipStream_t)stream),
                "t2i_nearest_images");
+}
+
+size_t t2i_resample_bilinear_workspace_bytes(int32_t B, int32_t Hi, int32_t Wo) {
+  return (B > 0 && Hi > 0 && Wo > 0) ? resample_bilinear_ws(B, Hi, Wo) : 0;
+}
+
+int t2i_resample_bilinear(const void* src, int32_t src_f32, int64_t N, int32_t Hi, int32_t Wi, const int32_t* rows, int32_t B,
+                          int32_t Ho, int32_t Wo, const int32_t* xb, const int32_t* xk, int32_t kx, const int32_t* yb,
+                          const int32_t* yk, int32_t ky, void* y, int32_t out_u8, void* ws, size_t ws_bytes, t2i_stream_t stream) {
+  if (!src || !xb || !xk || !yb || !yk || !y || (src_f32 != 0 && src_f32 != 1) || (out_u8 != 0 && out_u8 != 1) || N <= 0 ||
+      Hi <= 0 || Wi <= 0 || B <= 0 || B > 65535 || Ho <= 0 || Ho > 65535 || Wo <= 0 || kx <= 0 || ky <= 0 ||
+      (int64_t)Wo * 3 > INT32_MAX - 256 || (!rows && B > N)) {
+    set_error("t2i_resample_bilinear: bad argument (N=%lld B=%d %dx%d -> %dx%d, kx=%d ky=%d, src_f32=%d out_u8=%d, rows %s)",
+              (long long)N, B, Hi, Wi, Ho, Wo, kx, ky, src_f32, out_u8, rows ? "given" : "NULL");
+    return T2I_ERR_INVALID;
+  }
+  if (!ws || ws_bytes < resample_bilinear_ws(B, Hi, Wo)) {
+    set_error("t2i_resample_bilinear: workspace too small (%zu bytes, need %zu)", ws_bytes, resample_bilinear_ws(B, Hi, Wo));
+    return T2I_ERR_WORKSPACE;
+  }
+  return check(resample_bilinear_launch(src, src_f32 != 0, N, Hi, Wi, rows, B, Ho, Wo, xb, xk, kx, yb, yk, ky, y, out_u8 != 0, ws,
+                                        (hipStream_t)stream),
+               "t2i_resample_bilinear");
+}
+
+int t2i_pool2d(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t KH, int32_t KW, int32_t SH, int32_t SW,
+               int32_t same, int32_t op, float* y, int32_t y_ld, int32_t y_c0, t2i_stream_t stream) {
+  if (!x || !y || B <= 0 || H <= 0 || W <= 0 || C <= 0 || KH <= 0 || KW <= 0 || SH <= 0 || SH > 4 || SW <= 0 || SW > 4 ||
+      (op != T2I_POOL_MAX && op != T2I_POOL_AVG) || y_c0 < 0 || (int64_t)y_c0 + C > y_ld) {
+    set_error("t2i_pool2d: bad argument (B=%d %dx%dx%d, window %dx%d stride %dx%d, op %d, y_ld=%d y_c0=%d)", B, H, W, C, KH, KW,
+              SH, SW, op, y_ld, y_c0);
+    return T2I_ERR_INVALID;
+  }
+  int Ho, Wo, pt = 0, pl = 0;
+  if (same) {                                  // TF SAME: out = ceil(in / s), the odd padding pixel at the bottom / right
+    Ho = (H + SH - 1) / SH;
+    Wo = (W + SW - 1) / SW;
+    pt = ((Ho - 1) * SH + KH - H > 0 ? (Ho - 1) * SH + KH - H : 0) / 2;
+    pl = ((Wo - 1) * SW + KW - W > 0 ? (Wo - 1) * SW + KW - W : 0) / 2;
+  } else {
+    Ho = H >= KH ? (H - KH) / SH + 1 : 0;
+    Wo = W >= KW ? (W - KW) / SW + 1 : 0;
+  }
+  if (Ho <= 0 || Wo <= 0) {
+    set_error("t2i_pool2d: empty output for %dx%d input and a %dx%d VALID window", H, W, KH, KW);
+    return T2I_ERR_INVALID;
+  }
+  return check(pool2d_launch(x, B, H, W, C, KH, KW, SH, SW, pt, pl, Ho, Wo, op == T2I_POOL_MAX, y, y_ld, y_c0,
+                             (hipStream_t)stream),
+               "t2i_pool2d");
+}
+
+int t2i_channel_slice_copy(const float* x, int64_t rows, int32_t C, float* y, int32_t y_ld, int32_t y_c0, t2i_stream_t stream) {
+  if (!x || !y || rows <= 0 || C <= 0 || y_c0 < 0 || (int64_t)y_c0 + C > y_ld) {
+    set_error("t2i_channel_slice_copy: bad argument (rows=%lld C=%d y_ld=%d y_c0=%d)", (long long)rows, C, y_ld, y_c0);
+    return T2I_ERR_INVALID;
+  }
+  return check(channel_slice_copy_launch(x, rows, C, y, y_ld, y_c0, (hipStream_t)stream), "t2i_channel_slice_copy");
+}
+
+size_t t2i_gram_accumulate_workspace_bytes(int64_t n, int32_t d) { (void)n; (void)d; return 0; }
+
+int t2i_gram_accumulate(const float* X, int64_t n, int32_t d, const float* s, double* sum, double* G, void* ws, size_t ws_bytes,
+                        t2i_stream_t stream) {
+  (void)ws; (void)ws_bytes;
+  if (!X || !s || !sum || !G || n <= 0 || n > INT32_MAX || d <= 0 || d > 65535 * 64) {
+    set_error("t2i_gram_accumulate: bad argument (n=%lld d=%d)", (long long)n, d);
+    return T2I_ERR_INVALID;
+  }
+  return check(gram_accumulate_launch(X, (int)n, d, s, sum, G, (hipStream_t)stream), "t2i_gram_accumulate");
 }
 
 int t2i_gather_mean(const float* emb, int64_t N, int32_t En, int32_t D, const int32_t* ids, const int32_t* choice, int32_t B,

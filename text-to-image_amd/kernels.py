@@ -1126,6 +1126,100 @@ def nearest_images(src_u8, queries, row0=None, col0=None, flip=None, lo=-1.0, hi
     return idx.long(), dist2
 
 
+# ---- evaluator: Inception score and FID (reference evaluation/, utils/utils.py prep_incep_img) -------------------------------
+_RESAMPLE_TABLES = {}
+
+
+def _resample_tables(Hi, Wi, Ho, Wo, device):
+    key = (Hi, Wi, Ho, Wo, str(device))
+    hit = _RESAMPLE_TABLES.get(key)
+    if hit is None:
+        from .evaluation.resize import bilinear_tables
+        (xb, xk), (yb, yk) = bilinear_tables(Wi, Wo), bilinear_tables(Hi, Ho)
+        hit = _RESAMPLE_TABLES[key] = tuple(torch.from_numpy(t).to(device) for t in (xb, xk, yb, yk))
+    return hit
+
+
+def resample_bilinear(src, Ho, Wo, rows=None, out_u8=False, out=None):
+    """Pillow's bilinear Image.resize of a batch, bit for bit, then u / 127.5 - 1 (prep_incep_img).  src [N,Hi,Wi,3]: uint8, or
+    float32 generator output in [-1, 1] read as ((x + 1) * 127.5).astype(uint8) (denormalize_images).  rows int [B]: the store
+    rows to take, in order (None: all N).  -> float32 [B,Ho,Wo,3] in [-1, 1], or the uint8 pixels with out_u8 (written into `out`
+    if given: contiguous, that shape and dtype)."""
+    if src.dtype not in (torch.uint8, torch.float32) or src.dim() != 4 or src.shape[3] != 3:
+        raise ValueError('resample_bilinear expects a uint8 or float32 [N,H,W,3] store, got %s %s' % (src.dtype, tuple(src.shape)))
+    if not src.is_contiguous():
+        raise ValueError('resample_bilinear: the store must be contiguous')
+    N, Hi, Wi = src.shape[0], src.shape[1], src.shape[2]
+    B = N if rows is None else rows.numel()
+    shape, dt = (B, Ho, Wo, 3), torch.uint8 if out_u8 else torch.float32
+    y = torch.empty(shape, dtype=dt, device=src.device) if out is None else out
+    if tuple(y.shape) != shape or y.dtype != dt or not y.is_contiguous() or y.device != src.device:
+        raise ValueError('resample_bilinear: out must be a contiguous %s %s on %s' % (dt, shape, src.device))
+    if _live(src) and B > 0:
+        xb, xk, yb, yk = _resample_tables(Hi, Wi, Ho, Wo, src.device)
+        r = rows.to(device=src.device, dtype=torch.int32).contiguous() if rows is not None else None
+        wsp, wsn = _ws_args(src, int(lib.t2i_resample_bilinear_workspace_bytes(B, Hi, Wo)))
+        check(lib.t2i_resample_bilinear(_ptr(src), int(src.dtype == torch.float32), N, Hi, Wi, _ptr(r), B, Ho, Wo, _ptr(xb), _ptr(xk),
+                                        xk.shape[1], _ptr(yb), _ptr(yk), yk.shape[1], _ptr(y), int(out_u8), wsp, wsn, _stream()),
+              't2i_resample_bilinear')
+    return y
+
+
+POOL_MAX, POOL_AVG = 0, 1
+
+
+def pool_out_size(n, k, s, padding):
+    """TF's output extent of a pooling window (and of a conv)."""
+    if padding.upper() == 'SAME':
+        return -(-n // s)
+    if padding.upper() == 'VALID':
+        return (n - k) // s + 1
+    raise ValueError('Invalid padding %s' % padding)
+
+
+def pool2d(x, KH, KW, SH, SW, padding, op, out=None, c0=0):
+    """TF max_pool / avg_pool of x [B,H,W,C] float32.  out None: a new [B,Ho,Wo,C]; else a contiguous [B,Ho,Wo,ld] float32 whose
+    channels [c0, c0 + C) receive the result (one branch of a concatenation).  -> the written tensor."""
+    _chk(x, 'x', f32=True)
+    B, H, W, C = x.shape
+    Ho, Wo = pool_out_size(H, KH, SH, padding), pool_out_size(W, KW, SW, padding)
+    if out is None:
+        out = torch.empty((B, Ho, Wo, C), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape[:3]) != (B, Ho, Wo) or out.dim() != 4 or c0 + C > out.shape[3]:
+        raise ValueError('pool2d: output %s cannot take [%d,%d,%d] x %d channels at %d' % (tuple(out.shape), B, Ho, Wo, C, c0))
+    _chk(out, 'out', f32=True)
+    if _live(x):
+        check(lib.t2i_pool2d(_ptr(x), B, H, W, C, KH, KW, SH, SW, int(padding.upper() == 'SAME'), op, _ptr(out), out.shape[3], c0,
+                             _stream()), 't2i_pool2d')
+    return out
+
+
+def channel_slice_copy(x, out, c0):
+    """x [..., C] float32 into channels [c0, c0 + C) of out [..., ld] (same leading shape): a concatenation branch."""
+    _chk(x, 'x', f32=True); _chk(out, 'out', f32=True)
+    C, ld = x.shape[-1], out.shape[-1]
+    if tuple(x.shape[:-1]) != tuple(out.shape[:-1]) or c0 < 0 or c0 + C > ld:
+        raise ValueError('channel_slice_copy: %s into channels %d.. of %s' % (tuple(x.shape), c0, tuple(out.shape)))
+    rows = x.numel() // C
+    if _live(x) and rows > 0:
+        check(lib.t2i_channel_slice_copy(_ptr(x), rows, C, _ptr(out), ld, c0, _stream()), 't2i_channel_slice_copy')
+    return out
+
+
+def gram_accumulate(X, s, sum64, G64):
+    """sum64 [d] += sum_k (X[k] - s) and G64 [d,d] += (X - s)^T (X - s), fp64 accumulators, X [n,d] and s [d] float32."""
+    _chk(X, 'X', f32=True); _chk(s, 's', f32=True)
+    n, d = X.shape
+    if tuple(s.shape) != (d,) or tuple(sum64.shape) != (d,) or tuple(G64.shape) != (d, d) or sum64.dtype != torch.float64 or \
+            G64.dtype != torch.float64 or not (sum64.is_contiguous() and G64.is_contiguous()):
+        raise ValueError('gram_accumulate: X %s, s %s, sum %s %s, G %s %s' % (tuple(X.shape), tuple(s.shape), sum64.dtype,
+                                                                           tuple(sum64.shape), G64.dtype, tuple(G64.shape)))
+    if _live(X) and n > 0:
+        wsp, wsn = _ws_args(X, int(lib.t2i_gram_accumulate_workspace_bytes(n, d)))
+        check(lib.t2i_gram_accumulate(_ptr(X), n, d, _ptr(s), _ptr(sum64), _ptr(G64), wsp, wsn, _stream()), 't2i_gram_accumulate')
+    return sum64, G64
+
+
 def gather_mean(emb, ids, choice):
     """emb [N,En,D] float32; ids int32 [B]; choice int32 [B,k] -> [B,D] mean of the chosen rows, in choice order."""
     _chk(emb, 'emb')

@@ -1,17 +1,18 @@
 """Entry point of the wgancls model — reference models/wgancls/run.py:13-74.
 
-    python -m t2i_amd.models.wgancls.run --cfg <yaml> [--train | --visualize [--interp N]] [--synthetic] [--steps N] [--batch B]
-                                         [--graphs 0|1]
+    python -m t2i_amd.models.wgancls.run --cfg <yaml> [--train | --visualize [--interp N] | --eval is|fid [--incep-batch N]]
+                                         [--synthetic] [--steps N] [--batch B] [--graphs 0|1]
 
 Behaviour of the reference's main(): read the config, create CHECKPOINT_DIR / SAMPLE_DIR / LOGS_DIR, load the pickled
 dataset from cfg.DATASET_DIR (`TextDataset(datadir, 64)`, splits `<datadir>/test` and `<datadir>/train`), then switch on
 the mode flags: EVAL.FLAG -> Inception-score evaluation, TRAIN.FLAG -> `WGanClsTrainer(...).train()` with its periodic
-side effects (captions, sample grids, checkpoints, resume), neither -> the caption visualiser.  Evaluation is outside
-this build's scope and says so instead of silently doing something else.
+side effects (captions, sample grids, checkpoints, resume), neither -> the caption visualiser.
 Additions that the reference does not have, all explicit: `--train` forces the training mode whatever the yml says (the
 shipped yml has TRAIN.FLAG: False); `--visualize` selects the caption visualiser (visualize_wgan.py) whatever TRAIN.FLAG
 says, with `--interp N` rounds of interpolation sheets (the reference runs none) — without it TRAIN.FLAG: False still
-raises, so that no run of the shipped yml starts something the caller did not ask for; `--synthetic` replaces the pickled dataset by the on-device synthetic one
+raises, so that no run of the shipped yml starts something the caller did not ask for; `--eval is|fid` runs the
+Inception-score or FID evaluator (eval_wgan.py) whatever EVAL.FLAG says, with `--incep-batch N` overriding
+EVAL.INCEP_BATCH_SIZE — EVAL.FLAG: True without it still raises, for the same reason; `--synthetic` replaces the pickled dataset by the on-device synthetic one
 (t2i_amd.data) for machines without the data; `--steps` / `--batch` override TRAIN.MAX_STEPS / TRAIN.BATCH_SIZE."""
 import argparse
 import os
@@ -49,6 +50,9 @@ def main(argv=None):
     mode.add_argument('--train', action='store_true', help='train even if the yml says TRAIN.FLAG: False')
     mode.add_argument('--visualize', action='store_true', help='run the caption visualiser on the latest checkpoint (needs the '
                       'pickled dataset)')
+    mode.add_argument('--eval', choices=('is', 'fid'), default=None, help='run the Inception-score or FID evaluator on the latest '
+                      'checkpoint (needs the pickled dataset and an Inception checkpoint in EVAL.INCEP_CHECKPOINT_DIR)')
+    ap.add_argument('--incep-batch', type=int, default=None, help='--eval: Inception batch size (default EVAL.INCEP_BATCH_SIZE)')
     ap.add_argument('--interp', type=int, default=0, help='--visualize: rounds of interpolation / captioned sheets (default 0)')
     ap.add_argument('--synthetic', action='store_true', help='synthetic on-device dataset instead of cfg.DATASET_DIR')
     ap.add_argument('--steps', type=int, default=None, help='override TRAIN.MAX_STEPS')
@@ -65,9 +69,20 @@ def main(argv=None):
         if not os.path.exists(d):
             os.makedirs(d)
 
+    if args.incep_batch is not None and (not args.eval or args.incep_batch <= 0):
+        raise ValueError('--incep-batch takes a positive batch size and needs --eval (got %r)' % args.incep_batch)
+    if args.eval:
+        if args.synthetic:
+            raise ValueError('--eval needs the pickled dataset (embeddings are drawn from its test split); the --synthetic data '
+                             'set has none')
+        from t2i_amd.models.wgancls.eval_wgan import WGanClsEval
+        wgan = WGanCls(cfg, build_model=False)           # the evaluator creates and restores the generator's variables only
+        dataset = load_dataset(cfg, wgan.device)
+        ev = WGanClsEval(sess=None, model=wgan, dataset=dataset, cfg=cfg, incep_batch_size=args.incep_batch)
+        return ev.evaluate_inception() if args.eval == 'is' else ev.evaluate_fid()
     if cfg.EVAL.FLAG:
-        raise NotImplementedError('EVAL.FLAG: Inception-score / FID evaluation (reference models/wgancls/eval_wgan.py) is '
-                                  'outside the hot path this build covers; see DESIGN.md §7')
+        raise NotImplementedError('EVAL.FLAG: pass --eval is or --eval fid to run the Inception-score / FID evaluation '
+                                  '(reference models/wgancls/eval_wgan.py)')
     if args.visualize:
         if args.synthetic:
             raise ValueError('--visualize needs the pickled dataset (the neighbour search reads its uint8 image store); the '
