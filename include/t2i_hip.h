@@ -72,7 +72,7 @@ typedef struct t2i_conv_desc {
 enum { T2I_MATH_F32 = 0, T2I_MATH_BF16 = 1 };
 
 /* ---- library ------------------------------------------------------------------------------------------------ */
-int t2i_version(void);            /* ABI version, currently 11 (v11: t2i_resample_bilinear, t2i_pool2d, t2i_channel_slice_copy, t2i_gram_accumulate and their workspace queries added — no existing signature changed; v10: t2i_nearest_images and t2i_nearest_images_workspace_bytes added — no existing signature changed; v9: t2i_conv_opts gained xform_valid_rows / xform_plane_rows, t2i_bn_train_fwd_grouped gained moving_groups, t2i_trunc_normal and t2i_zero_ranges added; v8: t2i_sigmoid_ce_head, t2i_bn_train_fwd_grouped, t2i_bn_bwd_grouped, t2i_bn_grouped_workspace_bytes added — no existing signature changed; v7: v7: t2i_conv2d_bwd_pair, t2i_row_scale_div, t2i_stat, t2i_filter_cache_assume added, t2i_adam_tf takes m == NULL at beta1 == 0 — no existing signature changed; v2: t2i_conv_desc.math; v3: caller-owned filter-cache arena,
+int t2i_version(void);            /* ABI version, currently 12 (v12: t2i_pool_dropout, t2i_softmax_ce_head (+ workspace query), t2i_pooled_grad_scatter and t2i_rmsprop_tf added — no existing signature changed; v11: t2i_resample_bilinear, t2i_pool2d, t2i_channel_slice_copy, t2i_gram_accumulate and their workspace queries added — no existing signature changed; v10: t2i_nearest_images and t2i_nearest_images_workspace_bytes added — no existing signature changed; v9: t2i_conv_opts gained xform_valid_rows / xform_plane_rows, t2i_bn_train_fwd_grouped gained moving_groups, t2i_trunc_normal and t2i_zero_ranges added; v8: t2i_sigmoid_ce_head, t2i_bn_train_fwd_grouped, t2i_bn_bwd_grouped, t2i_bn_grouped_workspace_bytes added — no existing signature changed; v7: v7: t2i_conv2d_bwd_pair, t2i_row_scale_div, t2i_stat, t2i_filter_cache_assume added, t2i_adam_tf takes m == NULL at beta1 == 0 — no existing signature changed; v2: t2i_conv_desc.math; v3: caller-owned filter-cache arena,
                                    * t2i_tuning_set, t2i_kt_sgd; v4: t2i_filter_cache_refresh, bf16 operand images; v5: t2i_conv_opts
                                    * and explicit image arguments instead of thread-local one-shot hand-overs; v6: bf16 STORAGE —
                                    * activation tensors may be bf16 at this interface: t2i_dtype arguments, t2i_conv_opts.in_dtype /
@@ -492,6 +492,33 @@ int t2i_channel_slice_copy(const float* x, int64_t rows, int32_t C, float* y, in
 size_t t2i_gram_accumulate_workspace_bytes(int64_t n, int32_t d);
 int t2i_gram_accumulate(const float* X, int64_t n, int32_t d, const float* s, double* sum, double* G, void* ws, size_t ws_bytes,
                         t2i_stream_t stream);
+
+/* ---- InceptionV3 fine-tuning (reference models/inception/trainer.py) -------------------------------------------------- */
+/* AvgPool_1a_8x8 + Dropout_1b of slim inception_v3(is_training=True): x fp32 [B, HW, D] (the Mixed_7c output, HW = 64) ->
+ * pre[b, d] = (sum_p x[b, p, d]) / HW (fp32, taps in order: t2i_pool2d's AVG), mask[b, d] = floor(keep + U) in {0, 1} and
+ * y[b, d] = pre / keep * mask (tf.nn.dropout).  U in [0, 1) has 24 bits from Philox4x32-10 with key seed and counter
+ * (element / 4, step): the mask is a pure function of (seed, step, b, d).  D % 4 == 0, 16-byte aligned tensors. */
+int t2i_pool_dropout(const float* x, int32_t B, int32_t HW, int32_t D, float keep, uint64_t seed, uint64_t step, float* pre,
+                     float* mask, float* y, t2i_stream_t stream);
+/* The logits head and its mean sparse softmax cross-entropy, forward and backward, in two launches: logits = y W + bias
+ * (y fp32 [B, D], W [D, C], bias [C], labels int32 [B] in [0, C)), prob = softmax(logits), loss[0] = mean_b (logsumexp -
+ * logit[label]), acc[0] = mean_b (argmax prob == label; the first maximum), and with dz = (prob - onehot) / B: dW = y^T dz,
+ * db = colsum dz (accumulate != 0: +=), dy = dz W^T.  Each output element is summed by one thread in a fixed order: no
+ * atomics, bitwise-repeatable.  Any C <= 1024 with B * C <= 16384; D <= 16384. */
+size_t t2i_softmax_ce_head_workspace_bytes(int32_t B, int32_t C);
+int t2i_softmax_ce_head(const float* y, const float* W, const float* bias, const int32_t* labels, int32_t B, int32_t D, int32_t C,
+                        float* logits, float* prob, float* loss, float* acc, float* dW, float* db, int32_t accumulate, float* dy,
+                        void* ws, size_t ws_bytes, t2i_stream_t stream);
+/* Gradient of the n <= T2I_MAX_SCATTER_BRANCHES Mixed_7c branch outputs from the gradient g [B, D] of the dropout output:
+ * outs[i] [B, HW, C[i]] (device pointers in a HOST array) receives g[b, c0[i] + c] * mask[b, c0[i] + c] / keep / HW at every
+ * pixel — the backward of t2i_pool_dropout, sliced into the branches of the concatenation.  C[i] % 4 == 0, c0[i] % 4 == 0. */
+#define T2I_MAX_SCATTER_BRANCHES 8
+int t2i_pooled_grad_scatter(const float* g, const float* mask, int32_t B, int32_t HW, int32_t D, float keep, int32_t n,
+                            float* const* outs, const int32_t* c0, const int32_t* C, t2i_stream_t stream);
+/* tf.train.RMSPropOptimizer (ApplyRMSProp) over a flat arena of n floats: ms += (g^2 - ms)(1 - rho);
+ * mom = momentum * mom + lr * g / sqrt(ms + eps); w -= mom.  One launch. */
+int t2i_rmsprop_tf(float* w, const float* g, float* ms, float* mom, int64_t n, float lr, float rho, float momentum, float eps,
+                   t2i_stream_t stream);
 
 #ifdef __cplusplus
 }

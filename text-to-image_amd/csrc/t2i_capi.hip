@@ -63,6 +63,15 @@ hipError_t pool2d_launch(const float*, int, int, int, int, int, int, int, int, i
                          hipStream_t);
 hipError_t channel_slice_copy_launch(const float*, int64_t, int, float*, int, int, hipStream_t);
 hipError_t gram_accumulate_launch(const float*, int, int, const float*, double*, double*, hipStream_t);
+// implemented in t2i_incep_train.hip
+size_t softmax_ce_head_ws(int B, int C);
+hipError_t pool_dropout_launch(const float*, int, int, int, float, unsigned long long, unsigned long long, float*, float*, float*,
+                               hipStream_t);
+hipError_t softmax_ce_head_launch(const float*, const float*, const float*, const int32_t*, int, int, int, float*, float*, float*,
+                                  float*, float*, int, float*, float*, void*, hipStream_t);
+hipError_t pooled_grad_scatter_launch(const float*, const float*, int, int, int, float, int, float* const*, const int32_t*,
+                                      const int32_t*, hipStream_t);
+hipError_t rmsprop_tf_launch(float*, const float*, float*, float*, int64_t, float, float, float, float, hipStream_t);
 hipError_t resample2_launch(bool, const float*, int, int, int, int, float, float*, hipStream_t);
 hipError_t row_moments_launch(const float*, const float*, int, int64_t, float*, float*, void*, hipStream_t);
 size_t row_moments_ws(int B);
@@ -684,7 +693,7 @@ using namespace t2i;
 
 extern "C" {
 
-int t2i_version(void) { return 11; }
+int t2i_version(void) { return 12; }
 
 const char* t2i_last_error(void) { return g_err; }
 
@@ -1542,6 +1551,59 @@ int t2i_gram_accumulate(const float* X, int64_t n, int32_t d, const float* s, do
     return T2I_ERR_INVALID;
   }
   return check(gram_accumulate_launch(X, (int)n, d, s, sum, G, (hipStream_t)stream), "t2i_gram_accumulate");
+}
+
+int t2i_pool_dropout(const float* x, int32_t B, int32_t HW, int32_t D, float keep, uint64_t seed, uint64_t step, float* pre,
+                     float* mask, float* y, t2i_stream_t stream) {
+  if (!x || !pre || !mask || !y || B <= 0 || HW <= 0 || D <= 0 || D % 4 || !(keep > 0.f && keep <= 1.f) ||
+      (int64_t)B * HW * D > ((int64_t)1 << 40) || !aligned16(x) || !aligned16(pre) || !aligned16(mask) || !aligned16(y)) {
+    set_error("t2i_pool_dropout: bad argument (B=%d HW=%d D=%d keep=%g; D %% 4 == 0 and 16-byte aligned tensors)", B, HW, D, keep);
+    return T2I_ERR_INVALID;
+  }
+  return check(pool_dropout_launch(x, B, HW, D, keep, seed, step, pre, mask, y, (hipStream_t)stream), "t2i_pool_dropout");
+}
+
+size_t t2i_softmax_ce_head_workspace_bytes(int32_t B, int32_t C) { return (B > 0 && C > 0) ? softmax_ce_head_ws(B, C) : 0; }
+
+int t2i_softmax_ce_head(const float* y, const float* W, const float* bias, const int32_t* labels, int32_t B, int32_t D, int32_t C,
+                        float* logits, float* prob, float* loss, float* acc, float* dW, float* db, int32_t accumulate, float* dy,
+                        void* ws, size_t ws_bytes, t2i_stream_t stream) {
+  if (!y || !W || !bias || !labels || !logits || !prob || !loss || !acc || !dW || !db || !dy || B <= 0 || B > 65535 || D <= 0 ||
+      D > 16384 || C <= 0 || C > 1024 || (int64_t)B * C > 16384) {
+    set_error("t2i_softmax_ce_head: bad argument (B=%d D=%d C=%d; C <= 1024, B * C <= 16384, D <= 16384)", B, D, C);
+    return T2I_ERR_INVALID;
+  }
+  if (!ws || ws_bytes < softmax_ce_head_ws(B, C)) {
+    set_error("t2i_softmax_ce_head: workspace too small (%zu bytes, need %zu)", ws_bytes, softmax_ce_head_ws(B, C));
+    return T2I_ERR_WORKSPACE;
+  }
+  return check(softmax_ce_head_launch(y, W, bias, labels, B, D, C, logits, prob, loss, acc, dW, accumulate != 0, db, dy, ws,
+                                      (hipStream_t)stream),
+               "t2i_softmax_ce_head");
+}
+
+int t2i_pooled_grad_scatter(const float* g, const float* mask, int32_t B, int32_t HW, int32_t D, float keep, int32_t n,
+                            float* const* outs, const int32_t* c0, const int32_t* C, t2i_stream_t stream) {
+  bool ok = g && mask && outs && c0 && C && B > 0 && HW > 0 && D > 0 && D % 4 == 0 && keep > 0.f && n > 0 &&
+            n <= T2I_MAX_SCATTER_BRANCHES && aligned16(g) && aligned16(mask);
+  for (int i = 0; ok && i < n; ++i)
+    ok = outs[i] && aligned16(outs[i]) && C[i] > 0 && C[i] % 4 == 0 && c0[i] >= 0 && c0[i] % 4 == 0 && (int64_t)c0[i] + C[i] <= D &&
+         (int64_t)B * HW * (C[i] / 4) < ((int64_t)1 << 31) * 256;
+  if (!ok) {
+    set_error("t2i_pooled_grad_scatter: bad argument (B=%d HW=%d D=%d keep=%g n=%d; branch widths and offsets multiples of 4 "
+              "inside D, at most %d branches)", B, HW, D, keep, n, T2I_MAX_SCATTER_BRANCHES);
+    return T2I_ERR_INVALID;
+  }
+  return check(pooled_grad_scatter_launch(g, mask, B, HW, D, keep, n, outs, c0, C, (hipStream_t)stream), "t2i_pooled_grad_scatter");
+}
+
+int t2i_rmsprop_tf(float* w, const float* g, float* ms, float* mom, int64_t n, float lr, float rho, float momentum, float eps,
+                   t2i_stream_t stream) {
+  if (!w || !g || !ms || !mom || n <= 0) {
+    set_error("t2i_rmsprop_tf: bad argument (n=%lld)", (long long)n);
+    return T2I_ERR_INVALID;
+  }
+  return check(rmsprop_tf_launch(w, g, ms, mom, n, lr, rho, momentum, eps, (hipStream_t)stream), "t2i_rmsprop_tf");
 }
 
 int t2i_gather_mean(const float* emb, int64_t N, int32_t En, int32_t D, const int32_t* ids, const int32_t* choice, int32_t B,

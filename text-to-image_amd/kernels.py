@@ -1492,3 +1492,76 @@ def lerp_dev(a, b, t_dev, mode=0):
         check(lib.t2i_lerp_dev(_ptr(a), _ptr(_chk(b, 'b') if b is not None else None), _ptr(_chk(t_dev, 't')), mode, a.numel(), _ptr(out),
                                _stream()), 't2i_lerp_dev')
     return out
+
+
+# ---- InceptionV3 fine-tuning (t2i_incep_train.hip) ------------------------------------------------------------------------
+def pool_dropout(x, keep, seed, step):
+    """AvgPool_1a_8x8 + Dropout_1b: x [B, H, W, D] float32 -> (pre [B, D], mask [B, D] of 0 / 1, y = pre / keep * mask); the mask is a
+    pure function of (seed, step, b, d)."""
+    _chk(x, 'x', f32=True)
+    B, D = x.shape[0], x.shape[-1]
+    HW = x.numel() // (B * D)
+    pre, mask, y = (torch.empty((B, D), dtype=torch.float32, device=x.device) for _ in range(3))
+    if _live(x):
+        check(lib.t2i_pool_dropout(_ptr(x), B, HW, D, float(keep), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF,
+                                   _ptr(pre), _ptr(mask), _ptr(y), _stream()), 't2i_pool_dropout')
+    return pre, mask, y
+
+
+def softmax_ce_head(y, W, bias, labels, dW_out=None, db_out=None, accumulate=False):
+    """Logits head + mean sparse softmax cross-entropy, forward and backward (two launches).  y [B, D], W [D, C] (or the
+    [1, 1, D, C] conv filter), bias [C], labels int32 [B] -> dict(logits, prob, loss [1], acc [1], dW, db, dy [B, D]).  dW_out /
+    db_out: gradient-arena slots to write (accumulate: add) into."""
+    _chk(y, 'y', f32=True); _chk(W, 'W', f32=True); _chk(bias, 'bias', f32=True)
+    B, D = y.shape
+    C = bias.numel()
+    if W.numel() != D * C or labels.dtype != torch.int32 or labels.numel() != B:
+        raise ValueError('softmax_ce_head: y %s, W %s, bias %s, labels %s %s' % (tuple(y.shape), tuple(W.shape), tuple(bias.shape),
+                                                                                  labels.dtype, tuple(labels.shape)))
+    labels = labels.contiguous()
+    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=y.device)       # noqa: E731
+    out = dict(logits=f(B, C), prob=f(B, C), loss=f(1), acc=f(1), dy=f(B, D))
+    out['dW'] = dW_out if dW_out is not None else f(D, C)
+    out['db'] = db_out if db_out is not None else f(C)
+    assert out['dW'].numel() == D * C and out['db'].numel() == C
+    _drop_image(out['dW'])
+    if _live(y):
+        wsp, wsn = _ws_args(y, int(lib.t2i_softmax_ce_head_workspace_bytes(B, C)))
+        check(lib.t2i_softmax_ce_head(_ptr(y), _ptr(W), _ptr(bias), _ptr(labels), B, D, C, _ptr(out['logits']), _ptr(out['prob']),
+                                      _ptr(out['loss']), _ptr(out['acc']), _ptr(out['dW']), _ptr(out['db']), 1 if accumulate else 0,
+                                      _ptr(out['dy']), wsp, wsn, _stream()), 't2i_softmax_ce_head')
+    return out
+
+
+def pooled_grad_scatter(g, mask, keep, outs, c0s, HW):
+    """Backward of pool_dropout into the branches of a concatenation: outs[i] [B, H, W, C_i] (contiguous float32) =
+    g[:, c0s[i]:c0s[i] + C_i] * mask / keep / HW at every pixel.  One launch."""
+    _chk(g, 'g', f32=True); _chk(mask, 'mask', f32=True)
+    B, D = g.shape
+    n = len(outs)
+    if n != len(c0s) or not 0 < n <= MAX_SCATTER_BRANCHES:
+        raise ValueError('pooled_grad_scatter: %d outputs, %d offsets' % (n, len(c0s)))
+    for o in outs:
+        _chk(o, 'out', f32=True)
+        if o.shape[0] != B or o.numel() != B * HW * o.shape[-1]:
+            raise ValueError('pooled_grad_scatter: output %s for B=%d HW=%d' % (tuple(o.shape), B, HW))
+    if _live(g):
+        ptrs = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
+        c0 = (ctypes.c_int32 * n)(*[int(c) for c in c0s])
+        cb = (ctypes.c_int32 * n)(*[int(o.shape[-1]) for o in outs])
+        check(lib.t2i_pooled_grad_scatter(_ptr(g), _ptr(mask), B, int(HW), D, float(keep), n, ptrs, c0, cb, _stream()),
+              't2i_pooled_grad_scatter')
+    return outs
+
+
+MAX_SCATTER_BRANCHES = 8          # T2I_MAX_SCATTER_BRANCHES
+
+
+def rmsprop_tf(w, g, ms, mom, lr, rho=0.9, momentum=0.0, eps=1e-10):
+    """tf.train.RMSPropOptimizer's update in place on flat arenas, one launch."""
+    for t in (w, g, ms, mom):
+        _chk(t, f32=True)
+    assert w.numel() == g.numel() == ms.numel() == mom.numel()
+    if _live(w):
+        check(lib.t2i_rmsprop_tf(_ptr(w), _ptr(g), _ptr(ms), _ptr(mom), w.numel(), float(lr), float(rho), float(momentum), float(eps),
+                                 _stream()), 't2i_rmsprop_tf')

@@ -201,3 +201,31 @@ class AdamTF(object):
     def step(self, lr, grad_scale=1.0):
         self.prepare(lr)
         self.apply(grad_scale)
+
+
+class RMSPropTF(object):
+    """tf.train.RMSPropOptimizer(lr, decay=0.9, momentum=0.0, epsilon=1e-10) over an Arena (reference
+    models/inception/trainer.py): ms += (g^2 - ms)(1 - decay); mom = momentum * mom + lr g / sqrt(ms + eps); w -= mom, one launch
+    (t2i_rmsprop_tf).  The `rms` slot starts at ONES (the TF 1.x initial value), `momentum` at zeros.  Checkpoints keep them under
+    TF's slot names `<variable>/RMSProp` and `<variable>/RMSProp_1` (slots / slot_key: utils/saver.py)."""
+
+    def __init__(self, arena, lr=5e-5, decay=0.9, momentum=0.0, eps=1e-10):
+        self.arena, self.lr, self.decay, self.momentum, self.eps = arena, lr, decay, momentum, eps
+        self.ms = torch.ones_like(arena.flat)
+        self.mom = torch.zeros_like(arena.flat)
+
+    def slots(self):
+        """slot name -> flat buffer over the arena, in TF's slot order."""
+        return OrderedDict([('RMSProp', self.ms), ('RMSProp_1', self.mom)])
+
+    @staticmethod
+    def slot_key(oname, var, slot):
+        """TF names an optimizer slot after its variable alone (`InceptionV3/Logits/Conv2d_1c_1x1/weights/RMSProp`)."""
+        return '%s/%s' % (var, slot)
+
+    def step(self, lr=None):
+        """One update of every variable of the arena from its gradient slot; the cached filter images of the arena are dropped."""
+        self.arena.finish_step()
+        K.rmsprop_tf(self.arena.flat, self.arena.grad, self.ms, self.mom, self.lr if lr is None else lr, self.decay, self.momentum, self.eps)
+        if self.arena.flat.is_cuda:
+            K.filter_cache_invalidate(self.arena.flat, external=False)

@@ -3,7 +3,8 @@
 On-disk format: one `<prefix>-<step>.npz` per checkpoint holding every variable of the store under its TF name
 (`d_net/Conv_3/weights`, `g_net/BatchNorm_4/moving_mean`, ... — conv kernels HWIO, deconv [kh,kw,Cout,Cin], dense
 [in,out], i.e. exactly the key space and layouts of the reference's TF checkpoints, so arrays dumped from a real TF run
-load unchanged), plus optimizer slots under `<opt>/<name>/Adam` and `/Adam_1`, the step counts `<opt>/t` and whatever
+load unchanged), plus optimizer slots under `<opt>/<name>/Adam` and `/Adam_1` and the step counts `<opt>/t` (an optimizer with `slots()` names its own
+slots through `slot_key`: optim.RMSPropTF writes TF's `<name>/RMSProp` and `/RMSProp_1`) and whatever
 scalars the trainer registers through `extra` (wgancls: `kt` and `global_step`); and a `checkpoint` text file naming the latest one (what tf.train.get_checkpoint_state reads).  `load`
 returns (found, counter) with the counter parsed from the file name like the reference does."""
 import os
@@ -30,6 +31,12 @@ class Saver(object):
         out = {n: v.detach().cpu().numpy() for n, v in self._selected()}
         for oname, opt in self.optimizers.items():
             a = opt.arena
+            if hasattr(opt, 'slots'):            # an optimizer that names its own slots (optim.RMSPropTF)
+                for n in a.names:
+                    o, k = a.offsets[n]
+                    for slot, buf in opt.slots().items():
+                        out[opt.slot_key(oname, n, slot)] = buf[o:o + k].view(a.vars[n].shape).cpu().numpy()
+                continue
             for n in a.names:
                 o, k = a.offsets[n]
                 out['%s/%s/Adam' % (oname, n)] = opt.m[o:o + k].view(a.vars[n].shape).cpu().numpy()
@@ -50,6 +57,15 @@ class Saver(object):
                 v.copy_(torch.from_numpy(z[n]).to(v.device))
             for oname, opt in self.optimizers.items():
                 a = opt.arena
+                if hasattr(opt, 'slots'):
+                    for n in a.names:
+                        o, k = a.offsets[n]
+                        for slot, buf in opt.slots().items():
+                            key = opt.slot_key(oname, n, slot)
+                            if key not in z.files:
+                                raise KeyError('checkpoint %s has no optimizer slot %s' % (path, key))
+                            buf[o:o + k].copy_(torch.from_numpy(z[key]).reshape(-1).to(buf.device))
+                    continue
                 for n in a.names:
                     o, k = a.offsets[n]
                     if '%s/%s/Adam' % (oname, n) in z.files:
