@@ -72,7 +72,7 @@ typedef struct t2i_conv_desc {
 enum { T2I_MATH_F32 = 0, T2I_MATH_BF16 = 1 };
 
 /* ---- library ------------------------------------------------------------------------------------------------ */
-int t2i_version(void);            /* ABI version, currently 12 (v12: t2i_pool_dropout, t2i_softmax_ce_head (+ workspace query), t2i_pooled_grad_scatter and t2i_rmsprop_tf added — no existing signature changed; v11: t2i_resample_bilinear, t2i_pool2d, t2i_channel_slice_copy, t2i_gram_accumulate and their workspace queries added — no existing signature changed; v10: t2i_nearest_images and t2i_nearest_images_workspace_bytes added — no existing signature changed; v9: t2i_conv_opts gained xform_valid_rows / xform_plane_rows, t2i_bn_train_fwd_grouped gained moving_groups, t2i_trunc_normal and t2i_zero_ranges added; v8: t2i_sigmoid_ce_head, t2i_bn_train_fwd_grouped, t2i_bn_bwd_grouped, t2i_bn_grouped_workspace_bytes added — no existing signature changed; v7: v7: t2i_conv2d_bwd_pair, t2i_row_scale_div, t2i_stat, t2i_filter_cache_assume added, t2i_adam_tf takes m == NULL at beta1 == 0 — no existing signature changed; v2: t2i_conv_desc.math; v3: caller-owned filter-cache arena,
+int t2i_version(void);            /* ABI version, currently 13 (v13: t2i_cosine_distance added — no existing signature changed; v12: t2i_pool_dropout, t2i_softmax_ce_head (+ workspace query), t2i_pooled_grad_scatter and t2i_rmsprop_tf added — no existing signature changed; v11: t2i_resample_bilinear, t2i_pool2d, t2i_channel_slice_copy, t2i_gram_accumulate and their workspace queries added — no existing signature changed; v10: t2i_nearest_images and t2i_nearest_images_workspace_bytes added — no existing signature changed; v9: t2i_conv_opts gained xform_valid_rows / xform_plane_rows, t2i_bn_train_fwd_grouped gained moving_groups, t2i_trunc_normal and t2i_zero_ranges added; v8: t2i_sigmoid_ce_head, t2i_bn_train_fwd_grouped, t2i_bn_bwd_grouped, t2i_bn_grouped_workspace_bytes added — no existing signature changed; v7: v7: t2i_conv2d_bwd_pair, t2i_row_scale_div, t2i_stat, t2i_filter_cache_assume added, t2i_adam_tf takes m == NULL at beta1 == 0 — no existing signature changed; v2: t2i_conv_desc.math; v3: caller-owned filter-cache arena,
                                    * t2i_tuning_set, t2i_kt_sgd; v4: t2i_filter_cache_refresh, bf16 operand images; v5: t2i_conv_opts
                                    * and explicit image arguments instead of thread-local one-shot hand-overs; v6: bf16 STORAGE —
                                    * activation tensors may be bf16 at this interface: t2i_dtype arguments, t2i_conv_opts.in_dtype /
@@ -491,6 +491,15 @@ int t2i_channel_slice_copy(const float* x, int64_t rows, int32_t C, float* y, in
  * are bitwise identical from call to call.  The workspace query returns 0 (no scratch); ws may be NULL. */
 size_t t2i_gram_accumulate_workspace_bytes(int64_t n, int32_t d);
 int t2i_gram_accumulate(const float* X, int64_t n, int32_t d, const float* s, double* sum, double* G, void* ws, size_t ws_bytes,
+                        t2i_stream_t stream);
+
+/* IMD (reference evaluation/imd.py): for n row pairs of a fp32 [n, d] (row stride lda >= d) and b fp32 [n, d] (ldb >= d),
+ * out[i] (fp64) = clip(1 - uv / sqrt(uu * vv), 0, 2) with uv = a_i . b_i, uu = |a_i|^2, vv = |b_i|^2 — scipy's
+ * spatial.distance.cosine — and NaN when uu or vv is 0.  Products and sums in fp64; one wave64 per pair, each lane a fixed
+ * stride of columns (16-byte reads where d, lda, ldb are multiples of 4 and a, b are 16-byte aligned), then a fixed-order
+ * butterfly across the wave: no atomics, bitwise-repeatable.  Any d.  Bad arguments (n <= 0, d <= 0, ld < d, a NULL
+ * pointer) return T2I_ERR_INVALID before anything is launched. */
+int t2i_cosine_distance(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t n, int32_t d, double* out,
                         t2i_stream_t stream);
 
 /* ---- InceptionV3 fine-tuning (reference models/inception/trainer.py) -------------------------------------------------- */

@@ -112,6 +112,7 @@ SIGNATURES = {
     't2i_channel_slice_copy': (ctypes.c_int, [_p, _i64, _i32, _p, _i32, _i32, _p]),
     't2i_gram_accumulate_workspace_bytes': (_sz, [_i64, _i32]),
     't2i_gram_accumulate': (ctypes.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _sz, _p]),
+    't2i_cosine_distance': (ctypes.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p]),
     't2i_pool_dropout': (ctypes.c_int, [_p, _i32, _i32, _i32, _f, ctypes.c_uint64, ctypes.c_uint64, _p, _p, _p, _p]),
     't2i_softmax_ce_head_workspace_bytes': (_sz, [_i32, _i32]),
     't2i_softmax_ce_head': (ctypes.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _sz, _p]),
@@ -124,7 +125,7 @@ if not os.path.exists(LIB_PATH):
     raise ImportError('libt2i_hip.so not found at %s — build it with text-to-image_amd/csrc/build.sh '
                       '(or `python -c "import __graft_entry__ as g; g.build()"`); there is no CPU fallback' % LIB_PATH)
 
-ABI_VERSION = 12         # include/t2i_hip.h T2I_ABI_VERSION: argument lists changed in v5, v6 and v7 — symbols alone do not tell
+ABI_VERSION = 13         # include/t2i_hip.h T2I_ABI_VERSION: argument lists changed in v5, v6 and v7 — symbols alone do not tell
 
 lib = ctypes.CDLL(LIB_PATH)
 try:

@@ -63,6 +63,7 @@ hipError_t pool2d_launch(const float*, int, int, int, int, int, int, int, int, i
                          hipStream_t);
 hipError_t channel_slice_copy_launch(const float*, int64_t, int, float*, int, int, hipStream_t);
 hipError_t gram_accumulate_launch(const float*, int, int, const float*, double*, double*, hipStream_t);
+hipError_t cosine_distance_launch(const float*, int64_t, const float*, int64_t, int64_t, int, double*, hipStream_t);
 // implemented in t2i_incep_train.hip
 size_t softmax_ce_head_ws(int B, int C);
 hipError_t pool_dropout_launch(const float*, int, int, int, float, unsigned long long, unsigned long long, float*, float*, float*,
@@ -693,7 +694,7 @@ using namespace t2i;
 
 extern "C" {
 
-int t2i_version(void) { return 12; }
+int t2i_version(void) { return 13; }
 
 const char* t2i_last_error(void) { return g_err; }
 
@@ -1551,6 +1552,16 @@ int t2i_gram_accumulate(const float* X, int64_t n, int32_t d, const float* s, do
     return T2I_ERR_INVALID;
   }
   return check(gram_accumulate_launch(X, (int)n, d, s, sum, G, (hipStream_t)stream), "t2i_gram_accumulate");
+}
+
+int t2i_cosine_distance(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t n, int32_t d, double* out,
+                        t2i_stream_t stream) {
+  if (!a || !b || !out || n <= 0 || n > INT32_MAX || d <= 0 || lda < d || ldb < d) {
+    set_error("t2i_cosine_distance: bad argument (n=%lld d=%d lda=%lld ldb=%lld, a %s, b %s, out %s)", (long long)n, d,
+              (long long)lda, (long long)ldb, a ? "given" : "NULL", b ? "given" : "NULL", out ? "given" : "NULL");
+    return T2I_ERR_INVALID;
+  }
+  return check(cosine_distance_launch(a, lda, b, ldb, n, d, out, (hipStream_t)stream), "t2i_cosine_distance");
 }
 
 int t2i_pool_dropout(const float* x, int32_t B, int32_t HW, int32_t D, float keep, uint64_t seed, uint64_t step, float* pre,

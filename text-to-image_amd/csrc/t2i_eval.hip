@@ -14,6 +14,9 @@
 //   gram_kernel / colsum_kernel   FID statistics: (X - s)^T (X - s) on the fp32 matrix pipe (v_mfma_f32_32x32x2_f32) and
 //                           sum (X - s), both added into fp64 accumulators.  Each output element is owned by one lane of one
 //                           workgroup and summed in a fixed order: no atomics, bitwise-repeatable.
+//   cosine_kernel           IMD (reference evaluation/imd.py, scipy.spatial.distance.cosine): one wave64 per row pair; each
+//                           lane sums u.v, u.u and v.v of a fixed stride of columns in fp64, then a fixed butterfly across
+//                           the wave.  No atomics, bitwise-repeatable.
 // The element-wise kernels read and write 16-byte vectors over channels where C % 4 == 0 (and the slice is aligned).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -215,6 +218,58 @@ __global__ __launch_bounds__(kThreads) void colsum_kernel(const float* __restric
   sum[j] += acc;
 }
 
+// ---- IMD: per-pair cosine distance -------------------------------------------------------------------------------------
+constexpr int kCosWaves = kThreads / 64;   // row pairs per workgroup
+
+__device__ __forceinline__ void cos_acc(float u, float v, double& uv, double& uu, double& vv) {
+  const double a = u, b = v;               // fp32 x fp32 is exact in fp64: fma or not, the same sum
+  uv += a * b;
+  uu += a * a;
+  vv += b * b;
+}
+
+// out[i] = clip(1 - a_i.b_i / sqrt(|a_i|^2 |b_i|^2), 0, 2), NaN if either norm is 0 (scipy's statement).  Lane l reads the
+// columns l, l + 64, ... (V == 4: the float4 columns), so a wave's loads are 64 consecutive elements (or 16-byte vectors).
+template <int V>
+__global__ __launch_bounds__(kThreads) void cosine_kernel(const float* __restrict__ a, int64_t lda, const float* __restrict__ b,
+                                                          int64_t ldb, int64_t n, int d, double* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * kCosWaves + (threadIdx.x >> 6);
+  if (row >= n) return;                    // whole wave: no barrier below
+  const float* pa = a + row * lda;
+  const float* pb = b + row * ldb;
+  double uv = 0.0, uu = 0.0, vv = 0.0;
+  if (V == 4) {
+    const float4* qa = reinterpret_cast<const float4*>(pa);
+    const float4* qb = reinterpret_cast<const float4*>(pb);
+    for (int k = lane; k < d / 4; k += 64) {
+      const float4 x = qa[k], y = qb[k];
+      cos_acc(x.x, y.x, uv, uu, vv);
+      cos_acc(x.y, y.y, uv, uu, vv);
+      cos_acc(x.z, y.z, uv, uu, vv);
+      cos_acc(x.w, y.w, uv, uu, vv);
+    }
+  } else {
+    for (int k = lane; k < d; k += 64) cos_acc(pa[k], pb[k], uv, uu, vv);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    uv += __shfl_xor(uv, off, 64);
+    uu += __shfl_xor(uu, off, 64);
+    vv += __shfl_xor(vv, off, 64);
+  }
+  if (lane == 0) {
+    double r;
+    if (uu == 0.0 || vv == 0.0) {
+      r = __longlong_as_double(0x7ff8000000000000LL);
+    } else {
+      r = 1.0 - uv / sqrt(uu * vv);
+      r = r < 0.0 ? 0.0 : (r > 2.0 ? 2.0 : r);
+    }
+    out[row] = r;
+  }
+}
+
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
@@ -275,6 +330,17 @@ hipError_t gram_accumulate_launch(const float* X, int n, int d, const float* s, 
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(colsum_kernel, dim3((d + kThreads - 1) / kThreads), dim3(kThreads), 0, stream, X, n, d, s, sum);
+  return hipGetLastError();
+}
+
+hipError_t cosine_distance_launch(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t n, int d, double* out,
+                                  hipStream_t stream) {
+  const bool v4 = (d % 4 == 0) && (lda % 4 == 0) && (ldb % 4 == 0) && al16(a) && al16(b);
+  const dim3 grid((unsigned)((n + kCosWaves - 1) / kCosWaves));
+  if (v4)
+    hipLaunchKernelGGL(cosine_kernel<4>, grid, dim3(kThreads), 0, stream, a, lda, b, ldb, n, d, out);
+  else
+    hipLaunchKernelGGL(cosine_kernel<1>, grid, dim3(kThreads), 0, stream, a, lda, b, ldb, n, d, out);
   return hipGetLastError();
 }
 

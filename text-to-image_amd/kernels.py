@@ -1220,6 +1220,23 @@ def gram_accumulate(X, s, sum64, G64):
     return sum64, G64
 
 
+def cosine_distance(a, b, out=None):
+    """IMD's per-pair distance: a, b float32 [n, d] (rows may be strided, columns contiguous) -> float64 [n] with
+    out[i] = clip(1 - a_i.b_i / sqrt(|a_i|^2 |b_i|^2), 0, 2), NaN for a zero row (scipy.spatial.distance.cosine)."""
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or a.dim() != 2 or tuple(a.shape) != tuple(b.shape):
+        raise ValueError('cosine_distance expects two float32 [n, d] tensors of one shape, got %s %s and %s %s' % (
+            a.dtype, tuple(a.shape), b.dtype, tuple(b.shape)))
+    if a.stride(1) != 1 or b.stride(1) != 1:
+        raise ValueError('cosine_distance: the columns must be contiguous (strides %s, %s)' % (a.stride(), b.stride()))
+    n, d = a.shape
+    y = torch.empty(n, dtype=torch.float64, device=a.device) if out is None else out
+    if tuple(y.shape) != (n,) or y.dtype != torch.float64 or not y.is_contiguous() or y.device != a.device:
+        raise ValueError('cosine_distance: out must be a contiguous float64 [%d] on %s' % (n, a.device))
+    if _live(a) and n > 0:
+        check(lib.t2i_cosine_distance(_ptr(a), a.stride(0), _ptr(b), b.stride(0), n, d, _ptr(y), _stream()), 't2i_cosine_distance')
+    return y
+
+
 def gather_mean(emb, ids, choice):
     """emb [N,En,D] float32; ids int32 [B]; choice int32 [B,k] -> [B,D] mean of the chosen rows, in choice order."""
     _chk(emb, 'emb')

@@ -216,20 +216,78 @@ class ConditionalGanTrainer(object):
                                  S.scalar('g_gan_loss', float(g['G_gan_loss'])), S.scalar('g_kl_loss', float(g['G_kl_loss']))], counter)
         self.writer.flush()
 
-    def train(self, max_updates=None, log=None, summaries=False):
-        """summaries=True: an event file in cfg.LOGS_DIR with the reference's per-update summaries (write_summaries)."""
+    # the reference's periods (stageI/trainer.py:151,163): a sample grid when counter % 500 == 0, a checkpoint when
+    # counter % 500 == 0.  TRAIN.SAMPLE_PERIOD / TRAIN.CHECKPOINT_PERIOD override the periods; the phase stays
+    SAMPLE_PERIOD, CHECKPOINT_PERIOD, CHECKPOINT_PHASE = 500, 500, 0
+
+    def make_savers(self):
+        """-> (the saver the run resumes from and saves to, [(saver, dir, loaded message, failed message)] to restore first).
+        Stage I: tf.train.Saver() built before the optimizers (trainer.py:46) holds every variable of g_net and d_net, batch-norm
+        moving statistics included, and no Adam slot: a resumed run restarts Adam from zero."""
+        from ....utils.saver import Saver
+        saver = Saver(self.model.store, var_list=[self.model.g_scope, self.model.d_scope],
+                      max_to_keep=int(self.cfg.TRAIN.CHECKPOINTS_TO_KEEP))
+        return saver, [(saver, self.cfg.CHECKPOINT_DIR, ' [*] Load SUCCESS', ' [!] Load failed...')]
+
+    def _period(self, key, default):
+        p = int(getattr(self.cfg.TRAIN, key, None) or default)
+        if p <= 0:
+            raise ValueError('TRAIN.%s must be positive, got %d' % (key, p))
+        return p
+
+    def train(self, max_updates=None, log=None, summaries=False, side_effects=False, graphs=False):
+        """summaries=True: an event file in cfg.LOGS_DIR with the reference's per-update summaries (write_summaries).
+        side_effects=True: the rest of reference trainer.py:95-165 — sample_z, then the fixed test batch and its captions
+        (SAMPLE_DIR/captions.txt); resume from the latest checkpoint (counter from its name, epoch_start = counter //
+        updates_per_epoch, idx from 0); a sampler grid `train_{epoch:02d}_{idx:04d}.png` and a checkpoint on the periods above.
+        max_updates: updates run by this call.  graphs=True: the iteration is replayed from hipGraphs after its first eager run."""
+        import numpy as np
         log = log or (lambda s: (sys.stdout.write(s + '\n'), sys.stdout.flush()))
+        m = self.model
         if summaries and getattr(self.cfg, 'LOGS_DIR', None):
             self.define_summaries()
-        t0, counter = time.time(), 1
-        for epoch in range(self.cfg.TRAIN.EPOCH):
-            updates_per_epoch = self.dataset.train.num_examples // self.model.batch_size
+        counter = 1
+        epoch_start = 0
+        updates_per_epoch = self.dataset.train.num_examples // m.batch_size
+        if side_effects:
+            from ....utils.saver import load, save
+            from ....utils.utils import get_balanced_factorization, save_captions, save_images
+            sample_period = self._period('SAMPLE_PERIOD', self.SAMPLE_PERIOD)
+            ckpt_period = self._period('CHECKPOINT_PERIOD', self.CHECKPOINT_PERIOD)
+            self.saver, restores = self.make_savers()
+            sample_z = np.random.normal(0, 1, (m.sample_num, m.z_dim))
+            _, sample_embed, _, captions = self.dataset.test.next_batch_test(m.sample_num, 0, 1)
+            sample_z = torch.as_tensor(sample_z, dtype=torch.float32).to(m.device)
+            sample_embed = torch.as_tensor(sample_embed[0]).to(device=m.device, dtype=torch.float32).reshape(m.sample_num, -1)
+            save_captions(self.cfg.SAMPLE_DIR, captions)
+            for i, (saver, directory, ok, failed) in enumerate(restores):
+                could_load, checkpoint_counter = load(saver, None, directory)
+                if i == 0 and could_load:
+                    counter = checkpoint_counter
+                log(ok if could_load else failed)
+            if updates_per_epoch <= 0:
+                raise ValueError('the training split has %d examples, fewer than one batch of %d' % (
+                    self.dataset.train.num_examples, m.batch_size))
+            epoch_start = counter // updates_per_epoch
+            self.start_counter, self.epoch_start = counter, epoch_start
+        t0, done = time.time(), 0
+        for epoch in range(epoch_start, self.cfg.TRAIN.EPOCH):
             for idx in range(updates_per_epoch):
-                out = self.iteration(self.make_feed(), epoch)
+                feed = self.make_feed()
+                out = self.iteration(feed, epoch)
+                if graphs and getattr(self, '_graphs', None) is None:
+                    self.enable_graphs(feed)
                 if getattr(self, 'writer', None) is not None:
                     self.write_summaries(counter, out)
+                counter += 1
+                done += 1
                 log('Epoch: [%2d] [%4d/%4d] time: %4.4f, d_loss: %.8f, g_loss: %.8f' % (
                     epoch, idx, updates_per_epoch, time.time() - t0, float(out['d']['D_loss']), float(out['g']['G_loss'])))
-                counter += 1
-                if max_updates is not None and counter > max_updates:
+                if side_effects:
+                    if counter % sample_period == 0:
+                        save_images(m.sampler(sample_z, sample_embed), get_balanced_factorization(m.sample_num),
+                                    '{}train_{:02d}_{:04d}.png'.format(self.cfg.SAMPLE_DIR, epoch, idx))
+                    if counter % ckpt_period == self.CHECKPOINT_PHASE % ckpt_period:
+                        save(self.saver, None, self.cfg.CHECKPOINT_DIR, counter)
+                if max_updates is not None and done >= max_updates:
                     return

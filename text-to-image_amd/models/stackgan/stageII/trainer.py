@@ -17,6 +17,23 @@ class ConditionalGanTrainer(_StageITrainer):
         self.cfg_stage_i = cfg_stage_i
         super().__init__(sess, model, dataset, cfg)
 
+    # reference stageII/trainer.py:162,176: a sample grid when counter % 2000 == 0, a checkpoint when counter % 500 == 2
+    SAMPLE_PERIOD, CHECKPOINT_PERIOD, CHECKPOINT_PHASE = 2000, 500, 2
+
+    def make_savers(self):
+        """stageII/trainer.py:44-49,107-121: the checkpoints hold stageII_g_net + stageII_d_net only; the Stage-I generator (g_net)
+        is restored from cfg_stage_i.CHECKPOINT_DIR, and a failed load there only warns."""
+        from ....utils.saver import Saver
+        m = self.model
+        saver = Saver(m.store, var_list=[m.g_scope, m.d_scope], max_to_keep=int(self.cfg.TRAIN.CHECKPOINTS_TO_KEEP))
+        restores = [(saver, self.cfg.CHECKPOINT_DIR, ' [*] Load SUCCESS: Stage II networks are loaded.',
+                     ' [!] Load failed for stage II networks...')]
+        if self.cfg_stage_i is not None:
+            restores.append((Saver(m.store, var_list=[m.stagei.g_scope]), self.cfg_stage_i.CHECKPOINT_DIR,
+                             ' [*] Load SUCCESS: Stage I generator is loaded',
+                             ' [!] WARNING!!! Failed to load the parameters for stage I generator...'))
+        return saver, restores
+
     def _generate(self, feed, which):
         m = self.model
         with torch.no_grad():      # Stage-I variables are in no var_list; under update_ops() its BN moving averages move
