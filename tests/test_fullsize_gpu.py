@@ -122,12 +122,9 @@ def _stage2_full_size(gpu, bf16):
     hf.update({k: v for k, v in f.items() if k.startswith('ca_noise')})
     moving0 = {n: v.detach().clone() for n, v in m.store.vars.items() if 'moving' in n}
     tr = ConditionalGanTrainer(None, m, None, c2)
-    if tr.batched:          # the critic passes of one sess.run stacked along the batch axis (see _cgan_steps)
-        plan = [('G',), ('Dfake', 'Dmatch', 'Dmis')]
-        # the generator step: round 6 stacks its three critic evaluations too (fake with the gradient | match | mismatch); T2I_CGAN_STACK_G=0: two passes
-        plan_g = plan if os.environ.get('T2I_CGAN_STACK_G', '1') != '0' else [('G',), ('Dfake',), ('Dmatch', 'Dmis')]
-    else:
-        plan = plan_g = [('G',), ('Dfake',), ('Dmatch',), ('Dmis',)]
+    # the critic passes of one sess.run stacked along the batch axis (see _cgan_steps); the generator step stacks its three critic
+    # evaluations too (fake with the gradient | match | mismatch)
+    plan = [('G',), ('Dfake', 'Dmatch', 'Dmis')]
     chk = Checker()
     env = STAGE2_COMPLIANT
     flip_tol = env['flips'] if bf16 else 1e-4
@@ -191,7 +188,7 @@ def _stage2_full_size(gpu, bf16):
     own = T.SectionTape()
     with T.use_tape(own), T.forward_only():        # the oracle's own branches: forward passes only
         SG.g_step(P, o2, feed, 2, o1)
-    masks = split_sections(rec, own.record, plan_g)
+    masks = split_sections(rec, own.record, plan)
     fl, units = flips(own.record, masks)
     print('Stage-II generator step: %d of %d branches differ (%.2e)' % (fl, units, fl / units))
     assert fl <= flip_tol * units
@@ -277,13 +274,9 @@ def _cgan_steps(tag, tr, m, hf, d_oracle, g_oracle, loss_keys_d, loss_keys_g, ch
     mask-pinned; d_oracle / g_oracle: callables that run the oracle step under whatever tape is installed."""
     moving0 = {n: v.detach().clone() for n, v in m.store.vars.items() if 'moving' in n}
     # the HIP passes in launch order (tests/branches.split_sections): gancls stacks the critic passes of one sess.run along the batch axis
-    # (GanClsTrainer.batched: fake | match | mismatch in the critic step; fake, then match | mismatch, in the generator step)
-    if getattr(tr, 'batched', False):
-        plan = [('G',), ('Dfake', 'Dmatch', 'Dmis')]
-        # the generator step: round 6 stacks its three critic evaluations too (fake with the gradient | match | mismatch); T2I_CGAN_STACK_G=0: two passes
-        plan_g = plan if os.environ.get('T2I_CGAN_STACK_G', '1') != '0' else [('G',), ('Dfake',), ('Dmatch', 'Dmis')]
-    else:
-        plan = plan_g = [('G',), ('Dfake',), ('Dmatch',), ('Dmis',)]
+    # (fake | match | mismatch in the critic step; the generator step stacks its three critic evaluations too: fake with the gradient |
+    # match | mismatch)
+    plan = [('G',), ('Dfake', 'Dmatch', 'Dmis')]
     rec = []
     with record_branches(rec):
         d = tr.d_losses(hf)
@@ -312,7 +305,7 @@ def _cgan_steps(tag, tr, m, hf, d_oracle, g_oracle, loss_keys_d, loss_keys_g, ch
     own = T.SectionTape()
     with T.use_tape(own), T.forward_only():        # the oracle's own branches: forward passes only
         g_oracle()
-    masks = split_sections(rec, own.record, plan_g)
+    masks = split_sections(rec, own.record, plan)
     fl, units = flips(own.record, masks)
     print('%s generator step: %d of %d branches differ (%.2e)' % (tag, fl, units, fl / units))
     assert fl <= 1e-4 * units

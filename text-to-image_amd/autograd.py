@@ -9,7 +9,6 @@ norm) are first-order (``once_differentiable``), exactly what the reference's tw
 there only d/d(input) is wanted, so filter / bias gradients are not launched.
 """
 import contextlib
-import os
 import weakref
 
 import torch
@@ -84,7 +83,7 @@ SIDE = _Side()
 
 
 def enable_side_stream(on=True):
-    SIDE.stream = torch.cuda.Stream(priority=int(os.environ.get('T2I_SIDE_PRIO', '0'))) if on else None
+    SIDE.stream = torch.cuda.Stream() if on else None
     SIDE.keep = []
 
 
@@ -135,17 +134,13 @@ def _filter_grad(x, gpre, geom, w, xform=None, xform_plane_rows=0):
                 K.conv_bwd_filter(xs, gs, geom[0], geom[1], out=sink, xform=xform, xform_plane_rows=xform_plane_rows, accumulate=acc)
             _notify(w)
             return None
-    if os.environ.get('T2I_DP_DEBUG') == '1' and NOTIFY[0] is not None:
-        import sys
-        sys.stderr.write('[ag] differentiable filter gradient: grad_enabled=%s sink=%s inputs_only=%s w.requires_grad=%s\n' % (
-            torch.is_grad_enabled(), sink_at(w.data_ptr()) is not None, _INPUTS_ONLY[0], w.requires_grad))
     return ConvBwdFilterFn.apply(x, gpre, geom)
 
 
 def _pair_ok(g, other, w):
     """Final (first-order) backward, sunk filter gradient, bf16 tensors on one stream: the layer's two backward GEMMs may share a
     launch (kernels.conv_bwd_pair).  Everything else keeps the two differentiable Functions."""
-    return (not torch.is_grad_enabled() and SIDE.stream is None and K.pair_calls() and g.dtype == torch.bfloat16 and
+    return (not torch.is_grad_enabled() and SIDE.stream is None and g.dtype == torch.bfloat16 and
             other.dtype == torch.bfloat16 and g.is_cuda and sink_at(w.data_ptr()) is not None)
 
 
@@ -416,9 +411,6 @@ class ActFn(Function):
         return ActBwdFn.apply(gy, y, ctx.act, ctx.alpha), None, None
 
 
-_BN_ONE_ENTRY = [os.environ.get('T2I_BN_ONE_ENTRY', '1') != '0']     # 0: the separate statistics / normalise calls of rounds 1-4
-
-
 class BatchNormTrainFn(Function):
     """Training-mode fused batch norm + activation: reference utils/ops.py:7-29.  Normalises with the biased batch
     variance; if moving_mean/var are given they are updated in place with the unbiased one (TF UPDATE_OPS semantics are
@@ -432,8 +424,9 @@ class BatchNormTrainFn(Function):
         # statistics (the producing conv's epilogue partials when ops.conv2d(..., stats=True) left any, else a pass over x;
         # numerically stable either way) and the finalize step in one chain of launches
         # round 5: one entry point — [first stage unless the conv left tile partials] -> [second stage + finalize] -> [normalise], the
-        # middle launch folded into the last one's prologue for the small tensors (t2i_bn_train_fwd_grouped with groups = 1)
-        if _BN_ONE_ENTRY[0] and C % 4 == 0 and x.data_ptr() % 16 == 0 and gamma.data_ptr() % 4 == 0:
+        # middle launch folded into the last one's prologue for the small tensors (t2i_bn_train_fwd_grouped with groups = 1); the
+        # separate statistics / normalise calls of rounds 1-4 remain for what that entry point refuses (C % 4 != 0, misaligned tensors)
+        if C % 4 == 0 and x.data_ptr() % 16 == 0 and gamma.data_ptr() % 4 == 0:
             y, mean, rstd = K.bn_train_fwd_grouped(x, gamma, beta, eps, decay, 1, act, alpha, moving_mean, moving_var, moving_updates)
             mean, rstd = mean[0], rstd[0]
         else:
@@ -466,12 +459,9 @@ class BatchNormTrainFn(Function):
         gsink = _sink_of(ctx.gamma_ref) if want_g else None
         bsink = _sink_of(ctx.beta_ref) if want_b else None
         sunk = gsink is not None and bsink is not None
-        if fused and _BN_ONE_ENTRY[0]:      # [act backward + both reductions] -> [second stage + coefficients + dx]: two launches when the partials are few
+        if fused:      # [act backward + both reductions] -> [second stage + coefficients + dx]: two launches when the partials are few
             dx, dgamma, dbeta = K.bn_bwd_grouped(gy, y if ctx.act != K.ACT_NONE else None, x, mean, rstd, gamma, 1, ctx.act, ctx.alpha,
                                                  dgamma_out=gsink if sunk else None, dbeta_out=bsink if sunk else None)
-        elif fused:          # [act backward + both reductions] -> [second stage + coefficients] -> [dx]: three launches
-            dx, dgamma, dbeta = K.bn_bwd_fused(gy, y if ctx.act != K.ACT_NONE else None, x, mean, rstd, gamma, ctx.act, ctx.alpha,
-                                               dgamma_out=gsink if sunk else None, dbeta_out=bsink if sunk else None)
         else:
             dx, dgamma, dbeta = K.bn_bwd(gy, x, mean, rstd, gamma, sum_dy, sum_dy_x, dgamma_out=gsink if sunk else None,
                                          dbeta_out=bsink if sunk else None)

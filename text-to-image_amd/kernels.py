@@ -186,7 +186,6 @@ def f32_outputs():
 # the latter when they are constructed outside any scope, so a later, unscoped model in the same process starts from the plain rules.
 _MIXED = [False]
 _BWD_MATH = [None]
-_SCOPE_TWINS = [os.environ.get('T2I_SCOPE_TWINS', '1') != '0']      # 0: the rule of rounds 4-5 (A/B; it never made a twin, see _twin_for)
 _SCOPE_GRAD = [True]     # torch.is_grad_enabled() when the innermost math_scope was entered — by model code, outside any autograd Function (inside a
                          # Function.forward grad mode is always off): "will this forward be differentiated?", for _twin_for
 
@@ -358,7 +357,7 @@ def _ws_args(t, nbytes):
 # filter gradient, the second-order pieces of the gradient penalty), a gradient by two (input and filter gradient): the image
 # is made once per tensor (and version) here, kept on the tensor object and handed to every conv that reads the tensor
 # (t2i_conv_opts.a_image / b_image), instead of each entry point staging its own copy into the workspace.
-_BF16_IMAGES = [os.environ.get('T2I_BF16_IMAGES', '1') != '0']
+_BF16_IMAGES = [True]
 _H_ALGO = {}
 
 
@@ -438,7 +437,7 @@ def _operand_images(opts, a, b=None):
 # ... and where the tensor a conv will read comes out of one of our own kernels (activation / batch-norm apply / residual join /
 # a conv epilogue with its activation fused / activation backward), that kernel writes the bf16 image as a TWIN of its fp32
 # output in the same pass (the y_h arguments / t2i_conv_opts.out_image): no cast launch at all for it.
-_TWINS = [os.environ.get('T2I_BF16_TWINS', '1') != '0']
+_TWINS = [True]
 
 
 def bf16_twins(on):
@@ -453,8 +452,8 @@ def _twin_for(out, *inputs):
     if _MIXED[0]:
         if _BWD_MATH[0] == MATH_BF16:            # inside a scope whose backward GEMMs read bf16 images: the saved activations get theirs here
             # (round 6: the grad mode of the scope's entry — the producers run inside autograd Functions, where torch.is_grad_enabled() is
-            # always False, so this rule never made a twin and every saved activation of the scoped network was cast in a launch of its own)
-            want = _SCOPE_GRAD[0] if _SCOPE_TWINS[0] else torch.is_grad_enabled()
+            # always False, so the rounds 4-5 rule that asked it never made a twin and every saved activation was cast in a launch of its own)
+            want = _SCOPE_GRAD[0]
         elif _STORE[0] is torch.bfloat16:        # outside the scope, bf16 storage: a float32 tensor here belongs to the scoped network's backward
             want = _MIXED[0] == 'bwd_bf16'
     if out.dtype != torch.float32 or not want or not (_TWINS[0] and _BF16_IMAGES[0]) or out.shape[-1] % 64 or out.numel() % 8:
@@ -475,7 +474,7 @@ def _twin_keep(out, img, written=True):
 # reads it instead of transforming x again (t2i_conv2d_input_transform).
 _XFORM_BYTES = {}
 LAST_XFORM = [None]
-_SHARE_XFORM = [os.environ.get('T2I_SHARE_XFORM', '1') != '0']
+_SHARE_XFORM = [True]
 
 
 def share_xform(on):
@@ -723,14 +722,6 @@ def conv_bwd_filter(x, dy, d, ws_bytes, out=None, xform=None, xform_valid_rows=0
 
 
 PAIR_FWD, PAIR_BWD_DATA = 0, 1
-_PAIR = [os.environ.get('T2I_PAIR_CALLS', '1') != '0']
-
-
-def pair_calls(on=None):
-    """Should a layer's backward hand its two GEMMs to conv_bwd_pair (one launch where the library can fuse them)?"""
-    if on is not None:
-        _PAIR[0] = bool(on)
-    return _PAIR[0]
 
 
 def conv_bwd_pair(first, g, w, fx, fdy, d, ws_bytes, dw_out, out_dtype=None, accumulate=True):

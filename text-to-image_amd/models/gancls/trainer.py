@@ -1,6 +1,5 @@
 """GanClsTrainer — reference models/gancls/trainer.py:12-164: losses, the two Adam optimizers (both under UPDATE_OPS) and
 the D-then-G update order of every iteration."""
-import os
 import sys
 import time
 
@@ -12,21 +11,19 @@ from ... import kernels as K
 from ... import optim
 from ...utils.ops import update_ops
 
-# the generator step's three critic evaluations as one stacked pass (stacked.py); T2I_CGAN_STACK_G=0: fake pass + [match | mismatch] pass
-_STACK_G = os.environ.get('T2I_CGAN_STACK_G', '1') != '0'
-
 
 class GanClsTrainer(object):
+    batched = True      # the critic's passes of one sess.run are one stacked batch (always: the unstacked forms are gone)
+
     def __init__(self, sess, model, dataset, cfg):
         self.sess, self.model, self.dataset, self.cfg = sess, model, dataset, cfg     # sess unused (no TF session)
         self.gen = torch.Generator(device=model.device).manual_seed(1234)
-        self.batched = os.environ.get('T2I_GANCLS_BATCHED', '1') != '0'      # the critic's passes of one sess.run as one stacked batch
         # The D run and the G run of one iteration evaluate the generator on the SAME feed (trainer.py:115-134: same z, same phi), the generator
         # has no noise input (model.py:111-192) and D_optim does not touch its variables: the two evaluations are the same numbers.  iteration()
         # therefore evaluates it ONCE (with the autograd graph the G run needs), hands the critic step a detached view, and lets the batch norms'
         # moving averages take the batch statistics twice, as the two runs under UPDATE_OPS do (update_ops(times=2)).  Single process only: under
-        # data parallelism the two halves live in separately captured graph segments.  T2I_GANCLS_SHARE_G=0: evaluate twice.
-        self.share_g = os.environ.get('T2I_GANCLS_SHARE_G', '1') != '0'
+        # data parallelism the two halves live in separately captured graph segments.  share_g = False: evaluate twice.
+        self.share_g = True
         self._shared_G = None
         self.define_losses()
 
@@ -51,26 +48,18 @@ class GanClsTrainer(object):
                 with torch.no_grad():
                     G = m.generator(z, phi, reuse=True)
             # the critic's three passes (fake / match / mismatch, model.py:48-51) as ONE stacked batch: per-sample layers run once on 3B
-            # samples, every batch norm keeps its statistics per pass (discriminator(groups=3)); T2I_GANCLS_BATCHED=0: three calls
-            if self.batched:
-                _, logits = m.discriminator(torch.cat([G, x, xw], 0), torch.cat([phi, phi, phi], 0), reuse=True, _prob=False, groups=3)
-                B = x.shape[0]
-                lv = logits.detach().reshape(3, B)
-                heads, outs = [lv[0], lv[1], lv[2]], [logits]
-                seed = torch.empty(3 * B, dtype=torch.float32, device=logits.device)
-            else:
-                _, l_fake = m.discriminator(G, phi, reuse=True, _prob=False)
-                _, l_match = m.discriminator(x, phi, reuse=True, _prob=False)
-                _, l_mis = m.discriminator(xw, phi, reuse=True, _prob=False)
-                heads, outs, seed = [l_fake.detach().reshape(-1), l_match.detach().reshape(-1), l_mis.detach().reshape(-1)], [l_fake, l_match, l_mis], None
+            # samples, every batch norm keeps its statistics per pass (discriminator(groups=3))
+            _, logits = m.discriminator(torch.cat([G, x, xw], 0), torch.cat([phi, phi, phi], 0), reuse=True, _prob=False, groups=3)
+            B = x.shape[0]
+            lv = logits.detach().reshape(3, B)
+            seed = torch.empty(3 * B, dtype=torch.float32, device=logits.device)
         # the three heads of trainer.py:20-34 in ONE launch (labels 0 / 0.9 one-sided smoothing / 0; D_loss = match + alpha mismatch +
         # (1 - alpha) fake): the loss scalars, d D_loss / d logits as the seeds of the backward pass, and the sigmoid outputs
-        losses, seeds, probs = K.sigmoid_ce_head(heads, [0.0, 0.9, 0.0], [1.0 - self.alpha, 1.0, self.alpha], seeds_into=seed)
+        losses, _, probs = K.sigmoid_ce_head(list(lv), [0.0, 0.9, 0.0], [1.0 - self.alpha, 1.0, self.alpha], seeds_into=seed)
         m.d_arena.zero_grad()
         if m.dp is not None and not getattr(self, '_capturing', False):
             m.dp.arm(m.d_arena)
-        grads = [seed.view_as(outs[0])] if seed is not None else [s_.view_as(l_) for s_, l_ in zip(seeds, outs)]
-        torch.autograd.backward(outs, grads, inputs=list(m.d_vars.values()))
+        torch.autograd.backward([logits], [seed.view_as(logits)], inputs=list(m.d_vars.values()))
         A.side_join()
         shape = (x.shape[0], 1, 1, 1)
         return dict(D_loss=losses[0], D_real_match_loss=losses[2], D_real_mismatch_loss=losses[3], D_synthetic_loss=losses[1], G=G,
@@ -85,7 +74,7 @@ class GanClsTrainer(object):
                 G = m.generator(z, phi, reuse=True)
             # G_optim also sits under ALL update ops of the graph: the match / mismatch critic passes run in this
             # sess.run too, only to move their batch-norm moving averages (trainer.py:46-51)
-            if self.batched and _STACK_G and x.is_cuda:
+            if x.is_cuda:
                 # round 6: fake | match | mismatch as ONE stacked pass of three evaluations (stacked.py): every conv once on 3B rows, per-evaluation
                 # batch-norm statistics, the moving averages move once per evaluation in this order (as the three calls did); only the fake rows
                 # carry a gradient, so the backward runs on B rows as before
@@ -97,11 +86,7 @@ class GanClsTrainer(object):
                 with m.store.frozen('d_net'):
                     _, l_fake = m.discriminator(G, phi, reuse=True, _prob=False)
                 with torch.no_grad():
-                    if self.batched:
-                        m.discriminator(torch.cat([x, xw], 0), torch.cat([phi, phi], 0), reuse=True, _prob=False, groups=2)
-                    else:
-                        m.discriminator(x, phi, reuse=True, _prob=False)
-                        m.discriminator(xw, phi, reuse=True, _prob=False)
+                    m.discriminator(torch.cat([x, xw], 0), torch.cat([phi, phi], 0), reuse=True, _prob=False, groups=2)
         losses, seeds, _ = K.sigmoid_ce_head([l_fake.detach().reshape(-1)], [1.0], [1.0], want_prob=False)      # G_loss: label 1 (trainer.py:36)
         m.g_arena.zero_grad()
         if m.dp is not None and not getattr(self, '_capturing', False):

@@ -1,7 +1,6 @@
 """ConditionalGanTrainer (Stage-I) — reference models/stackgan/stageI/trainer.py:11-165: sigmoid cross-entropy losses
 (real label 0.9), KL term of the conditioning augmentation, two Adam optimizers on ONE learning-rate placeholder
 (D_LR * 0.5 ** (epoch // 100)), both under tf.GraphKeys.UPDATE_OPS, D update then G update every iteration."""
-import os
 import sys
 import time
 
@@ -13,18 +12,15 @@ from .... import kernels as K
 from .... import optim
 from ....utils.ops import update_ops
 
-# the generator step's three critic evaluations as one stacked pass (stacked.py); T2I_CGAN_STACK_G=0: fake pass + [match | mismatch] pass
-_STACK_G = os.environ.get('T2I_CGAN_STACK_G', '1') != '0'
-
 
 class ConditionalGanTrainer(object):
     REAL_LABEL = 0.9                     # trainer.py:26 (Stage-II overrides with 0.95)
+    batched = True                       # the critic's passes of one sess.run are one stacked batch (always, as in models/gancls)
 
     def __init__(self, sess, model, dataset, cfg):
         self.sess, self.model, self.dataset, self.cfg = sess, model, dataset, cfg     # sess unused (no TF session)
         self.lr = float(cfg.TRAIN.D_LR)
         self.gen = torch.Generator(device=model.device).manual_seed(1234)
-        self.batched = os.environ.get('T2I_GANCLS_BATCHED', '1') != '0'      # the critic's passes of one sess.run as one stacked batch (models/gancls)
         self.define_losses()
 
     def define_losses(self):
@@ -49,24 +45,17 @@ class ConditionalGanTrainer(object):
         with update_ops():      # D_optim sits under control_dependencies(UPDATE_OPS): every BN moving average moves
             with torch.no_grad():
                 G, _, _ = self._generate(feed, 'd')
-            if self.batched:          # fake | match | mismatch stacked along the batch axis, batch-norm statistics per pass
-                _, logits = m.discriminator(torch.cat([G, x, xw], 0), torch.cat([phi, phi, phi], 0), reuse=True, _prob=False, groups=3)
-                B = x.shape[0]
-                lv = logits.detach().reshape(3, B)
-                heads, outs = [lv[0], lv[1], lv[2]], [logits]
-                seed = torch.empty(3 * B, dtype=torch.float32, device=logits.device)
-            else:
-                _, l_fake = m.discriminator(G, phi, reuse=True, _prob=False)
-                _, l_match = m.discriminator(x, phi, reuse=True, _prob=False)
-                _, l_mis = m.discriminator(xw, phi, reuse=True, _prob=False)
-                heads, outs, seed = [l_fake.detach().reshape(-1), l_match.detach().reshape(-1), l_mis.detach().reshape(-1)], [l_fake, l_match, l_mis], None
+            # fake | match | mismatch stacked along the batch axis, batch-norm statistics per pass (models/gancls)
+            _, logits = m.discriminator(torch.cat([G, x, xw], 0), torch.cat([phi, phi, phi], 0), reuse=True, _prob=False, groups=3)
+            B = x.shape[0]
+            heads = list(logits.detach().reshape(3, B))
+            seed = torch.empty(3 * B, dtype=torch.float32, device=logits.device)
         # the three heads (trainer.py:24-33) in one launch: loss scalars + d D_loss / d logits as the seeds of the backward pass
-        losses, seeds, _ = K.sigmoid_ce_head(heads, [0.0, self.REAL_LABEL, 0.0], [1.0 - self.alpha, 1.0, self.alpha], want_prob=False, seeds_into=seed)
+        losses, _, _ = K.sigmoid_ce_head(heads, [0.0, self.REAL_LABEL, 0.0], [1.0 - self.alpha, 1.0, self.alpha], want_prob=False, seeds_into=seed)
         m.d_arena.zero_grad()
         if m.dp is not None and not getattr(self, '_capturing', False):
             m.dp.arm(m.d_arena)
-        grads = [seed.view_as(outs[0])] if seed is not None else [s_.view_as(l_) for s_, l_ in zip(seeds, outs)]
-        torch.autograd.backward(outs, grads, inputs=list(m.d_vars.values()))
+        torch.autograd.backward([logits], [seed.view_as(logits)], inputs=list(m.d_vars.values()))
         A.side_join()
         # the three critic outputs (fake, match, mismatch logits) ride along for the D summary's histograms (trainer.py:59-61)
         return dict(D_loss=losses[0], D_real_match_loss=losses[2], D_real_mismatch_loss=losses[3], D_synthetic_loss=losses[1], G=G,
@@ -79,7 +68,7 @@ class ConditionalGanTrainer(object):
             G, mean, log_sigma = self._generate(feed, 'g')
             # G_optim also sits under ALL update ops of the graph: the match / mismatch critic passes run in this
             # sess.run too, only to move their batch-norm moving averages (trainer.py:50-55)
-            if self.batched and _STACK_G and x.is_cuda:
+            if x.is_cuda:
                 # round 6: fake | match | mismatch as ONE stacked pass of three evaluations (stacked.py): every conv once on 3B rows, per-evaluation
                 # batch-norm statistics, the moving averages move once per evaluation in this order (as the three calls did); only the fake rows
                 # carry a gradient, so the backward runs on B rows as before
@@ -91,11 +80,7 @@ class ConditionalGanTrainer(object):
                 with m.store.frozen(m.d_scope):
                     _, l_fake = m.discriminator(G, phi, reuse=True, _prob=False)
                 with torch.no_grad():
-                    if self.batched:
-                        m.discriminator(torch.cat([x, xw], 0), torch.cat([phi, phi], 0), reuse=True, _prob=False, groups=2)
-                    else:
-                        m.discriminator(x, phi, reuse=True, _prob=False)
-                        m.discriminator(xw, phi, reuse=True, _prob=False)
+                    m.discriminator(torch.cat([x, xw], 0), torch.cat([phi, phi], 0), reuse=True, _prob=False, groups=2)
         # G_loss = CE(fake, 1) + kl_coeff * KL (trainer.py:35-41): the CE head gives its value and d/d logits; the KL term stays a
         # differentiable tensor expression, so the two are seeded together
         losses, seeds, _ = K.sigmoid_ce_head([l_fake.detach().reshape(-1)], [1.0], [1.0], want_prob=False)

@@ -25,14 +25,6 @@ from ...utils.ops import (NCHW, add, batch_norm, concat_tile, conv2d, conv2d_tra
                           reshape_to_map, tanh, to_nchw, to_nhwc, update_ops)
 
 
-# capture mode of the data-parallel graph segments: thread-local, because the process group's watchdog thread polls events
-# while the capture is open (T2I_DP_CAPTURE_MODE=global for diagnostics with a backend that has no such thread)
-_CAPTURE_MODE = os.environ.get('T2I_DP_CAPTURE_MODE', 'thread_local')
-# one-graph iteration (single GPU): issue the G step's generator forward on a second stream beside the critic step
-_OVERLAP_G_FORWARD = os.environ.get('T2I_OVERLAP_G_FORWARD', '1') != '0'
-# the one-graph iteration trusts the critic's filter images its previous replay regenerated behind the critic's Adam step instead
-# of regenerating them again at its head (dg_step keeps them current across outside writers): T2I_TRUST_IMAGES=0 restores the refresh
-_TRUST_IMAGES = os.environ.get('T2I_TRUST_IMAGES', '1') != '0'
 # single GPU: the critic's four passes of a step as ONE stacked pass of 4B images (stacked.py); T2I_STACK_XHAT=0: the 3B + B form
 _STACK_XHAT = os.environ.get('T2I_STACK_XHAT', '1') != '0'
 # single GPU, D + G iteration: the generator's two evaluations (critic step: no gradient, its own noise; generator step: under UPDATE_OPS)
@@ -74,9 +66,6 @@ class WGanCls(object):
         self.pair_g = _PAIR_G                 # (needs stack_xhat: the pair writes both images into the stacked critic input's buffer)
         self.net_math = {}
         K.forget_scopes()          # a scoped model that lived in this process before leaves no twin policy behind for this one
-        if os.environ.get('T2I_G_MATH'):
-            gm = os.environ['T2I_G_MATH'].split(',')     # "f32" or "f32,bf16" (forward arithmetic[, backward arithmetic])
-            self.net_math['g_net'] = (gm[0], 'f32') + tuple(gm[1:2])
 
         if build_model:
             self.build_model()
@@ -217,8 +206,6 @@ class WGanCls(object):
         bufs = self._stack_buffers(B, x)
         inp4, cond4, seed4 = bufs['inp4'], bufs['cond4'], bufs['seed4']
         del ST._DEFERRED[:]                       # (records of a step that was abandoned half-way)
-        if not (x.is_cuda and torch.cuda.is_current_stream_capturing()):
-            ST.prepare_side(self.device)
         with torch.no_grad():
             if have_g:                                      # _g_forward_pair has already put this step's G into its slot
                 G = inp4[:B]
@@ -253,7 +240,6 @@ class WGanCls(object):
         scal, _, seed_s1, seed_s2 = K.wgan_d_head(lm.detach().reshape(-1), slopes1.detach(), slopes2.detach(), self.kt, self.gp_coeff)
         torch.autograd.backward([slopes1, slopes2], [seed_s1, seed_s2], inputs=list(self.d_vars.values()))
         ST.flush_deferred()                       # (filter gradients the double backward did not reach: none on this model)
-        ST.join()                                 # ... and the ones issued on the second stream (T2I_STACK_SIDE)
         A.side_join()
         out = {k: scal[i] for i, k in enumerate(K.D_HEAD_KEYS)}
         i0 = K.D_HEAD_KEYS.index('wdist')
@@ -624,8 +610,8 @@ class WGanCls(object):
         for k in ('ca_noise_d', 'ca_noise_g'):
             if k not in static:   # re-drawn in place before every replay (_load_static); nothing is drawn here, so the
                 static[k] = torch.zeros(feed['cond'].shape[0], self.compressed_embed_dim, device=self.device)   # RNG stream stays the eager one
-        if self.dp is None and _OVERLAP_G_FORWARD:
-            self._prepare_ahead()
+        if self.dp is None:
+            self._prepare_ahead()      # (the G step's generator forward goes on a second stream beside the critic step)
         torch.cuda.synchronize(self.device)
         gd, gg = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         if self.dp is None:
@@ -639,7 +625,9 @@ class WGanCls(object):
             with torch.cuda.graph(gg, pool=gd.pool(), capture_error_mode=_plain_mode):
                 self._refresh_filters()
                 g_out = self._g_body(static)
-            trust = _TRUST_IMAGES and K.filter_cache_enabled()        # nothing to trust (and nothing to capture below) without the cache
+            # the one-graph iteration trusts the critic's filter images its previous replay regenerated behind the critic's Adam step
+            # instead of regenerating them again at its head (dg_step keeps them current across outside writers)
+            trust = K.filter_cache_enabled()        # nothing to trust (and nothing to capture below) without the cache
             gref = None
             if trust:
                 gref = torch.cuda.CUDAGraph()            # the critic's filter images alone (dg_step: after an outside write); captured,
@@ -660,7 +648,7 @@ class WGanCls(object):
                     d_out2 = self._d_body(static, have_g=True)
                     g_out2 = self._g_body(static, fwd, ahead=False)
                 else:
-                    ahead = self._g_forward_ahead(static) if _OVERLAP_G_FORWARD else None   # beside the critic step, not after it
+                    ahead = self._g_forward_ahead(static)       # beside the critic step, not after it
                     d_out2 = self._d_body(static)
                     g_out2 = self._g_body(static, ahead)
             self._graphs = {'d': gd, 'g': gg, 'dg': gdg, 'd_out': d_out, 'g_out': g_out, 'dg_out': (d_out2, g_out2),
@@ -671,13 +659,13 @@ class WGanCls(object):
         scale = 1.0 / self.dp.world
         self._capturing = True
         try:
-            with torch.cuda.graph(gd, capture_error_mode=_CAPTURE_MODE):
+            with torch.cuda.graph(gd, capture_error_mode='thread_local'):
                 d_out = self.d_losses(static)
-            with torch.cuda.graph(gdu, pool=gd.pool(), capture_error_mode=_CAPTURE_MODE):
+            with torch.cuda.graph(gdu, pool=gd.pool(), capture_error_mode='thread_local'):
                 self._d_update(d_out, scale)
-            with torch.cuda.graph(gg, pool=gd.pool(), capture_error_mode=_CAPTURE_MODE):
+            with torch.cuda.graph(gg, pool=gd.pool(), capture_error_mode='thread_local'):
                 g_out = self.g_losses(static)
-            with torch.cuda.graph(ggu, pool=gd.pool(), capture_error_mode=_CAPTURE_MODE):
+            with torch.cuda.graph(ggu, pool=gd.pool(), capture_error_mode='thread_local'):
                 self.G_optim.apply(grad_scale=scale)
             # dg_step (the trainer's iteration): each backward is cut once.  [critic losses + first part of its backward] |
             # exchange of that part starts | [generator forward + rest of the critic backward] | exchange of the rest, wait |
@@ -685,15 +673,15 @@ class WGanCls(object):
             # exchange, wait | [generator Adam].  The autograd graph recorded in one capture is consumed by a later one (all
             # captures share one private pool and are replayed in capture order).
             gda, ggfdb, gduga, ggb = (torch.cuda.CUDAGraph() for _ in range(4))
-            with torch.cuda.graph(gda, pool=gd.pool(), capture_error_mode=_CAPTURE_MODE):
+            with torch.cuda.graph(gda, pool=gd.pool(), capture_error_mode='thread_local'):
                 d_out2 = self.d_losses(static, cut=True)
-            with torch.cuda.graph(ggfdb, pool=gd.pool(), capture_error_mode=_CAPTURE_MODE):
+            with torch.cuda.graph(ggfdb, pool=gd.pool(), capture_error_mode='thread_local'):
                 fwd = self._g_forward(static, keep_cut=True)
                 self.d_backward_rest()
-            with torch.cuda.graph(gduga, pool=gd.pool(), capture_error_mode=_CAPTURE_MODE):
+            with torch.cuda.graph(gduga, pool=gd.pool(), capture_error_mode='thread_local'):
                 self._d_update(d_out2, scale)
                 g_out2 = self.g_losses(static, fwd=fwd, cut=True)
-            with torch.cuda.graph(ggb, pool=gd.pool(), capture_error_mode=_CAPTURE_MODE):
+            with torch.cuda.graph(ggb, pool=gd.pool(), capture_error_mode='thread_local'):
                 self.g_backward_rest()
             del fwd
         finally:

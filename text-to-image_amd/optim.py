@@ -5,7 +5,6 @@ gradients, first and second moments in three more buffers of the same shape.  A 
 over ~29 M (critic) / ~23 M (generator) floats instead of one launch per tensor, and data-parallel gradient exchange
 works on contiguous slices of the gradient arena (dp.py)."""
 import math
-import os
 from collections import OrderedDict
 
 import torch
@@ -62,16 +61,14 @@ class Arena(object):
     _store_first = None
     _pending_check = False
 
-    def enable_sinks(self, store_first=None):
+    def enable_sinks(self, store_first=True):
         """Let the filter-gradient GEMMs accumulate directly into this arena (autograd.SINKS).
-        store_first (default: T2I_STORE_FIRST != 0): the slots of the large filters (>= 2^16 elements; conv / deconv / dense kernels) are
+        store_first: the slots of the large filters (>= 2^16 elements; conv / deconv / dense kernels) are
         never zero-filled — the first contribution a step writes into such a slot is a plain store (accumulate = 0 in the filter-gradient
         epilogue), later ones add.  Saves the fill (116 + 91 MB per wgancls iteration) and the epilogues' read of the slot.  A slot that
         receives NO contribution in a step would keep the previous step's gradient: finish_step() — called by the optimizer before it
         reads the arena — zeroes exactly those."""
         from . import autograd as A
-        if store_first is None:
-            store_first = os.environ.get('T2I_STORE_FIRST', '1') != '0'
         big = set()
         self._store_first, self._pending_check = None, False          # (a repeated call re-decides)
         if store_first and self.grad.is_cuda:
@@ -133,12 +130,7 @@ class AdamTF(object):
         # beta1 == 0 (both wgancls optimizers, PGGAN): m_t = g_t * grad_scale whatever m_{t-1} was, so the step neither reads nor
         # writes it (4 bytes per parameter less of the 24 the update streams); `m` is formed from the gradient arena when somebody
         # asks for it — a checkpoint between two iterations — which is valid until the arena is zeroed for the next backward
-        self.skip_m = beta1 == 0.0 and os.environ.get('T2I_ADAM_SKIP_M', '1') != '0'
-        # An EAGER Arena.zero_grad after a step forms the lagging moment before it clears its source (one read + one write of the
-        # arena: 8 bytes per parameter, more than the 4 the fast path saves on that iteration; replayed graphs never run it).  A
-        # loop that checkpoints only right after a step — every trainer here — may switch it off: `m` stays valid until the next
-        # zero_grad either way.  T2I_ADAM_KEEP_M=0 sets the default.
-        self.keep_m_across_zero_grad = os.environ.get('T2I_ADAM_KEEP_M', '1') != '0'
+        self.skip_m = beta1 == 0.0
         self._m_stale, self._last_scale = False, 1.0    # `_m` lags the last step (it is re-formed from the gradient arena on demand)
         self.t = 0
         self.lr_t_dev = torch.zeros(4, dtype=torch.float32, device=arena.flat.device)   # [0] = this step's lr_t
@@ -166,7 +158,7 @@ class AdamTF(object):
 
     def _materialize_m(self):
         """Arena.zero_grad (eager) is about to clear the gradients the on-demand first moment is formed from."""
-        if self.skip_m and self._m_stale and self.keep_m_across_zero_grad:
+        if self.skip_m and self._m_stale:
             self.m
 
     def moments_loaded(self):

@@ -132,7 +132,7 @@ class SActBwdFn(Function):
         gh = None
         if ggh is not None:
             yh = y4[R:]
-            if _TANGENT_IN_PLACE[0] and _DEFER[0] and not torch.is_grad_enabled() and ctx.act in (K.ACT_LRELU, K.ACT_RELU) and \
+            if _DEFER[0] and not torch.is_grad_enabled() and ctx.act in (K.ACT_LRELU, K.ACT_RELU) and \
                     ggh.dtype == yh.dtype and K._twin_for(yh, ggh) is None:
                 # The double backward of the gradient penalty (no third order): the result is the tangent that the layer ABOVE writes over
                 # the x_hat rows of its input for its one filter-gradient launch (SBwdDataFn.backward) — and its input IS this y4.  The
@@ -154,36 +154,6 @@ def _sact_bwd(gym, gyh, y4, act, alpha, colsum_into=None):
 # scored rows alone, so that no layer can lose its loss gradient to a pruned graph.
 _DEFERRED = []
 _DEFER = [True]
-
-# The deferred filter gradients on a stream of their own (T2I_STACK_SIDE=1): inside the double backward the critical path is the
-# tangent chain — per layer a B-row conv, an activation backward and a copy, kernels that leave most of the chip idle — while the 4B-row
-# filter gradients feed nothing but the optimizer.  Issued on a second stream they fill the chip beside the chain instead of
-# alternating with it.  join() makes the calling stream wait for them (before Adam reads the arena).
-import os as _os
-_SIDE = {'on': _os.environ.get('T2I_STACK_SIDE', '0') == '1', 'stream': None, 'keep': []}
-# SActBwdFn.backward writes the penalty's tangent straight over the x_hat rows of the activation it masks with (= the next layer's input,
-# where SBwdDataFn.backward wants it); 0: a fresh tensor + the copy, as before — same bits, nine launches more
-_TANGENT_IN_PLACE = [_os.environ.get('T2I_TANGENT_IN_PLACE', '1') != '0']
-
-
-def side_filter_gradients(on):
-    prev, _SIDE['on'] = _SIDE['on'], bool(on)
-    return prev
-
-
-def prepare_side(device):
-    """Create the stream and its workspace lane (outside any capture; the lane is sized like the main lane is NOW)."""
-    if _SIDE['on']:
-        if _SIDE['stream'] is None:
-            _SIDE['stream'] = torch.cuda.Stream(device=device)
-        K.stream_lane(_SIDE['stream'], device)
-
-
-def join():
-    s = _SIDE['stream']
-    if s is not None and _SIDE['keep']:
-        torch.cuda.current_stream().wait_stream(s)
-        del _SIDE['keep'][:]
 
 
 def defer_filter_gradients(on):
@@ -248,14 +218,7 @@ class SBwdDataFn(Function):
         xf, sink, ws4 = rec['xform'], rec['sink'], ctx.geom4[1]
         acc = A.sink_accumulate(w.data_ptr())
         launch = lambda: K.conv_bwd_filter(x4, gp4, d4, ws4, out=sink, xform=xf, xform_valid_rows=R if xf is not None else 0, accumulate=acc)
-        side = _SIDE['stream'] if (_SIDE['on'] and A.SIDE.stream is None) else None
-        if side is not None:
-            side.wait_stream(torch.cuda.current_stream())       # the tangent is in place; everything else it reads was final long ago
-            with torch.cuda.stream(side):
-                launch()
-            _SIDE['keep'].append((x4, gp4, xf, tang))
-        else:
-            A.sunk_launch(launch, (x4, gp4, xf))
+        A.sunk_launch(launch, (x4, gp4, xf))
         A._notify(w)
         rec['done'] = True
         rec['x4'] = rec['gp4'] = rec['xform'] = None
