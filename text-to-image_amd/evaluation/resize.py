@@ -6,7 +6,11 @@ then `astype(float32) / 127.5 - 1`).
 filter support is scaled by max(1, in / out), so a downscale is antialiased, and the weights become 22-bit fixed point.  The
 HIP kernel (t2i_resample_bilinear) applies the tables; `resize_u8` is the same two fixed-point passes in NumPy (horizontal,
 then vertical through an 8-bit intermediate, each rounding with 2^21 and clipping), the host statement the tests hold both
-Pillow and the kernel to."""
+Pillow and the kernel to.
+
+`bicubic_tables` / `resize_u8_bicubic` are the same construction for Pillow's BICUBIC (a = -0.5, support 2): the stage-size
+image stores of preprocess/stage_images.py.  Its negative lobes make some coefficients negative, and the 8-bit intermediate
+clip then matters; the passes above already clip, as Pillow does."""
 import functools
 import math
 
@@ -20,14 +24,35 @@ def _bilinear(x):
     return 1.0 - x if x < 1.0 else 0.0
 
 
+def _bicubic(x):
+    """Pillow's bicubic_filter: the cubic convolution kernel with a = -0.5, support 2 (Keys)."""
+    a = -0.5
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
 @functools.lru_cache(maxsize=None)
 def bilinear_tables(in_size, out_size):
     """-> (bounds int32 [out, 2] = (first input index, tap count), coeffs int32 [out, ksize]) for one axis."""
+    return _tables('bilinear_tables', _bilinear, 1.0, in_size, out_size)
+
+
+@functools.lru_cache(maxsize=None)
+def bicubic_tables(in_size, out_size):
+    """bilinear_tables for Pillow's BICUBIC (support 2, negative lobes: coefficients may be negative)."""
+    return _tables('bicubic_tables', _bicubic, 2.0, in_size, out_size)
+
+
+def _tables(what, filt, filter_support, in_size, out_size):
     if in_size <= 0 or out_size <= 0:
-        raise ValueError('bilinear_tables: sizes must be positive, got %d -> %d' % (in_size, out_size))
+        raise ValueError('%s: sizes must be positive, got %d -> %d' % (what, in_size, out_size))
     scale = float(in_size) / out_size
     filterscale = max(scale, 1.0)
-    support = 1.0 * filterscale                         # bilinear support 1.0
+    support = filter_support * filterscale
     ksize = int(math.ceil(support)) * 2 + 1
     bounds = np.zeros((out_size, 2), np.int32)
     coeffs = np.zeros((out_size, ksize), np.int32)
@@ -36,7 +61,7 @@ def bilinear_tables(in_size, out_size):
         center = (xx + 0.5) * scale
         xmin = max(int(center - support + 0.5), 0)      # int(): truncation toward zero, as the C cast
         xmax = min(int(center + support + 0.5), in_size) - xmin
-        w = [_bilinear((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        w = [filt((x + xmin - center + 0.5) * ss) for x in range(xmax)]
         ww = sum(w)                                     # left-to-right, as Pillow's loop
         if ww != 0.0:
             w = [v / ww for v in w]
@@ -57,13 +82,24 @@ def _pass(img, bounds, coeffs, axis):
     return np.clip(out >> PRECISION_BITS, 0, 255).astype(np.uint8)
 
 
-def resize_u8(img, out_h, out_w):
-    """uint8 [H, W, C] -> uint8 [out_h, out_w, C]: Image.fromarray(img).resize((out_w, out_h), Image.BILINEAR)."""
+def _resize(what, tables, img, out_h, out_w):
     img = np.asarray(img)
     if img.dtype != np.uint8 or img.ndim != 3:
-        raise ValueError('resize_u8 expects a uint8 [H, W, C] image, got %s %s' % (img.dtype, img.shape))
-    tmp = _pass(img, *bilinear_tables(img.shape[1], out_w), axis=1)
-    return _pass(tmp, *bilinear_tables(img.shape[0], out_h), axis=0)
+        raise ValueError('%s expects a uint8 [H, W, C] image, got %s %s' % (what, img.dtype, img.shape))
+    tmp = _pass(img, *tables(img.shape[1], out_w), axis=1)
+    return _pass(tmp, *tables(img.shape[0], out_h), axis=0)
+
+
+def resize_u8(img, out_h, out_w):
+    """uint8 [H, W, C] -> uint8 [out_h, out_w, C]: Image.fromarray(img).resize((out_w, out_h), Image.BILINEAR)."""
+    return _resize('resize_u8', bilinear_tables, img, out_h, out_w)
+
+
+def resize_u8_bicubic(img, out_h, out_w):
+    """uint8 [H, W, C] -> uint8 [out_h, out_w, C]: Image.fromarray(img).resize((out_w, out_h), Image.BICUBIC), which is what the
+    reference's preprocessing calls (`scipy.misc.imresize(uint8_img, [s, s], 'bicubic')` passes a uint8 image to Pillow
+    unchanged)."""
+    return _resize('resize_u8_bicubic', bicubic_tables, img, out_h, out_w)
 
 
 def to_rgb(img):

@@ -1121,12 +1121,13 @@ def nearest_images(src_u8, queries, row0=None, col0=None, flip=None, lo=-1.0, hi
 _RESAMPLE_TABLES = {}
 
 
-def _resample_tables(Hi, Wi, Ho, Wo, device):
-    key = (Hi, Wi, Ho, Wo, str(device))
+def _resample_tables(Hi, Wi, Ho, Wo, device, filter='bilinear'):
+    key = (Hi, Wi, Ho, Wo, str(device), filter)
     hit = _RESAMPLE_TABLES.get(key)
     if hit is None:
-        from .evaluation.resize import bilinear_tables
-        (xb, xk), (yb, yk) = bilinear_tables(Wi, Wo), bilinear_tables(Hi, Ho)
+        from .evaluation import resize
+        tables = {'bilinear': resize.bilinear_tables, 'bicubic': resize.bicubic_tables}[filter]
+        (xb, xk), (yb, yk) = tables(Wi, Wo), tables(Hi, Ho)
         hit = _RESAMPLE_TABLES[key] = tuple(torch.from_numpy(t).to(device) for t in (xb, xk, yb, yk))
     return hit
 
@@ -1153,6 +1154,32 @@ def resample_bilinear(src, Ho, Wo, rows=None, out_u8=False, out=None):
         check(lib.t2i_resample_bilinear(_ptr(src), int(src.dtype == torch.float32), N, Hi, Wi, _ptr(r), B, Ho, Wo, _ptr(xb), _ptr(xk),
                                         xk.shape[1], _ptr(yb), _ptr(yk), yk.shape[1], _ptr(y), int(out_u8), wsp, wsn, _stream()),
               't2i_resample_bilinear')
+    return y
+
+
+def resample_u8(src, Ho, Wo, filter='bicubic', rows=None, out=None):
+    """Pillow's 8-bit Image.resize of a uint8 store [N,Hi,Wi,3] with BICUBIC (or BILINEAR) filtering, bit for bit: the
+    t2i_resample_bilinear launch with the filter's tables (evaluation/resize.py; the kernel takes any tap count and clips the
+    8-bit intermediate, which the negative bicubic lobes need).  rows int [B]: the store rows to take, in order (None: all N).
+    -> uint8 [B,Ho,Wo,3] (written into `out` if given)."""
+    if filter not in ('bicubic', 'bilinear'):
+        raise ValueError("resample_u8: filter must be 'bicubic' or 'bilinear', got %r" % (filter,))
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[3] != 3:
+        raise ValueError('resample_u8 expects a uint8 [N,H,W,3] store, got %s %s' % (src.dtype, tuple(src.shape)))
+    if not src.is_contiguous():
+        raise ValueError('resample_u8: the store must be contiguous')
+    N, Hi, Wi = src.shape[0], src.shape[1], src.shape[2]
+    B = N if rows is None else rows.numel()
+    shape = (B, Ho, Wo, 3)
+    y = torch.empty(shape, dtype=torch.uint8, device=src.device) if out is None else out
+    if tuple(y.shape) != shape or y.dtype != torch.uint8 or not y.is_contiguous() or y.device != src.device:
+        raise ValueError('resample_u8: out must be a contiguous uint8 %s on %s' % (shape, src.device))
+    if _live(src) and B > 0:
+        xb, xk, yb, yk = _resample_tables(Hi, Wi, Ho, Wo, src.device, filter)
+        r = rows.to(device=src.device, dtype=torch.int32).contiguous() if rows is not None else None
+        wsp, wsn = _ws_args(src, int(lib.t2i_resample_bilinear_workspace_bytes(B, Hi, Wo)))
+        check(lib.t2i_resample_bilinear(_ptr(src), 0, N, Hi, Wi, _ptr(r), B, Ho, Wo, _ptr(xb), _ptr(xk), xk.shape[1], _ptr(yb),
+                                        _ptr(yk), yk.shape[1], _ptr(y), 1, wsp, wsn, _stream()), 't2i_resample_bilinear')
     return y
 
 

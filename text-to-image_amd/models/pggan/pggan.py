@@ -47,6 +47,7 @@ class PGGAN(object):
         self.alpha_tra = 0.0                      # tf.Variable(0.0, trainable=False, name='alpha_tra')
         self._alpha_dev = torch.zeros(1, device=self.device)      # ... kept in device memory: graph-replayable fade-in
         self._graphs = None
+        self.restored = None
         # data parallelism (BASELINE config 5 "DP=8"; the reference is single-device): an optional dp.DataParallel — replicas
         # at local batch `batch_size`, critic and generator gradients all-reduced over RCCL, bucketed and overlapped with the
         # backward when eager, exchanged between captured graph segments under replay (same contract as models/wgancls)
@@ -360,19 +361,22 @@ class PGGAN(object):
         self.writer.add_summary(vals, idx)
         self.writer.flush()
 
-    def train(self, max_steps=None, log=None, side_effects=False, summaries=False):
+    def train(self, max_steps=None, log=None, side_effects=False, summaries=False, final_sample=False):
         """Stage schedule semantics of pggan.py:147-247: a transition stage restores the previous stage's variables
         (`get_variables_up_to_stage(stage - 1)`) from check_dir_read, a stabilisation stage its own; new variables keep
-        their fresh initialisation; checkpoints of `get_variables_up_to_stage(stage)` go to check_dir_write."""
+        their fresh initialisation; checkpoints of `get_variables_up_to_stage(stage)` go to check_dir_write.  What was
+        restored is kept in `self.restored` = (directory, step, variable names), None when nothing was.  final_sample: the
+        last iteration, which writes the last checkpoint, also writes a sample grid (the reference only samples every 2000)."""
         from ...utils.saver import Saver, load, save
         from ...utils.utils import get_balanced_factorization, save_captions, save_images
         log = log or (lambda s: (sys.stdout.write(s + '\n'), sys.stdout.flush()))
         saver = Saver(self.store, var_list=self.get_variables_up_to_stage(self.stage), max_to_keep=2)
         if side_effects and self.stage != 1:
             src = Saver(self.store, var_list=self.get_variables_up_to_stage(self.stage - 1)) if self.trans else saver
-            could_load, _ = load(src, None, self.check_dir_read)
+            could_load, step = load(src, None, self.check_dir_read)
             if not could_load:
                 raise RuntimeError('Could not load previous stage during transition' if self.trans else 'Could not load current stage')
+            self.restored = (self.check_dir_read, step, list(src.var_list))
         gen = torch.Generator(device=self.device).manual_seed(1234)
         if side_effects:
             sample_z = torch.randn((self.sample_num, self.z_dim), generator=gen, device=self.device)
@@ -393,7 +397,7 @@ class PGGAN(object):
                 epoch = idx // max(self.dataset.train.num_examples // self.batch_size, 1)
                 log('Epoch: [%2d] [%4d] time: %4.4f, d_loss: %.8f, g_loss: %.8f' % (
                     epoch, idx, time.time() - t0, float(out['d']['D_loss']), float(out['g']['G_loss'])))
-            if side_effects and idx % 2000 == 0:
+            if side_effects and (idx % 2000 == 0 or (final_sample and idx == end - 1)):
                 samples = torch.clamp(self.sampler(sample_z, sample_cond), -1.0, 1.0)
                 save_images(samples, get_balanced_factorization(samples.shape[0]), '{}train_{:02d}_{:04d}.png'.format(self.sample_path, 0, idx))
             if side_effects and (idx % 2000 == 0 or idx == end - 1):      # end - 1 == steps - 1 unless max_steps truncates

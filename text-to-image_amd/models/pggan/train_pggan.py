@@ -1,7 +1,15 @@
 """Stage driver of the progressive-growing schedule — reference models/pggan/train_pggan.py:17-69: stages
 1, 2t, 2, 3t, 3, ... (t = fade-in transition), batch 16 (8 from stage 6 on), 600000 images per stage, checkpoints
-written under `<CHECKPOINT_DIR>/stage<k>/` and read from the previous stage's directory.  Synthetic data stands in for
-the pickled datasets; `--iters` bounds the iterations per stage (the full 600000 // batch when omitted)."""
+written under `<CHECKPOINT_DIR>/stage<k>/` and read from the previous stage's directory.  `--iters` bounds the iterations
+per stage (the full 600000 // batch when omitted).
+
+Without `--cfg`, synthetic data stands in for the pickled datasets and everything goes under `--out`.  With `--cfg <yml>`
+(models/pggan/cfg/flowers.yml, birds.yml) the entry runs on the real dataset as the reference does: `TextDataset(DATASET_DIR,
+MODEL.SIZES[stage - 1])` per entry, checkpoints in CHECKPOINT_DIR/stage%d/, sample grids and TensorBoard events in SAMPLE_DIR
+and LOGS_DIR under stage%d/ or stage_t%d/, `train(side_effects=True, summaries=True)`; each entry's last iteration also writes
+a sample grid next to its last checkpoint.  Every argument error, every missing image store (the stage-size stores come from
+`python -m t2i_amd.preprocess.stage_images`) and a missing checkpoint of the stage the first entry starts from are reported
+before any device work."""
 import argparse
 import os
 import sys
@@ -25,9 +33,60 @@ def dataset_for(size, device):
     return SyntheticTextDataset(cfg, device)
 
 
+def _has_checkpoint(directory):
+    """What utils/saver.load will find: a `checkpoint` state file naming an archive that exists."""
+    import re
+    state = os.path.join(directory, 'checkpoint')
+    if not os.path.isfile(state):
+        return False
+    m = re.search(r'model_checkpoint_path: "([^"]+)"', open(state).read())
+    return bool(m) and os.path.isfile(os.path.join(directory, m.group(1)))
+
+
+def check_real_run(cfg, first, last, bench=False):
+    """Raises before any device work if an entry's image store or the first entry's starting checkpoint is missing."""
+    from t2i_amd.preprocess.dataset import FINAL_SIZE_TO_ORIG, TextDataset
+    sizes = list(cfg.MODEL.SIZES)
+    if len(sizes) < max(STAGE[first:last + 1]):
+        raise ValueError('MODEL.SIZES has %d entries; stage %d needs %d' % (len(sizes), max(STAGE[first:last + 1]), max(STAGE[first:last + 1])))
+    datadir = cfg.DATASET_DIR
+    for i in range(first, last + 1):
+        size = sizes[STAGE[i] - 1]
+        if size not in FINAL_SIZE_TO_ORIG or size != 4 * 2 ** (STAGE[i] - 1):
+            raise ValueError('MODEL.SIZES[%d] = %d: stage %d generates %dx%d images' % (STAGE[i] - 1, size, STAGE[i], 4 * 2 ** (STAGE[i] - 1),
+                                                                                    4 * 2 ** (STAGE[i] - 1)))
+        for split in ('train', 'test'):
+            d = os.path.join(datadir, split)
+            for name in (TextDataset.EMBEDDINGS, TextDataset.FILENAMES, TextDataset.CLASSES):
+                if not os.path.isfile(os.path.join(d, name)):
+                    raise FileNotFoundError('%s is missing (DATASET_DIR %r: the reference preprocessing writes it)' % (os.path.join(d, name), datadir))
+            store = os.path.join(d, '%dimages.pickle' % FINAL_SIZE_TO_ORIG[size])
+            if not os.path.isfile(store):
+                raise FileNotFoundError('%s is missing (stage %d trains on %dx%d crops of it); derive the stage-size stores from '
+                                        '600images.pickle with: python -m t2i_amd.preprocess.stage_images --dir %s' % (
+                                            store, STAGE[i], size, size, datadir))
+    if not bench and STAGE[first] != 1:
+        rdir = os.path.join(cfg.CHECKPOINT_DIR, 'stage%d/' % PREV_STAGE[first])
+        if not _has_checkpoint(rdir):
+            raise FileNotFoundError('entry %d (stage %d%s) starts from the stage-%d checkpoint in %s, which does not exist; run the '
+                                    'earlier entries first (--first %d)' % (first, STAGE[first], 't' if first % 2 else '',
+                                                                             PREV_STAGE[first], rdir, max(first - 1, 0)))
+
+
+def real_dataset(cfg, stage, device):
+    """train_pggan.py:53-60: the stage's TextDataset with both splits read."""
+    from t2i_amd.preprocess.dataset import TextDataset
+    datadir = cfg.DATASET_DIR
+    dataset = TextDataset(datadir, cfg.MODEL.SIZES[stage - 1], device=device)
+    dataset.test = dataset.get_data('%s/test' % datadir)
+    dataset.train = dataset.get_data('%s/train' % datadir)
+    return dataset
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default='./pggan_run/')
+    ap.add_argument('--cfg', default=None, help='config of the real-data run (models/pggan/cfg/flowers.yml); without it: synthetic data under --out')
+    ap.add_argument('--out', default='./pggan_run/', help='output directory of the synthetic run (unused with --cfg)')
     ap.add_argument('--iters', type=int, default=None, help='iterations per stage (default: 600000 // batch as the reference)')
     ap.add_argument('--first', type=int, default=0, help='index into the 15-entry schedule to start from')
     ap.add_argument('--last', type=int, default=len(STAGE) - 1)
@@ -35,20 +94,39 @@ def main(argv=None):
     ap.add_argument('--eager', action='store_true', help='--bench: keep eager launches instead of hipGraph replay')
     ap.add_argument('--bench', action='store_true', help='time `--iters` iterations of each entry instead of training with side effects')
     args = ap.parse_args(argv)
+    if not 0 <= args.first <= args.last < len(STAGE):
+        ap.error('--first %d / --last %d: need 0 <= first <= last <= %d' % (args.first, args.last, len(STAGE) - 1))
+    if args.iters is not None and args.iters < 1:
+        ap.error('--iters must be positive')
+    cfg = None
+    if args.cfg is not None:
+        from t2i_amd.utils.config import config_from_yaml
+        if not os.path.isfile(args.cfg):
+            raise FileNotFoundError('--cfg %s does not exist' % args.cfg)
+        cfg = config_from_yaml(args.cfg)
+        check_real_run(cfg, args.first, args.last, args.bench)
     K.set_math(args.math)
     dev = torch.device('cuda')
+    records = []
     for i in range(args.first, args.last + 1):
         t = (i % 2 == 1)
         batch_size = 8 if STAGE[i] >= 6 else 16
         max_iters = 600000 // batch_size
-        wdir = os.path.join(args.out, 'checkpoints', 'stage%d/' % STAGE[i])
-        rdir = os.path.join(args.out, 'checkpoints', 'stage%d/' % PREV_STAGE[i])
-        sample_path = os.path.join(args.out, 'samples', ('stage_t%d/' if t else 'stage%d/') % STAGE[i])
-        for d in (wdir, rdir, sample_path):
+        sub = ('stage_t%d/' if t else 'stage%d/') % STAGE[i]
+        if cfg is None:
+            wdir = os.path.join(args.out, 'checkpoints', 'stage%d/' % STAGE[i])
+            rdir = os.path.join(args.out, 'checkpoints', 'stage%d/' % PREV_STAGE[i])
+            sample_path, logs_dir = os.path.join(args.out, 'samples', sub), None
+        else:
+            wdir = os.path.join(cfg.CHECKPOINT_DIR, 'stage%d/' % STAGE[i])
+            rdir = os.path.join(cfg.CHECKPOINT_DIR, 'stage%d/' % PREV_STAGE[i])
+            sample_path, logs_dir = os.path.join(cfg.SAMPLE_DIR, sub), os.path.join(cfg.LOGS_DIR, sub)
+        for d in (wdir, rdir, sample_path) + ((logs_dir,) if logs_dir else ()):
             os.makedirs(d, exist_ok=True)
         size = 4 * 2 ** (STAGE[i] - 1)
         pggan = PGGAN(batch_size=batch_size, steps=max_iters, check_dir_write=wdir, check_dir_read=rdir,
-                      dataset=dataset_for(size, dev), sample_path=sample_path, log_dir=None, stage=STAGE[i], trans=t, device=dev)
+                      dataset=dataset_for(size, dev) if cfg is None else real_dataset(cfg, STAGE[i], dev), sample_path=sample_path,
+                      log_dir=logs_dir, stage=STAGE[i], trans=t, device=dev)
         if args.bench:
             gen = torch.Generator(device=dev).manual_seed(0)
             feed = pggan.make_feed(gen)
@@ -65,10 +143,16 @@ def main(argv=None):
             dt = (time.perf_counter() - t0) / n
             print('pggan stage %d%s  %3dx%-3d batch %2d  %s  %.2f ms/iteration  %.1f images/s' % (
                 STAGE[i], 't' if t else ' ', size, size, batch_size, args.math + (' eager' if args.eager else ' graphs'), dt * 1e3, batch_size / dt))
-        else:
+        elif cfg is None:
             pggan.train(max_steps=args.iters, side_effects=True)
+        else:
+            pggan.train(max_steps=args.iters, side_effects=True, summaries=True, final_sample=True)
+            pggan.writer.close()
+        records.append(dict(entry=i, stage=STAGE[i], trans=t, restored=pggan.restored, checkpoint_dir=wdir, sample_path=sample_path,
+                            logs_dir=logs_dir))
         del pggan
         torch.cuda.empty_cache()
+    return records
 
 
 if __name__ == '__main__':

@@ -1,0 +1,90 @@
+"""The same images through every stage — reference models/pggan/visualize_last_stage.py.
+
+    python text-to-image_amd/models/pggan/visualize_last_stage.py --cfg models/pggan/cfg/flowers.yml
+
+One z [64, 128] ~ N(0, 1) and the embeddings of one window of 64 test images (its first caption each) at a random position,
+drawn in the reference's order; then, for stages 1 ... 7, that stage's `g_net` restored from CHECKPOINT_DIR/stage%d/ and its
+images with conditioning noise on, clipped to [-1, 1].  `stage_sample` is the reference's gen_pggan_sample, which calls
+`scipy.misc.imresize(float_image, (128, 128), interp='nearest')`: per image, scipy's bytescale (min -> 0, max -> 255, + 0.5,
+truncated to uint8), Pillow's NEAREST resize to 128 x 128, then / 127.5 - 1.  One sheet per caption,
+SAMPLE_DIR/<dataset>_visual/stages/stages{idx}.png: the seven stages side by side, the caption broken at 35 characters."""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))))
+
+import t2i_amd  # noqa: E402,F401
+from t2i_amd.models.pggan.eval_pggan import generate, load_stage_dataset, restore_generator, stage_model  # noqa: E402
+from t2i_amd.models.wgancls.visualize_wgan import WGanClsVisualizer  # noqa: E402
+from t2i_amd.utils import visualize as V  # noqa: E402
+
+STAGES = [1, 2, 3, 4, 5, 6, 7]
+
+
+def bytescale(data):
+    """scipy.misc.bytescale(data) for a float array (cmin / cmax = its min / max), in the array's own dtype as scipy computes it."""
+    cmin, cmax = data.min(), data.max()
+    cscale = cmax - cmin
+    if cscale == 0:
+        cscale = 1
+    scale = float(255 - 0) / cscale
+    bytedata = (data - cmin) * scale + 0
+    return (bytedata.clip(0, 255) + 0.5).astype(np.uint8)
+
+
+def stage_sample(samples, size=128):
+    """gen_pggan_sample: [stages][B, h, w, 3] in [-1, 1] -> float64 [stages, B, size, size, 3]."""
+    from PIL import Image
+    out = np.empty((len(samples), len(samples[0]), size, size, 3))
+    for sidx, stage in enumerate(samples):
+        for i, sample in enumerate(stage):
+            u8 = bytescale((np.array(sample) + 1.0) * 127.5)
+            out[sidx, i] = np.array(Image.fromarray(u8).resize((size, size), Image.NEAREST)) / 127.5 - 1.0
+    return out
+
+
+def visualize_last_stage(cfg, dataset, device, batch_size=64, stages=STAGES, **widths):
+    """-> dict(sheets: the uint8 sheets written, samples: the clipped stage outputs, resized: stage_sample's result)."""
+    z_dim = widths.get('z_dim', 128)
+    z_sample = np.random.standard_normal((batch_size, z_dim))
+    dataset_pos = np.random.randint(0, dataset.test.num_examples)
+    _, conditions, _, captions = dataset.test.next_batch_test(batch_size, dataset_pos, 1)
+    cond = torch.as_tensor(V._host(conditions[0]), dtype=torch.float32).to(device).reshape(batch_size, -1)
+    z = torch.as_tensor(z_sample, dtype=torch.float32).to(device)
+    print('Generating images for all stages...', flush=True)
+    all_samples = []
+    for stage in stages:
+        print('Generating stage %d' % stage, flush=True)
+        m = stage_model(cfg, stage, batch_size, dataset, device, **widths)
+        restore_generator(m)
+        all_samples.append(generate(m, z, cond).cpu().numpy())
+        del m
+    resized = stage_sample(all_samples, 128)
+    sheets = []
+    for idx in range(batch_size):
+        sheets.append(V.save_cap_batch(resized[:, idx], WGanClsVisualizer._first_caption(captions, idx),
+                                       '{}/{}_visual/stages/stages{}.png'.format(cfg.SAMPLE_DIR, dataset.name, idx), split=35))
+    return dict(sheets=sheets, samples=all_samples, resized=resized)
+
+
+def main(argv=None, **widths):
+    from t2i_amd.utils.config import config_from_yaml
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--cfg', required=True, help='models/pggan/cfg/flowers.yml or birds.yml')
+    args = ap.parse_args(argv)
+    cfg = config_from_yaml(args.cfg)
+    for stage in STAGES:
+        d = os.path.join(cfg.CHECKPOINT_DIR, 'stage%d' % stage)
+        if not os.path.isfile(os.path.join(d, 'checkpoint')):
+            raise RuntimeError('Could not load stage %d (no checkpoint in %s)' % (stage, d))
+    dev = torch.device('cuda')
+    dataset = load_stage_dataset(cfg, 5, dev)         # TextDataset(datadir, 64) as the reference: only its test captions are used
+    return visualize_last_stage(cfg, dataset, dev, **widths)
+
+
+if __name__ == '__main__':
+    main()
