@@ -222,6 +222,15 @@ int t2i_bn_finalize(const float* sum, const float* m2, int64_t n, int32_t C, con
  * instead of silently not writing it. */
 int t2i_bn_apply(const void* x, const float* scale, const float* shift, int64_t rows, int32_t C, int act,
                  float alpha, void* y, void* y_h, int32_t dtype, t2i_stream_t stream);
+/* Inference batch norm in one launch: y = res_act(residual + act(x*scale[c] + shift[c])) over x [rows, C], with
+ * scale = gamma / sqrt(moving_variance + eps) and shift = beta - moving_mean * scale formed inside the kernel from the four [C]
+ * vectors (any C: the channels are tiled).  residual: NULL, or a tensor of x's shape and dtype — then res_act is applied to the
+ * sum (the closing join of a residual block); without it res_act / res_alpha are ignored.  dtype: x, residual and y are fp32 or
+ * bf16 tensors (bf16: 16-byte aligned, C % 4 == 0).  16-byte accesses when C % 4 == 0 and the tensors are 16-byte aligned, a
+ * scalar form otherwise.  Added within ABI v13: no existing argument list changed. */
+int t2i_bn_infer(const void* x, const float* gamma, const float* beta, const float* moving_mean, const float* moving_variance, float eps,
+                 int64_t rows, int32_t C, int act, float alpha, const void* residual, int res_act, float res_alpha, void* y, int32_t dtype,
+                 t2i_stream_t stream);
 /* dx = gamma*rstd*(dy - sum_dy/n - xhat*sum_dy_xhat/n), xhat = (x-mean)*rstd, sum_dy_xhat = rstd * sum_dy_x with
  * sum_dy_x = sum dy*(x - mean) (t2i_col_reduce / t2i_act_bwd_colsum with center = mean).  Also emits dgamma, dbeta. */
 int t2i_bn_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,

@@ -761,6 +761,98 @@ hipError_t bn_apply_launch(const void* x, const float* scale, const float* shift
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// inference batch norm in ONE launch: y = res_act(residual + act(x * scale[c] + shift[c])) with scale = gamma / sqrt(mv + eps) and
+// shift = beta - mm * scale formed by the workgroup itself.  Grid (row chunks, channel tiles of BN_INFER_CT): a workgroup first
+// puts the (scale, shift) pairs of its channel tile into LDS (8 KB: C = 16384 of the rank-2 norm is 16 tiles), then walks its
+// [rows_per_block, tile width] slab flat, so that every lane is busy whatever C is and a wave reads whole rows of the tile
+// contiguously.  One read of x (and residual), one write of y; the pairs come back from LDS as one ds_read_b128 per quad.
+// VEC: C % 4 == 0 and 16-byte aligned tensors (H: bf16 storage); else the scalar form (fp32 only).
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int BN_INFER_CT = 1024;
+
+template <bool VEC, bool H>
+__global__ __launch_bounds__(256) void bn_infer_kernel(const void* __restrict__ xv, const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, const float* __restrict__ mmean,
+                                                       const float* __restrict__ mvar, float eps, int64_t rows, int C, int rows_per_block,
+                                                       int act, float alpha, const void* __restrict__ resv, int res_act, float res_alpha,
+                                                       void* __restrict__ yv) {
+  __shared__ __attribute__((aligned(16))) float s_scale[BN_INFER_CT];
+  __shared__ __attribute__((aligned(16))) float s_shift[BN_INFER_CT];
+  const int c0 = blockIdx.y * BN_INFER_CT;
+  const int cw = min(BN_INFER_CT, C - c0);                 // this tile's width in channels
+  for (int c = threadIdx.x; c < cw; c += blockDim.x) {
+    const float sc = gamma[c0 + c] / sqrtf(mvar[c0 + c] + eps);
+    s_scale[c] = sc;
+    s_shift[c] = beta[c0 + c] - mmean[c0 + c] * sc;
+  }
+  __syncthreads();
+  const int64_t row0 = (int64_t)blockIdx.x * rows_per_block;
+  const int nrows = (int)min((int64_t)rows_per_block, rows - row0);
+  if (VEC) {
+    const unsigned q = (unsigned)cw >> 2;                  // quads per row of the tile
+    const unsigned total = (unsigned)nrows * q;
+    float* y = H ? nullptr : reinterpret_cast<float*>(yv);
+    void* yh = H ? yv : nullptr;
+    for (unsigned j = threadIdx.x; j < total; j += blockDim.x) {
+      const unsigned r = j / q, cq = j - r * q;
+      const size_t i4 = (size_t)(((row0 + r) * C + c0) >> 2) + cq;
+      float4 v = ld4<H>(xv, i4);
+      const float4 sc = *reinterpret_cast<const float4*>(s_scale + 4 * cq);
+      const float4 sh = *reinterpret_cast<const float4*>(s_shift + 4 * cq);
+      v.x = apply_act(v.x * sc.x + sh.x, act, alpha);
+      v.y = apply_act(v.y * sc.y + sh.y, act, alpha);
+      v.z = apply_act(v.z * sc.z + sh.z, act, alpha);
+      v.w = apply_act(v.w * sc.w + sh.w, act, alpha);
+      if (resv) {
+        const float4 e = ld4<H>(resv, i4);
+        v.x = apply_act(e.x + v.x, res_act, res_alpha);
+        v.y = apply_act(e.y + v.y, res_act, res_alpha);
+        v.z = apply_act(e.z + v.z, res_act, res_alpha);
+        v.w = apply_act(e.w + v.w, res_act, res_alpha);
+      }
+      st4(y, yh, i4, v);
+    }
+  } else {
+    const float* x = reinterpret_cast<const float*>(xv);
+    const float* res = reinterpret_cast<const float*>(resv);
+    float* y = reinterpret_cast<float*>(yv);
+    const unsigned total = (unsigned)nrows * (unsigned)cw;
+    for (unsigned j = threadIdx.x; j < total; j += blockDim.x) {
+      const unsigned r = j / (unsigned)cw, c = j - r * (unsigned)cw;
+      const size_t i = (size_t)((row0 + r) * C + c0) + c;
+      float v = apply_act(x[i] * s_scale[c] + s_shift[c], act, alpha);
+      if (res) v = apply_act(res[i] + v, res_act, res_alpha);
+      y[i] = v;
+    }
+  }
+}
+
+// vec: C % 4 == 0 and every tensor 16-byte aligned (the C API has checked; bf16 storage implies it)
+hipError_t bn_infer_launch(const void* x, const float* gamma, const float* beta, const float* mm, const float* mv, float eps, int64_t rows,
+                           int C, int act, float alpha, const void* residual, int res_act, float res_alpha, void* y, hipStream_t stream,
+                           bool vec, bool x_bf16) {
+  const int tiles = (C + BN_INFER_CT - 1) / BN_INFER_CT;
+  const int cw = C < BN_INFER_CT ? C : BN_INFER_CT;
+  const int per_row = vec ? cw >> 2 : cw;                  // work items (quads / elements) per row of a full tile
+  // about four items per lane and block; at most 4096 blocks over all tiles (a slab stays far below 2^31 items: the kernel's index type)
+  int64_t rpb = (1024 + per_row - 1) / per_row;
+  const int64_t max_chunks = 4096 / tiles > 0 ? 4096 / tiles : 1;
+  if ((rows + rpb - 1) / rpb > max_chunks) rpb = (rows + max_chunks - 1) / max_chunks;
+  if (rpb * per_row >= (int64_t)1 << 31) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((rows + rpb - 1) / rpb), (unsigned)tiles);
+  if (x_bf16)
+    hipLaunchKernelGGL((bn_infer_kernel<true, true>), grid, dim3(256), 0, stream, x, gamma, beta, mm, mv, eps, rows, C, (int)rpb, act, alpha,
+                       residual, res_act, res_alpha, y);
+  else if (vec)
+    hipLaunchKernelGGL((bn_infer_kernel<true, false>), grid, dim3(256), 0, stream, x, gamma, beta, mm, mv, eps, rows, C, (int)rpb, act, alpha,
+                       residual, res_act, res_alpha, y);
+  else
+    hipLaunchKernelGGL((bn_infer_kernel<false, false>), grid, dim3(256), 0, stream, x, gamma, beta, mm, mv, eps, rows, C, (int)rpb, act, alpha,
+                       residual, res_act, res_alpha, y);
+  return hipGetLastError();
+}
+
 // dgamma/dbeta double as scratch-free outputs; k_* coefficients live in the caller-visible dgamma-sized buffers
 hipError_t bn_bwd_launch(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
                          const float* sum_dy, const float* sum_dy_x, int64_t rows, int C, float* dx, float* dgamma,

@@ -35,6 +35,9 @@ hipError_t bn_bwd_fused_launch(const void*, const void*, const void*, const floa
 hipError_t bn_finalize_launch(const float*, const float*, int64_t, int, const float*, const float*, float, float, float*,
                               float*, float*, float*, float*, float*, hipStream_t);
 hipError_t bn_apply_launch(const void*, const float*, const float*, int64_t, int, int, float, float*, hipStream_t, void* y_h, bool x_bf16);
+hipError_t bn_infer_launch(const void* x, const float* gamma, const float* beta, const float* mm, const float* mv, float eps, int64_t rows,
+                           int C, int act, float alpha, const void* residual, int res_act, float res_alpha, void* y, hipStream_t stream,
+                           bool vec, bool x_bf16);
 size_t bn_grouped_ws(int64_t rows_g, int C, int groups);
 hipError_t bn_fwd_grouped_launch(const void*, int64_t, int, int, const float*, const float*, float, float, float*, float*, float*, float*, float*, float*,
                                  int, float, float*, void*, void*, hipStream_t, bool, const float*, const float*, int, int, int, int);
@@ -1275,6 +1278,19 @@ int t2i_bn_apply(const void* x, const float* scale, const float* shift, int64_t 
   const bool h = dtype == T2I_DT_BF16;
   return check(bn_apply_launch(x, scale, shift, rows, al ? C : -C, act, alpha, h ? nullptr : reinterpret_cast<float*>(y), (hipStream_t)stream,
                                h ? y : y_h, h), "t2i_bn_apply");
+}
+
+int t2i_bn_infer(const void* x, const float* gamma, const float* beta, const float* moving_mean, const float* moving_variance, float eps,
+                 int64_t rows, int32_t C, int act, float alpha, const void* residual, int res_act, float res_alpha, void* y, int32_t dtype,
+                 t2i_stream_t stream) {
+  if (!x || !gamma || !beta || !moving_mean || !moving_variance || !y || rows <= 0 || C <= 0) {
+    set_error("t2i_bn_infer: bad argument");
+    return T2I_ERR_INVALID;
+  }
+  const bool al = aligned16(x) && aligned16(y) && aligned16(residual);
+  if (int rc = h_contract(dtype, al, C, nullptr, "t2i_bn_infer")) return rc;
+  return check(bn_infer_launch(x, gamma, beta, moving_mean, moving_variance, eps, rows, C, act, alpha, residual, res_act, res_alpha, y,
+                               (hipStream_t)stream, al && (C & 3) == 0, dtype == T2I_DT_BF16), "t2i_bn_infer");
 }
 
 size_t t2i_bn_grouped_workspace_bytes(int64_t rows_per_group, int32_t C, int32_t groups) {

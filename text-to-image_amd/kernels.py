@@ -805,6 +805,25 @@ def bn_apply(x, scale, shift, act=ACT_NONE, alpha=0.2, out=None):
     return y
 
 
+def bn_infer(x, gamma, beta, moving_mean, moving_variance, eps=1e-5, act=ACT_NONE, alpha=0.2, residual=None, res_act=ACT_NONE, res_alpha=0.2):
+    """Inference batch norm in one launch (t2i_bn_infer): res_act(residual + act(x * scale + shift)) with scale / shift formed in the
+    kernel from gamma, beta and the moving statistics.  residual: None, or a tensor of x's shape and dtype."""
+    _chk(x, 'x')
+    C = x.shape[-1]
+    for name, v in (('gamma', gamma), ('beta', beta), ('moving_mean', moving_mean), ('moving_variance', moving_variance)):
+        if _chk(v, name, f32=True).numel() != C:
+            raise ValueError('%s has %d entries, x has %d channels' % (name, v.numel(), C))
+    if residual is not None:
+        _chk(residual, 'residual')
+        if residual.shape != x.shape:
+            raise ValueError('residual has shape %s, x has %s' % (tuple(residual.shape), tuple(x.shape)))
+    y = torch.empty_like(x)
+    if _live(x):
+        check(lib.t2i_bn_infer(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(moving_mean), _ptr(moving_variance), eps, x.numel() // C, C, act, alpha,
+                               _ptr(residual), res_act, res_alpha, _ptr(y), _same_dt(x, residual), _stream()), 't2i_bn_infer')
+    return y
+
+
 def bn_apply_groups(x, scales, shifts, act=ACT_NONE, alpha=0.2):
     """bn_apply on a batched pass: slice g of x along the batch axis is normalised with (scales[g], shifts[g]); one output tensor.
     (A wrapper of its own so that instrumentation sees one call per batch-norm layer, like every other layer of a batched pass.)"""

@@ -81,17 +81,25 @@ class GanCls(object):
             logits = conv2d(h, 1, (s16, s16), (s16, s16), 'valid', kernel_initializer=self.w_init)
             return (torch.sigmoid(logits) if _prob else None), logits
 
+    # The eval-mode generator (sampler, evaluator, visualiser; never differentiated) runs each of its ten batch norms as ONE launch
+    # (ops.batch_norm(fused_infer=True)), a bottleneck's closing add + relu inside its last norm.  False: the unfused inference path.
+    fused_infer = True
+
+    def _bn(self, x, train, act=None, residual=None, res_act=None):
+        if not train and self.fused_infer and not torch.is_grad_enabled():
+            return batch_norm(x, train=False, init=self.batch_norm_init, act=act, fused_infer=True, residual=residual, res_act=res_act)
+        y = batch_norm(x, train=train, init=self.batch_norm_init, act=act)
+        return y if residual is None else add(residual, y, act=res_act)
+
     def _bottleneck(self, x, mid, out, train):
-        bn_init = self.batch_norm_init
-        r = batch_norm(conv2d(x, mid, (1, 1), (1, 1), 'valid', kernel_initializer=self.w_init), train=train, init=bn_init, act=relu)
-        r = batch_norm(conv2d(r, mid, (3, 3), (1, 1), 'same', kernel_initializer=self.w_init), train=train, init=bn_init, act=relu)
-        r = batch_norm(conv2d(r, out, (3, 3), (1, 1), 'same', kernel_initializer=self.w_init), train=train, init=bn_init, act=None)
-        return add(x, r, act=relu)
+        r = self._bn(conv2d(x, mid, (1, 1), (1, 1), 'valid', kernel_initializer=self.w_init), train, act=relu)
+        r = self._bn(conv2d(r, mid, (3, 3), (1, 1), 'same', kernel_initializer=self.w_init), train, act=relu)
+        return self._bn(conv2d(r, out, (3, 3), (1, 1), 'same', kernel_initializer=self.w_init), train, act=None, residual=x, res_act=relu)
 
     def _upsample(self, x, nf, train, act):
         u = conv2d_transpose(x, nf, (4, 4), (2, 2), 'same', kernel_initializer=self.w_init)
         u = conv2d(u, nf, (3, 3), (1, 1), 'same', kernel_initializer=self.w_init)
-        return batch_norm(u, train=train, init=self.batch_norm_init, act=act)
+        return self._bn(u, train, act=act)
 
     def generator(self, z, embed, is_training=True, reuse=False):
         """-> image NHWC in [-1,1]  (reference model.py:111-192)"""
@@ -99,7 +107,7 @@ class GanCls(object):
         with S.variable_scope('g_net', reuse=reuse):
             code = torch.cat([z, dense(embed, self.compressed_embed_dim)], 1)
             h = dense(code, nf * 8 * 16, kernel_initializer=self.w_init)
-            h = batch_norm(h, train=is_training, init=self.batch_norm_init)
+            h = self._bn(h, is_training)
             h = h.reshape(-1, 4, 4, nf * 8)                       # NHWC reshape: free
             h = self._bottleneck(h, nf * 2, nf * 8, is_training)
             h = self._upsample(h, nf * 4, is_training, act=None)

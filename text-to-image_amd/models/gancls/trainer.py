@@ -1,5 +1,6 @@
-"""GanClsTrainer — reference models/gancls/trainer.py:12-164: losses, the two Adam optimizers (both under UPDATE_OPS) and
-the D-then-G update order of every iteration."""
+"""GanClsTrainer — reference models/gancls/trainer.py:12-164: losses, the two Adam optimizers (both under UPDATE_OPS), the
+D-then-G update order of every iteration and, behind train(side_effects=True), the loop's side effects: sampled captions, sample
+grids, checkpoints and resume."""
 import sys
 import time
 
@@ -200,23 +201,79 @@ class GanClsTrainer(object):
         self.writer.add_summary([S.image('g_sum', np_(g['G'])), S.scalar('g_loss', float(g['G_loss']))], counter)
         self.writer.flush()
 
-    def train(self, max_updates=None, log=None, summaries=False):
-        """summaries=True: an event file in cfg.LOGS_DIR with the reference's per-update summaries (write_summaries)."""
+    def make_saver(self):
+        """tf.train.Saver(max_to_keep=CHECKPOINTS_TO_KEEP) built after the optimizers (reference trainer.py:41-51): every global variable
+        under its tf.layers name — weights, batch-norm moving statistics, both optimizers' Adam slots and their step counts (from which
+        beta1_power / beta2_power follow) — so that a resumed run continues bit for bit."""
+        from ...utils.saver import Saver
+        return Saver(self.model.store, {'D_optim': self.D_optim, 'G_optim': self.G_optim},
+                     max_to_keep=int(getattr(self.cfg.TRAIN, 'CHECKPOINTS_TO_KEEP', 5)))
+
+    # the reference's periods (trainer.py:141,163): a sampler grid when counter % 100 == 0, a checkpoint when counter % 500 == 2
+    SAMPLE_PERIOD, CHECKPOINT_PERIOD, CHECKPOINT_PHASE = 100, 500, 2
+
+    def train(self, max_updates=None, log=None, summaries=False, side_effects=False, graphs=False):
+        """summaries=True: an event file in cfg.LOGS_DIR with the reference's per-update summaries (write_summaries).
+        max_updates: updates run by this call.
+        side_effects=True: the rest of reference trainer.py:83-164 — sample_z and the test window at a random position, its captions
+        printed; resume from the latest checkpoint of cfg.CHECKPOINT_DIR (counter from its name); the sampler's 8 x 8 grid
+        `SAMPLE_DIR/train_{epoch:02d}_{idx:04d}.png` when counter % 100 == 0 (outside any captured graph); a checkpoint when
+        counter % 500 == 2; the log line every update instead of every tenth.
+        graphs=True: the iteration is replayed from a hipGraph after its first eager run."""
         log = log or (lambda s: (sys.stdout.write(s + '\n'), sys.stdout.flush()))
+        m = self.model
         if summaries and getattr(self.cfg, 'LOGS_DIR', None):
             self.define_summaries()
-        t0, counter = time.time(), 1
+        counter = 1
+        if side_effects:
+            from random import randint
+            import numpy as np
+            from ...utils.saver import load, save
+            from ...utils.utils import get_balanced_factorization, save_images
+            sample_z = np.random.normal(0, 1, size=(m.sample_num, m.z_dim))
+            _, sample_embed, _, captions = self.dataset.test.next_batch_test(m.sample_num, randint(0, self.dataset.test.num_examples), 1)
+            sample_z = torch.as_tensor(sample_z, dtype=torch.float32).to(m.device)
+            sample_embed = torch.as_tensor(sample_embed[0]).to(device=m.device, dtype=torch.float32).reshape(m.sample_num, -1)
+            log(str(tuple(sample_embed.shape)))
+
+            def log_captions():
+                log('\nCaptions of the sampled x:')
+                for caption_idx, caption_batch in enumerate(captions):
+                    log('{}: {}'.format(caption_idx + 1, caption_batch[0]))
+                log('')
+            log_captions()
+            self.saver = self.make_saver()
+            could_load, checkpoint_counter = load(self.saver, None, self.cfg.CHECKPOINT_DIR)
+            if could_load:
+                counter = checkpoint_counter
+            log(' [*] Load SUCCESS' if could_load else ' [!] Load failed...')
+            self.start_counter = counter
+        t0, done, out = time.time(), 0, None
         for epoch in range(self.cfg.TRAIN.EPOCH):
-            updates_per_epoch = self.dataset.train.num_examples // self.model.batch_size
+            updates_per_epoch = self.dataset.train.num_examples // m.batch_size
             for idx in range(updates_per_epoch):
                 feed = self.make_feed()
                 out = self.iteration(feed)
+                if graphs and getattr(self, '_graphs', None) is None:
+                    self.enable_graphs(feed)
                 if getattr(self, 'writer', None) is not None:
                     self.write_summaries(counter, feed, out)
-                if counter % 10 == 0:
+                if not side_effects and counter % 10 == 0:
                     log('Epoch: [%2d] [%4d/%4d] time: %4.4f, d_loss: %.8f, g_loss: %.8f' % (
                         epoch, idx, updates_per_epoch, time.time() - t0, float(out['d']['D_loss']), float(out['g']['G_loss'])))
                 counter += 1
-                if max_updates is not None and counter > max_updates:
+                done += 1
+                if side_effects:
+                    err_d, err_g = float(out['d']['D_loss']), float(out['g']['G_loss'])
+                    log('Epoch: [%2d] [%4d/%4d] time: %4.4f, d_loss: %.8f, g_loss: %.8f' % (
+                        epoch, idx, updates_per_epoch, time.time() - t0, err_d, err_g))
+                    if counter % self.SAMPLE_PERIOD == 0:
+                        save_images(m.sampler(sample_z, sample_embed), get_balanced_factorization(m.sample_num),
+                                    '{}train_{:02d}_{:04d}.png'.format(self.cfg.SAMPLE_DIR, epoch, idx))
+                        log('[Sample] d_loss: %.8f, g_loss: %.8f' % (err_d, err_g))
+                        log_captions()
+                    if counter % self.CHECKPOINT_PERIOD == self.CHECKPOINT_PHASE:
+                        save(self.saver, None, self.cfg.CHECKPOINT_DIR, counter)
+                if max_updates is not None and done >= max_updates:
                     return out
         return out

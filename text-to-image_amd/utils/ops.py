@@ -160,13 +160,20 @@ class update_ops(object):
         _UPDATE_OPS[0] = self.prev
 
 
-def batch_norm(x, train, init=None, act=None, name=None, eps=1e-5, decay=0.9, df=NHWC, groups=1):
+def batch_norm(x, train, init=None, act=None, name=None, eps=1e-5, decay=0.9, df=NHWC, groups=1, fused_infer=False, residual=None, res_act=None):
     """reference utils/ops.py:7-29 (tf.contrib.layers.batch_norm, fused, scale=True).  Rank-4 (per channel) or rank-2
     (per feature).  Variables: <scope>/BatchNorm[_k]/{beta, gamma, moving_mean, moving_variance}.
     groups > 1 (not in the reference; training mode): x is a batched pass whose `groups` equal slices along the batch axis are separate
-    passes of the reference graph — each slice is normalised with its own batch statistics (autograd.BatchNormTrainGroupedFn)."""
+    passes of the reference graph — each slice is normalised with its own batch statistics (autograd.BatchNormTrainGroupedFn).
+    fused_infer (not in the reference; inference only, no gradient): the whole norm is ONE launch (kernels.bn_infer: scale / shift are formed
+    in the kernel), and with `residual` (a tensor of x's shape) the result is res_act(residual + act(norm(x))) — a residual block's closing
+    add(residual, ·, res_act) in the same launch."""
     st = S.default_store()
     _check_df(df)
+    if fused_infer and (train or groups > 1):
+        raise ValueError('fused_infer is the inference path: train must be False and groups 1')
+    if residual is not None and not fused_infer:
+        raise ValueError('residual needs fused_infer=True')
     if x.dim() == 4:
         xp = _phys(x, df)
     elif x.dim() == 2:
@@ -197,6 +204,16 @@ def batch_norm(x, train, init=None, act=None, name=None, eps=1e-5, decay=0.9, df
     elif train:
         upd = _UPDATE_OPS[0]
         y, _, _ = A.BatchNormTrainFn.apply(xp, gamma, beta, mm if upd else None, mv if upd else None, eps, decay, kind, alpha, max(int(upd), 1))
+    elif fused_infer:
+        if isinstance(xp, ST.Stacked) or post is not None:
+            raise NotImplementedError('fused_infer takes a plain tensor and a fusable activation')
+        rkind, ralpha, rpost = _split_act(res_act)
+        if rpost is not None:
+            raise NotImplementedError('fused_infer: res_act must be None or an ops.Activation')
+        res = None
+        if residual is not None:
+            res = (_phys(residual, df) if x.dim() == 4 else residual).detach().contiguous()
+        y = K.bn_infer(xp.detach().contiguous(), gamma.detach(), beta.detach(), mm, mv, eps, kind, alpha, res, rkind, ralpha)
     else:
         # inference: y = act(x*scale + shift) with the moving statistics; [C]-sized host-side vector math
         with torch.no_grad():
