@@ -72,7 +72,7 @@ typedef struct t2i_conv_desc {
 enum { T2I_MATH_F32 = 0, T2I_MATH_BF16 = 1 };
 
 /* ---- library ------------------------------------------------------------------------------------------------ */
-int t2i_version(void);            /* ABI version, currently 13 (v13: t2i_cosine_distance added — no existing signature changed; v12: t2i_pool_dropout, t2i_softmax_ce_head (+ workspace query), t2i_pooled_grad_scatter and t2i_rmsprop_tf added — no existing signature changed; v11: t2i_resample_bilinear, t2i_pool2d, t2i_channel_slice_copy, t2i_gram_accumulate and their workspace queries added — no existing signature changed; v10: t2i_nearest_images and t2i_nearest_images_workspace_bytes added — no existing signature changed; v9: t2i_conv_opts gained xform_valid_rows / xform_plane_rows, t2i_bn_train_fwd_grouped gained moving_groups, t2i_trunc_normal and t2i_zero_ranges added; v8: t2i_sigmoid_ce_head, t2i_bn_train_fwd_grouped, t2i_bn_bwd_grouped, t2i_bn_grouped_workspace_bytes added — no existing signature changed; v7: v7: t2i_conv2d_bwd_pair, t2i_row_scale_div, t2i_stat, t2i_filter_cache_assume added, t2i_adam_tf takes m == NULL at beta1 == 0 — no existing signature changed; v2: t2i_conv_desc.math; v3: caller-owned filter-cache arena,
+int t2i_version(void);            /* ABI version, currently 13 (v13: t2i_cosine_distance added, then t2i_bn_infer and t2i_bytescale_nearest (+ workspace query) — no existing signature changed; v12: t2i_pool_dropout, t2i_softmax_ce_head (+ workspace query), t2i_pooled_grad_scatter and t2i_rmsprop_tf added — no existing signature changed; v11: t2i_resample_bilinear, t2i_pool2d, t2i_channel_slice_copy, t2i_gram_accumulate and their workspace queries added — no existing signature changed; v10: t2i_nearest_images and t2i_nearest_images_workspace_bytes added — no existing signature changed; v9: t2i_conv_opts gained xform_valid_rows / xform_plane_rows, t2i_bn_train_fwd_grouped gained moving_groups, t2i_trunc_normal and t2i_zero_ranges added; v8: t2i_sigmoid_ce_head, t2i_bn_train_fwd_grouped, t2i_bn_bwd_grouped, t2i_bn_grouped_workspace_bytes added — no existing signature changed; v7: v7: t2i_conv2d_bwd_pair, t2i_row_scale_div, t2i_stat, t2i_filter_cache_assume added, t2i_adam_tf takes m == NULL at beta1 == 0 — no existing signature changed; v2: t2i_conv_desc.math; v3: caller-owned filter-cache arena,
                                    * t2i_tuning_set, t2i_kt_sgd; v4: t2i_filter_cache_refresh, bf16 operand images; v5: t2i_conv_opts
                                    * and explicit image arguments instead of thread-local one-shot hand-overs; v6: bf16 STORAGE —
                                    * activation tensors may be bf16 at this interface: t2i_dtype arguments, t2i_conv_opts.in_dtype /
@@ -510,6 +510,25 @@ int t2i_gram_accumulate(const float* X, int64_t n, int32_t d, const float* s, do
  * pointer) return T2I_ERR_INVALID before anything is launched. */
 int t2i_cosine_distance(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t n, int32_t d, double* out,
                         t2i_stream_t stream);
+
+/* ---- caption sheets: scipy.misc.imresize(float image, (size, size), interp='nearest') -------------------------------------- */
+/* The reference's gen_multiple_stage_img / gen_pggan_sample resize FLOAT images with scipy.misc.imresize, i.e. scipy's bytescale
+ * per image, Pillow's NEAREST resize, and (on the host, not here) / 127.5 - 1.  x fp32 [N, h, w, C] (contiguous, C in 1..4) ->
+ * y uint8 [N, size, size, C].  Per image n, every operation rounded to fp32 on its own, in this order, no fused multiply-add:
+ *   v = fl32(fl32(x + 1) * 127.5);  cmin, cmax = min, max of v over the whole image, all channels;
+ *   cscale = fl32(cmax - cmin), replaced by 1 when it is 0;  scale = fl32(255 / cscale);
+ *   u8 = (uint8) trunc(clip(fl32(fl32(v - cmin) * scale), 0, 255) + 0.5)
+ * Output pixel (r, c) reads source pixel (floor((r + 0.5) * h / size), floor((c + 0.5) * w / size)), computed in integers.
+ * Inputs are finite by contract (a generator's tanh output, clipped or not); there is no NaN policy.
+ * Two launches: partial min / max per (image, chunk) into the workspace (16-byte loads where h*w*C % 4 == 0 and x is 16-byte
+ * aligned), then per (image, tile of output rows) a fold of that image's partials and the gather, which quantises only the source
+ * pixels it reads.  No atomics: results are bitwise identical from call to call.  An image holds at most 2^30 elements on either
+ * side.  Bad arguments (a NULL pointer, N, h, w or size <= 0, C outside 1..4) return T2I_ERR_INVALID and a workspace that is NULL,
+ * misaligned or smaller than the query T2I_ERR_WORKSPACE, before anything is launched.  Added within ABI v13: no existing
+ * argument list changed. */
+size_t t2i_bytescale_nearest_workspace_bytes(int64_t N, int32_t h, int32_t w, int32_t C);
+int t2i_bytescale_nearest(const float* x, int64_t N, int32_t h, int32_t w, int32_t C, int32_t size, uint8_t* y, void* ws,
+                          size_t ws_bytes, t2i_stream_t stream);
 
 /* ---- InceptionV3 fine-tuning (reference models/inception/trainer.py) -------------------------------------------------- */
 /* AvgPool_1a_8x8 + Dropout_1b of slim inception_v3(is_training=True): x fp32 [B, HW, D] (the Mixed_7c output, HW = 64) ->

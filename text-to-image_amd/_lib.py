@@ -114,7 +114,9 @@ SIGNATURES = {
     't2i_gram_accumulate_workspace_bytes': (_sz, [_i64, _i32]),
     't2i_gram_accumulate': (ctypes.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _sz, _p]),
     't2i_cosine_distance': (ctypes.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p]),
-    't2i_pool_dropout': (ctypes.c_int, [_p, _i32, _i32, _i32, _f, ctypes.c_uint64, ctypes.c_uint64, _p, _p, _p, _p]),
+    't2i_bytescale_nearest_workspace_bytes': (_sz, [_i64, _i32, _i32, _i32]),
+    't2i_bytescale_nearest': (ctypes.c_int, [_p, _i64, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),
+    't2i_pool_dropout':(ctypes.c_int, [_p, _i32, _i32, _i32, _f, ctypes.c_uint64, ctypes.c_uint64, _p, _p, _p, _p]),
     't2i_softmax_ce_head_workspace_bytes': (_sz, [_i32, _i32]),
     't2i_softmax_ce_head': (ctypes.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _sz, _p]),
     't2i_pooled_grad_scatter': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _f, _i32, ctypes.POINTER(ctypes.c_void_p),

@@ -67,6 +67,8 @@ hipError_t pool2d_launch(const float*, int, int, int, int, int, int, int, int, i
 hipError_t channel_slice_copy_launch(const float*, int64_t, int, float*, int, int, hipStream_t);
 hipError_t gram_accumulate_launch(const float*, int, int, const float*, double*, double*, hipStream_t);
 hipError_t cosine_distance_launch(const float*, int64_t, const float*, int64_t, int64_t, int, double*, hipStream_t);
+size_t bytescale_nearest_ws(int64_t N, int64_t per);
+hipError_t bytescale_nearest_launch(const float*, int64_t, int, int, int, int, uint8_t*, void*, hipStream_t);
 // implemented in t2i_incep_train.hip
 size_t softmax_ce_head_ws(int B, int C);
 hipError_t pool_dropout_launch(const float*, int, int, int, float, unsigned long long, unsigned long long, float*, float*, float*,
@@ -1578,6 +1580,34 @@ int t2i_cosine_distance(const float* a, int64_t lda, const float* b, int64_t ldb
     return T2I_ERR_INVALID;
   }
   return check(cosine_distance_launch(a, lda, b, ldb, n, d, out, (hipStream_t)stream), "t2i_cosine_distance");
+}
+
+// per-image element counts of t2i_bytescale_nearest stay within 2^30 so that the kernels index an image with int32
+static bool bytescale_shape_ok(int64_t N, int32_t h, int32_t w, int32_t C, int32_t size) {
+  const int64_t lim = (int64_t)1 << 30;
+  if (N <= 0 || h <= 0 || w <= 0 || size <= 0 || C < 1 || C > 4) return false;
+  if ((int64_t)h * w > lim / C || (int64_t)size * size > lim / C) return false;
+  const int64_t per = (int64_t)h * w * C;
+  return N <= INT32_MAX / ((per + 8191) / 8192) && N <= INT32_MAX / size;      // (image, chunk) and (image, row tile) grids
+}
+
+size_t t2i_bytescale_nearest_workspace_bytes(int64_t N, int32_t h, int32_t w, int32_t C) {
+  return bytescale_shape_ok(N, h, w, C, 1) ? bytescale_nearest_ws(N, (int64_t)h * w * C) : 0;
+}
+
+int t2i_bytescale_nearest(const float* x, int64_t N, int32_t h, int32_t w, int32_t C, int32_t size, uint8_t* y, void* ws,
+                          size_t ws_bytes, t2i_stream_t stream) {
+  if (!x || !y || !bytescale_shape_ok(N, h, w, C, size)) {
+    set_error("t2i_bytescale_nearest: bad argument (N=%lld h=%d w=%d C=%d size=%d, x %s, y %s; C in 1..4, an image of at most 2^30 "
+              "elements)", (long long)N, h, w, C, size, x ? "given" : "NULL", y ? "given" : "NULL");
+    return T2I_ERR_INVALID;
+  }
+  const size_t need = bytescale_nearest_ws(N, (int64_t)h * w * C);
+  if (!ws || ws_bytes < need || !aligned16(ws)) {
+    set_error("t2i_bytescale_nearest: workspace too small or misaligned (%zu bytes, need %zu)", ws_bytes, need);
+    return T2I_ERR_WORKSPACE;
+  }
+  return check(bytescale_nearest_launch(x, N, h, w, C, size, y, ws, (hipStream_t)stream), "t2i_bytescale_nearest");
 }
 
 int t2i_pool_dropout(const float* x, int32_t B, int32_t HW, int32_t D, float keep, uint64_t seed, uint64_t step, float* pre,

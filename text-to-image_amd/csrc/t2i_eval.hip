@@ -17,6 +17,8 @@
 //   cosine_kernel           IMD (reference evaluation/imd.py, scipy.spatial.distance.cosine): one wave64 per row pair; each
 //                           lane sums u.v, u.u and v.v of a fixed stride of columns in fp64, then a fixed butterfly across
 //                           the wave.  No atomics, bitwise-repeatable.
+//   bytescale_minmax_kernel / bytescale_gather_kernel   the caption sheets' scipy.misc.imresize(float image, 'nearest'): scipy's
+//                           per-image bytescale and Pillow's NEAREST resize, bit for bit (described at the kernels).
 // The element-wise kernels read and write 16-byte vectors over channels where C % 4 == 0 (and the slice is aligned).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -270,9 +272,161 @@ __global__ __launch_bounds__(kThreads) void cosine_kernel(const float* __restric
   }
 }
 
+// ---- bytescale + nearest resize: scipy.misc.imresize(float_image, (size, size), 'nearest') before its / 127.5 - 1 ----------
+// Per image: v = fl32(fl32(x + 1) * 127.5); cmin / cmax = min / max of v over the whole image; cscale = fl32(cmax - cmin), 1 when
+// that is 0; scale = fl32(255 / cscale); u8 = (uint8) trunc(clip(fl32(fl32(v - cmin) * scale), 0, 255) + 0.5) — every operation
+// rounded to fp32 on its own (no fused multiply-add), as NumPy evaluates scipy's bytescale on a float32 array.  Output pixel
+// (r, c) takes source pixel (floor((r + 0.5) * h / size), floor((c + 0.5) * w / size)), in exact integer arithmetic.
+// Inputs are finite by contract (a generator's tanh output, clipped or not): there is no NaN policy.
+// Two launches, no atomics (min and max do not depend on order, so the result is bitwise repeatable):
+//   bytescale_minmax_kernel   one workgroup per (image, chunk of kBsChunk elements): partial min / max of v into the workspace;
+//   bytescale_gather_kernel   one workgroup per (image, tile of output rows): folds its image's partials, then quantises only
+//                             the source pixels it gathers.
+constexpr int kBsChunk = kThreads * 4 * 8;          // elements of one image that one workgroup of the first pass reduces
+constexpr int kBsTileBytes = kThreads * 4 * 4;      // output bytes one workgroup of the second pass writes (whole rows)
+
+__device__ __forceinline__ float bs_value(float x) {
+#pragma clang fp contract(off)
+  const float s = x + 1.0f;
+  return s * 127.5f;
+}
+
+__device__ __forceinline__ uint32_t bs_quant(float v, float cmin, float scale) {
+#pragma clang fp contract(off)
+  const float d = v - cmin;
+  float b = d * scale;
+  b = fminf(fmaxf(b, 0.0f), 255.0f);
+  const float r = b + 0.5f;
+  return (uint32_t)(int)r;
+}
+
+// min / max over the workgroup: a butterfly across each wave64, then LDS across the waves.  Every thread returns the result.
+__device__ __forceinline__ void block_minmax(float& lo, float& hi, float* s_lo, float* s_hi) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    lo = fminf(lo, __shfl_xor(lo, off, 64));
+    hi = fmaxf(hi, __shfl_xor(hi, off, 64));
+  }
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    s_lo[wave] = lo;
+    s_hi[wave] = hi;
+  }
+  __syncthreads();
+  lo = s_lo[0];
+  hi = s_hi[0];
+#pragma unroll
+  for (int k = 1; k < kThreads / 64; ++k) {
+    lo = fminf(lo, s_lo[k]);
+    hi = fmaxf(hi, s_hi[k]);
+  }
+}
+
+// kVec: per % 4 == 0 and x 16-byte aligned, so every image and every chunk starts on a 16-byte boundary and ends on a whole float4.
+template <bool kVec>
+__global__ __launch_bounds__(kThreads) void bytescale_minmax_kernel(const float* __restrict__ x, int per, int chunks,
+                                                                    float* __restrict__ part) {
+  __shared__ float s_lo[kThreads / 64], s_hi[kThreads / 64];
+  const int n = blockIdx.x / chunks, ch = blockIdx.x - n * chunks;
+  const float* img = x + (size_t)n * per;
+  const int beg = ch * kBsChunk;
+  const int end = min(beg + kBsChunk, per);
+  float lo = __builtin_inff(), hi = -__builtin_inff();
+  if (kVec) {
+    for (int i = beg + (int)threadIdx.x * 4; i < end; i += kThreads * 4) {
+      const float4 q = *reinterpret_cast<const float4*>(img + i);
+      const float a = bs_value(q.x), b = bs_value(q.y), c = bs_value(q.z), d = bs_value(q.w);
+      lo = fminf(lo, fminf(fminf(a, b), fminf(c, d)));
+      hi = fmaxf(hi, fmaxf(fmaxf(a, b), fmaxf(c, d)));
+    }
+  } else {
+    for (int i = beg + (int)threadIdx.x; i < end; i += kThreads) {
+      const float a = bs_value(img[i]);
+      lo = fminf(lo, a);
+      hi = fmaxf(hi, a);
+    }
+  }
+  block_minmax(lo, hi, s_lo, s_hi);
+  if (threadIdx.x == 0) {
+    part[2 * (size_t)blockIdx.x] = lo;
+    part[2 * (size_t)blockIdx.x + 1] = hi;
+  }
+}
+
+// kPack: size * C % 4 == 0 and y 4-byte aligned, so every tile starts on a 4-byte boundary and holds whole 4-byte words.
+template <bool kPack>
+__global__ __launch_bounds__(kThreads) void bytescale_gather_kernel(const float* __restrict__ x, int h, int w, int C, int size,
+                                                                    int tiles, int tile_rows, const float* __restrict__ part,
+                                                                    int chunks, uint8_t* __restrict__ y) {
+  __shared__ float s_lo[kThreads / 64], s_hi[kThreads / 64];
+  const int n = blockIdx.x / tiles, t = blockIdx.x - n * tiles;
+  float lo = __builtin_inff(), hi = -__builtin_inff();
+  for (int k = threadIdx.x; k < chunks; k += kThreads) {
+    lo = fminf(lo, part[2 * ((size_t)n * chunks + k)]);
+    hi = fmaxf(hi, part[2 * ((size_t)n * chunks + k) + 1]);
+  }
+  block_minmax(lo, hi, s_lo, s_hi);
+  const float cmin = lo;
+  float cscale = hi - lo;
+  if (cscale == 0.0f) cscale = 1.0f;
+  const float scale = __fdiv_rn(255.0f, cscale);
+
+  const float* img = x + (size_t)n * h * w * C;
+  uint8_t* out = y + (size_t)n * size * size * C;
+  const int row_bytes = size * C;
+  const int beg = t * tile_rows * row_bytes;
+  const int end = min(t * tile_rows + tile_rows, size) * row_bytes;
+  const int64_t den = 2 * (int64_t)size;
+  for (int i = beg + (int)threadIdx.x * 4; i < end; i += kThreads * 4) {
+    const int cnt = min(4, end - i);
+    uint32_t word = 0;
+    for (int k = 0; k < cnt; ++k) {
+      const int e = i + k;
+      const int r = e / row_bytes, rem = e - r * row_bytes;
+      const int c = rem / C, chn = rem - c * C;
+      const int sr = (int)(((2 * (int64_t)r + 1) * h) / den);          // floor((r + 0.5) * h / size) < h
+      const int sc = (int)(((2 * (int64_t)c + 1) * w) / den);
+      const uint32_t u = bs_quant(bs_value(img[((size_t)sr * w + sc) * C + chn]), cmin, scale);
+      if (kPack)
+        word |= u << (8 * k);
+      else
+        out[e] = (uint8_t)u;
+    }
+    if (kPack) *reinterpret_cast<uint32_t*>(out + i) = word;
+  }
+}
+
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+inline int bs_chunks(int64_t per) { return (int)((per + kBsChunk - 1) / kBsChunk); }
+
 }  // namespace
+
+size_t bytescale_nearest_ws(int64_t N, int64_t per) { return ((size_t)N * bs_chunks(per) * 2 * sizeof(float) + 255) & ~(size_t)255; }
+
+// The caller (t2i_capi.hip) has checked: per = h * w * C and size * size * C fit in 2^30, N * chunks and N * tiles fit in int32.
+hipError_t bytescale_nearest_launch(const float* x, int64_t N, int h, int w, int C, int size, uint8_t* y, void* ws,
+                                    hipStream_t stream) {
+  const int per = h * w * C;
+  const int chunks = bs_chunks(per);
+  float* part = static_cast<float*>(ws);
+  const dim3 g1((unsigned)(N * chunks));
+  if (per % 4 == 0 && al16(x))
+    hipLaunchKernelGGL(bytescale_minmax_kernel<true>, g1, dim3(kThreads), 0, stream, x, per, chunks, part);
+  else
+    hipLaunchKernelGGL(bytescale_minmax_kernel<false>, g1, dim3(kThreads), 0, stream, x, per, chunks, part);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const int row_bytes = size * C;
+  const int tile_rows = row_bytes >= kBsTileBytes ? 1 : kBsTileBytes / row_bytes;
+  const int tiles = (size + tile_rows - 1) / tile_rows;
+  const dim3 g2((unsigned)(N * tiles));
+  if (row_bytes % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 3) == 0)
+    hipLaunchKernelGGL(bytescale_gather_kernel<true>, g2, dim3(kThreads), 0, stream, x, h, w, C, size, tiles, tile_rows, part, chunks, y);
+  else
+    hipLaunchKernelGGL(bytescale_gather_kernel<false>, g2, dim3(kThreads), 0, stream, x, h, w, C, size, tiles, tile_rows, part, chunks, y);
+  return hipGetLastError();
+}
 
 size_t resample_bilinear_ws(int B, int Hi, int Wo) { return (((size_t)B * Hi * Wo * 3) + 255) & ~(size_t)255; }
 

@@ -1136,6 +1136,24 @@ def nearest_images(src_u8, queries, row0=None, col0=None, flip=None, lo=-1.0, hi
     return idx.long(), dist2
 
 
+def bytescale_nearest(x, size):
+    """The reference's scipy.misc.imresize(float_image, (size, size), interp='nearest') before its / 127.5 - 1, for a batch
+    (t2i_bytescale_nearest): per image scipy's bytescale of (x + 1) * 127.5 (the image's own min -> 0 and max -> 255, + 0.5,
+    truncated) and Pillow's NEAREST resize, bit for bit.  x float32 [N,h,w,C] (device, finite values, C in 1..4) -> uint8
+    [N,size,size,C]."""
+    if x.dtype != torch.float32 or x.dim() != 4 or not 1 <= x.shape[3] <= 4:
+        raise ValueError('bytescale_nearest expects a float32 [N,h,w,C] batch with C in 1..4, got %s %s' % (x.dtype, tuple(x.shape)))
+    N, h, w, C = (int(s) for s in x.shape)
+    size = int(size)
+    if min(N, h, w) <= 0 or size <= 0:
+        raise ValueError('bytescale_nearest: empty batch, image or output (x %s, size %d)' % (tuple(x.shape), size))
+    y = torch.empty((N, size, size, C), dtype=torch.uint8, device=x.device)
+    if _live(x):
+        wsp, wsn = _ws_args(x, int(lib.t2i_bytescale_nearest_workspace_bytes(N, h, w, C)))
+        check(lib.t2i_bytescale_nearest(_ptr(x.contiguous()), N, h, w, C, size, _ptr(y), wsp, wsn, _stream()), 't2i_bytescale_nearest')
+    return y
+
+
 # ---- evaluator: Inception score and FID (reference evaluation/, utils/utils.py prep_incep_img) -------------------------------
 _RESAMPLE_TABLES = {}
 

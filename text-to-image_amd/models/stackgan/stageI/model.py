@@ -99,17 +99,25 @@ class ConditionalGan(object):
             # _prob=False / groups: see models/gancls/model.py (the trainer stacks the critic passes of one sess.run along the batch axis)
             return (torch.sigmoid(logits) if _prob else None), logits
 
+    # The eval-mode generator (sampler, evaluators, visualiser; never differentiated) runs each of its ten batch norms as ONE launch
+    # (ops.batch_norm(fused_infer=True)), a bottleneck's closing add + relu inside its last norm.  False: the unfused inference path.
+    fused_infer = True
+
+    def _bn(self, x, train, act=None, residual=None, res_act=None):
+        if not train and self.fused_infer and not torch.is_grad_enabled():
+            return batch_norm(x, train=False, init=self.batch_norm_init, act=act, fused_infer=True, residual=residual, res_act=res_act)
+        y = batch_norm(x, train=train, init=self.batch_norm_init, act=act)
+        return y if residual is None else add(residual, y, act=res_act)
+
     def _bottleneck(self, x, mid, out, train):
-        bn_init = self.batch_norm_init
-        r = batch_norm(conv2d(x, mid, ks=(1, 1), s=(1, 1), padding='valid', init=self.w_init), train=train, init=bn_init, act=relu)
-        r = batch_norm(conv2d(r, mid, ks=(3, 3), s=(1, 1), init=self.w_init), train=train, init=bn_init, act=relu)
-        r = batch_norm(conv2d(r, out, ks=(3, 3), s=(1, 1), init=self.w_init), train=train, init=bn_init)
-        return add(x, r, act=relu)
+        r = self._bn(conv2d(x, mid, ks=(1, 1), s=(1, 1), padding='valid', init=self.w_init), train, act=relu)
+        r = self._bn(conv2d(r, mid, ks=(3, 3), s=(1, 1), init=self.w_init), train, act=relu)
+        return self._bn(conv2d(r, out, ks=(3, 3), s=(1, 1), init=self.w_init), train, residual=x, res_act=relu)
 
     def _upsample(self, x, nf, train, act):
         u = conv2d_transpose(x, nf, ks=(4, 4), s=(2, 2), init=self.w_init)
         u = conv2d(u, nf, ks=(3, 3), s=(1, 1), init=self.w_init)
-        return batch_norm(u, train=train, init=self.batch_norm_init, act=act)
+        return self._bn(u, train, act=act)
 
     def generator(self, z, embed, is_training=True, reuse=False, cond_noise=True, noise=None):
         """-> (image NHWC in [-1,1], mean, log_sigma)  (model.py:123-171)"""
@@ -118,7 +126,7 @@ class ConditionalGan(object):
             mean, log_sigma = self.generate_conditionals(embed)
             code = self.sample_normal_conditional(mean, log_sigma, cond_noise, noise)
             h = dense(torch.cat([z, code], 1), nf * 8 * s16 * s16, kernel_initializer=self.w_init)
-            h = batch_norm(h, train=is_training, init=self.batch_norm_init)
+            h = self._bn(h, is_training)
             h = h.reshape(-1, s16, s16, nf * 8)                     # NHWC reshape: free
             h = self._bottleneck(h, nf * 2, nf * 8, is_training)
             h = self._upsample(h, nf * 4, is_training, act=None)

@@ -110,24 +110,31 @@ class ConditionalGan(object):
             return (torch.sigmoid(logits) if _prob else None), logits
 
     # ---- generator (stageII/model.py:135-201) -----------------------------------------------------------------------------
+    # The eval-mode generator (sampler, evaluators, visualiser; never differentiated) runs each of its fifteen batch norms as ONE launch
+    # (ops.batch_norm(fused_infer=True)), a residual layer's closing add + relu inside its last norm.  False: the unfused inference path.
+    fused_infer = True
+
+    def _bn(self, x, train, act=None, residual=None, res_act=None):
+        if not train and self.fused_infer and not torch.is_grad_enabled():
+            return batch_norm(x, train=False, init=self.batch_norm_init, act=act, fused_infer=True, residual=residual, res_act=res_act)
+        y = batch_norm(x, train=train, init=self.batch_norm_init, act=act)
+        return y if residual is None else add(residual, y, act=res_act)
+
     def generator_encode_image(self, image, is_training=True):
-        bn_init = self.batch_norm_init
         h = conv2d(image, self.gf_dim, ks=(3, 3), s=(1, 1), act=relu)
-        h = batch_norm(conv2d(h, self.gf_dim * 2, ks=(4, 4), s=(2, 2)), train=is_training, init=bn_init, act=relu)
-        return batch_norm(conv2d(h, self.gf_dim * 4, ks=(4, 4), s=(2, 2)), train=is_training, init=bn_init, act=relu)
+        h = self._bn(conv2d(h, self.gf_dim * 2, ks=(4, 4), s=(2, 2)), is_training, act=relu)
+        return self._bn(conv2d(h, self.gf_dim * 4, ks=(4, 4), s=(2, 2)), is_training, act=relu)
 
     def generator_residual_layer(self, input_layer, is_training=True):
-        bn_init = self.batch_norm_init
-        h = batch_norm(conv2d(input_layer, self.gf_dim * 4, ks=(4, 4), s=(1, 1)), train=is_training, init=bn_init, act=relu)
-        h = batch_norm(conv2d(h, self.gf_dim * 4, ks=(4, 4), s=(1, 1)), train=is_training, init=bn_init)
-        return add(input_layer, h, act=relu)
+        h = self._bn(conv2d(input_layer, self.gf_dim * 4, ks=(4, 4), s=(1, 1)), is_training, act=relu)
+        return self._bn(conv2d(h, self.gf_dim * 4, ks=(4, 4), s=(1, 1)), is_training, residual=input_layer, res_act=relu)
 
     def generator_upsample(self, input_layer, is_training=True):
         h = input_layer
         for nf in (self.gf_dim * 2, self.gf_dim, self.gf_dim // 2, self.gf_dim // 4):
             h = conv2d_transpose(h, nf, ks=(4, 4), init=self.w_init)
             h = conv2d(h, nf, ks=(3, 3), s=(1, 1))
-            h = batch_norm(h, train=is_training, init=self.batch_norm_init, act=relu)
+            h = self._bn(h, is_training, act=relu)
         return conv2d(h, self.image_dims[-1], ks=(3, 3), s=(1, 1), act=tanh)
 
     def generator(self, image, embed, is_training=True, reuse=False, cond_noise=True, noise=None):
@@ -138,7 +145,7 @@ class ConditionalGan(object):
             code = self.sample_normal_conditional(mean, log_sigma, cond_noise, noise)
             h = concat_tile(encoded, code)
             h = conv2d(h, self.gf_dim * 4, ks=(3, 3), s=(1, 1))
-            h = batch_norm(h, train=is_training, init=self.batch_norm_init, act=relu)
+            h = self._bn(h, is_training, act=relu)
             for _ in range(4):
                 h = self.generator_residual_layer(h, is_training=is_training)
             return self.generator_upsample(h, is_training=is_training), mean, log_sigma

@@ -1,13 +1,13 @@
 """Entry point of StackGAN Stage II — reference models/stackgan/stageII/run.py:22-88.
 
     python -m t2i_amd.models.stackgan.stageII.run --cfg_stage_I <stage-I yaml> --cfg <stage-II yaml>
-                                                  [--train | --eval is|fid|imd [--incep-batch N]]
+                                                  [--train | --eval is|fid|imd [--incep-batch N] | --visualize [--interp N]]
                                                   [--synthetic] [--steps N] [--batch B] [--graphs 0|1]
 
 The modes and argument rules of stageI/run.py, on `TextDataset(DATASET_DIR, 256)` (304images.pickle).  Training restores the
 Stage-I generator from the Stage-I config's CHECKPOINT_DIR (a warning if there is none) and checkpoints the Stage-II networks;
-the evaluators chain the Stage-I and Stage-II generators (eval_stageii.py).  TRAIN.FLAG: False without `--train` raises in place
-of the caption visualiser (visualize_stageiI.py, not built)."""
+the evaluators and the caption visualiser (visualize_stageii.py, the reference's visualize_stageiI.py) chain the Stage-I and
+Stage-II generators.  TRAIN.FLAG: False without `--train` / `--visualize` raises in place of the visualiser."""
 import os
 import sys
 
@@ -42,6 +42,11 @@ def main(argv=None):
         stage_ii = ConditionalGan(stage_i, cfg, build_model=False)
         dataset = load_dataset(cfg, stage_ii.device)
         return run_eval(StageIIEval(sess=None, model=stage_ii, dataset=dataset, cfg=cfg, incep_batch_size=args.incep_batch), args.eval)
+    if args.visualize:
+        from t2i_amd.models.stackgan.stageII.visualize_stageii import StageIIVisualizer
+        stage_ii = ConditionalGan(stage_i, cfg, build_model=False)
+        dataset = load_dataset(cfg, stage_ii.device)
+        return StageIIVisualizer(sess=None, model=stage_ii, dataset=dataset, cfg=cfg).visualize(interp=args.interp)
     from t2i_amd.models.stackgan.stageII.trainer import ConditionalGanTrainer
     stage_ii = ConditionalGan(stage_i, cfg)
     dataset = load_dataset(cfg, stage_ii.device, synthetic=args.synthetic)

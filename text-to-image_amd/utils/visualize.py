@@ -174,6 +174,41 @@ def gen_captioned_img(gen, cond, z_dim, batch_size):
     return gen(sample_z, cond)
 
 
+def stage_imgs_host(samples, size):
+    """The host statement of the reference's float `scipy.misc.imresize(img, (size, size), interp='nearest')` before its
+    / 127.5 - 1: models/pggan/visualize_last_stage.py's `bytescale` of (img + 1) * 127.5, then Pillow's NEAREST resize.
+    samples [n,h,w,C] (C = 1 or 3) -> uint8 [n,size,size,C].  The checker of kernels.bytescale_nearest; nothing on the product
+    path calls it."""
+    from PIL import Image
+    from ..models.pggan.visualize_last_stage import bytescale
+    samples = np.asarray(_host(samples), dtype=np.float32)
+    C = samples.shape[3]
+    out = np.empty((samples.shape[0], size, size, C), np.uint8)
+    for i, sample in enumerate(samples):
+        u8 = bytescale((np.array(sample) + 1.0) * 127.5)
+        if C == 3:
+            out[i] = np.array(Image.fromarray(u8).resize((size, size), Image.NEAREST))
+        else:               # Pillow has no 1-, 2- or 4-channel image of this meaning: one grey plane at a time (NEAREST mixes no channels)
+            for ch in range(C):
+                out[i, :, :, ch] = np.array(Image.fromarray(u8[:, :, ch]).resize((size, size), Image.NEAREST))
+    return out
+
+
+def gen_multiple_stage_img(gens, cond, z_dim, batch_size, size=128):
+    """One z batch through every generator of `gens` (the stages of one model): the first 8 images of each, NOT clipped (the
+    reference does not clip here), resized to size x size as the reference's float imresize(..., 'nearest') does — per image
+    bytescale + Pillow NEAREST, one kernels.bytescale_nearest call per generator — then / 127.5 - 1 in float64 on the host, so
+    that a sheet's denormalize_images truncates exactly as the reference's.  -> float64 [8 * len(gens), size, size, 3]."""
+    sample_z = np.random.standard_normal((batch_size, z_dim))
+    out = []
+    for gen in gens:
+        imgs = gen(sample_z, cond)[:8]
+        if not torch.is_tensor(imgs) or not imgs.is_cuda:          # the file's generators hand back host arrays
+            imgs = torch.as_tensor(np.asarray(_host(imgs), dtype=np.float32)).to('cuda')
+        out.append(K.bytescale_nearest(imgs, size).cpu().numpy() / 127.5 - 1.0)
+    return np.concatenate(out)
+
+
 def closest_images_of_batch(samples, split):
     """Closest image of `split` (a preprocess.dataset.Dataset) to each of the Q samples [Q,s,s,3] (values clipped to [-1, 1]).
 
