@@ -530,6 +530,51 @@ size_t t2i_bytescale_nearest_workspace_bytes(int64_t N, int32_t h, int32_t w, in
 int t2i_bytescale_nearest(const float* x, int64_t N, int32_t h, int32_t w, int32_t C, int32_t size, uint8_t* y, void* ws,
                           size_t ws_bytes, t2i_stream_t stream);
 
+/* ---- load-size image stores: reference preprocess/utils.py transform (colorize, custom_crop, imresize 'bicubic') --------- */
+/* Pillow's precompute_coeffs + normalize_coeffs_8bpc (libImaging/Resample.c) formed on the device in fp64, every operation
+ * rounded on its own, in the order of evaluation/resize.py: for each of N axes, axis i resizing in_sizes[i] -> out_size,
+ * bounds int32 [N, out_size, 2] = (first input index, tap count) and coeffs int32 [N, out_size, kmax] = the 22-bit fixed-point
+ * weights, zero beyond the tap count.  in_sizes is a DEVICE int32 array.  An axis needs 2 * ceil(support * max(in / out, 1)) + 1
+ * taps (support 1 for T2I_FILTER_BILINEAR, 2 for T2I_FILTER_BICUBIC); an axis that needs more than kmax, or whose size is
+ * outside 1 .. T2I_PREPROCESS_MAX_SIDE, gets empty rows (count 0, weights 0).  out_size <= T2I_PREPROCESS_MAX_OUT. */
+#define T2I_PREPROCESS_MAX_SIDE 16384 /* largest stored height / width of a source image */
+#define T2I_PREPROCESS_MAX_OUT 2048   /* largest output side S */
+enum { T2I_FILTER_BILINEAR = 0, T2I_FILTER_BICUBIC = 1 };
+int t2i_pillow_tables(int32_t filter, const int32_t* in_sizes, int64_t N, int32_t out_size, int32_t* bounds, int32_t* coeffs,
+                      int32_t kmax, t2i_stream_t stream);
+
+/* One image of a ragged batch: uint8 [height, width, channels] stored at packed + offset, rows [y1, y2) and columns [x1, x2)
+ * of it taken.  channels 1 (grey: read for all three output channels), 3, or 4 (the fourth is never read). */
+typedef struct t2i_image_desc {
+  int64_t offset;
+  int32_t height, width, channels;
+  int32_t y1, y2, x1, x2;
+  int32_t reserved;
+} t2i_image_desc;
+
+/* scipy.misc.imresize(float image, [S, S], 'bicubic') of N cropped images, bit for bit, into y uint8 [N, S, S, 3].  Per image:
+ * cmin, cmax = min, max over the crop (the channels that are read); scipy's bytescale as a 256-entry table in fp64,
+ *   lut[u] = (uint8) trunc(clip((u - cmin) * (255.0 / cscale), 0, 255) + 0.5),  cscale = cmax - cmin, or 1 when that is 0
+ * (a constant image comes out black); then Pillow's 8-bit BICUBIC resize of lut[pixel] with the tables above for
+ * (crop width -> S) and (crop height -> S): horizontal pass into a uint8 intermediate, vertical pass, each
+ * clip8(2^21 + sum).  No atomics: results are bitwise identical from call to call.
+ * packed is device memory of packed_bytes bytes.  desc is a HOST array of N descriptors: the call checks every one, copies them
+ * to the device on `stream`, enqueues its kernels behind the copy and then waits for the copy alone, so desc may be changed or
+ * freed as soon as the call returns while the kernels may still be running.  (It is therefore the one entry point that waits on
+ * the stream's earlier work, and it cannot be captured into a graph.)
+ * The uint8 intermediate holds exactly the batch's rows: the workspace query takes total_rows, the sum of the crops' heights
+ * y2 - y1, and max_side, the largest crop height or width.  The filter tables are NOT ragged: every image's two tables have
+ * the tap count of max_side, N * 2 * S * taps * 4 bytes in all, so one extreme downscale in a batch of many images is paid for
+ * by all of them (batch such images apart).  Limits: stored sides
+ * <= T2I_PREPROCESS_MAX_SIDE, S <= T2I_PREPROCESS_MAX_OUT, N <= 2^24, N * S < 2^31, total_rows < 2^31.
+ * Bad arguments (a NULL pointer, N or S <= 0 or above the limits, channels outside {1, 3, 4}, a crop that
+ * is empty or leaves its image, an image that ends past packed_bytes) return T2I_ERR_INVALID and a workspace that is NULL,
+ * misaligned (16 bytes) or smaller than the query T2I_ERR_WORKSPACE, before anything is launched.  Added within ABI v13: no
+ * existing argument list changed. */
+size_t t2i_preprocess_images_workspace_bytes(int64_t N, int64_t total_rows, int32_t max_side, int32_t S);
+int t2i_preprocess_images(const uint8_t* packed, size_t packed_bytes, const t2i_image_desc* desc, int64_t N, int32_t S, uint8_t* y,
+                          void* ws, size_t ws_bytes, t2i_stream_t stream);
+
 /* ---- InceptionV3 fine-tuning (reference models/inception/trainer.py) -------------------------------------------------- */
 /* AvgPool_1a_8x8 + Dropout_1b of slim inception_v3(is_training=True): x fp32 [B, HW, D] (the Mixed_7c output, HW = 64) ->
  * pre[b, d] = (sum_p x[b, p, d]) / HW (fp32, taps in order: t2i_pool2d's AVG), mask[b, d] = floor(keep + U) in {0, 1} and

@@ -26,6 +26,12 @@ class ConvOpts(ctypes.Structure):
                 ('xform_kept', ctypes.c_int32), ('in_dtype', ctypes.c_int32), ('out_dtype', ctypes.c_int32), ('xform_valid_rows', ctypes.c_int32), ('xform_plane_rows', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
+class ImageDesc(ctypes.Structure):
+    """t2i_image_desc: one image of t2i_preprocess_images' ragged batch"""
+    _fields_ = [('offset', ctypes.c_int64)] + [(n, ctypes.c_int32) for n in
+                                               ('height', 'width', 'channels', 'y1', 'y2', 'x1', 'x2', 'reserved')]
+
+
 XFORM_NONE, XFORM_KEEP, XFORM_HAVE = 0, 1, 2
 DT_F32, DT_BF16 = 0, 1           # t2i_dtype: element type of the activation tensors of a call
 
@@ -116,6 +122,9 @@ SIGNATURES = {
     't2i_cosine_distance': (ctypes.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p]),
     't2i_bytescale_nearest_workspace_bytes': (_sz, [_i64, _i32, _i32, _i32]),
     't2i_bytescale_nearest': (ctypes.c_int, [_p, _i64, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),
+    't2i_pillow_tables': (ctypes.c_int, [_i32, _p, _i64, _i32, _p, _p, _i32, _p]),
+    't2i_preprocess_images_workspace_bytes': (_sz, [_i64, _i64, _i32, _i32]),
+    't2i_preprocess_images': (ctypes.c_int, [_p, _sz, _p, _i64, _i32, _p, _p, _sz, _p]),
     't2i_pool_dropout':(ctypes.c_int, [_p, _i32, _i32, _i32, _f, ctypes.c_uint64, ctypes.c_uint64, _p, _p, _p, _p]),
     't2i_softmax_ce_head_workspace_bytes': (_sz, [_i32, _i32]),
     't2i_softmax_ce_head': (ctypes.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _sz, _p]),

@@ -1,7 +1,8 @@
 // t2i_capi.hip — the extern "C" surface of libt2i_hip.so (declared in include/t2i_hip.h): argument validation, GEMM
 // planning (tile shape, split-K, stride phases, vector-path eligibility) and launches.  No allocation, no
 // synchronisation: every entry point only enqueues kernels on the caller's stream, so a whole training step can be
-// captured into a hipGraph.
+// captured into a hipGraph.  (One exception, outside any training step: t2i_preprocess_images copies its host descriptors to the
+// device and waits for that copy.)
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <initializer_list>
@@ -69,6 +70,11 @@ hipError_t gram_accumulate_launch(const float*, int, int, const float*, double*,
 hipError_t cosine_distance_launch(const float*, int64_t, const float*, int64_t, int64_t, int, double*, hipStream_t);
 size_t bytescale_nearest_ws(int64_t N, int64_t per);
 hipError_t bytescale_nearest_launch(const float*, int64_t, int, int, int, int, uint8_t*, void*, hipStream_t);
+// implemented in t2i_preprocess.hip
+int pillow_table_taps(int filter, int in_size, int out_size);
+hipError_t pillow_tables_launch(int, const int32_t*, int64_t, int, int32_t*, int32_t*, int, hipStream_t);
+size_t preprocess_images_ws(int64_t N, int64_t total_rows, int max_side, int S);
+hipError_t preprocess_images_launch(const uint8_t*, const t2i_image_desc*, int64_t, int64_t, int, int, uint8_t*, void*, hipStream_t);
 // implemented in t2i_incep_train.hip
 size_t softmax_ce_head_ws(int B, int C);
 hipError_t pool_dropout_launch(const float*, int, int, int, float, unsigned long long, unsigned long long, float*, float*, float*,
@@ -1608,6 +1614,67 @@ int t2i_bytescale_nearest(const float* x, int64_t N, int32_t h, int32_t w, int32
     return T2I_ERR_WORKSPACE;
   }
   return check(bytescale_nearest_launch(x, N, h, w, C, size, y, ws, (hipStream_t)stream), "t2i_bytescale_nearest");
+}
+
+int t2i_pillow_tables(int32_t filter, const int32_t* in_sizes, int64_t N, int32_t out_size, int32_t* bounds, int32_t* coeffs,
+                      int32_t kmax, t2i_stream_t stream) {
+  if (!in_sizes || !bounds || !coeffs || (filter != T2I_FILTER_BILINEAR && filter != T2I_FILTER_BICUBIC) || N <= 0 ||
+      out_size <= 0 || out_size > T2I_PREPROCESS_MAX_OUT || kmax <= 0 || N > ((int64_t)1 << 31) / out_size ||
+      kmax > pillow_table_taps(filter, T2I_PREPROCESS_MAX_SIDE, 1)) {
+    set_error("t2i_pillow_tables: bad argument (filter=%d N=%lld out_size=%d kmax=%d, in_sizes %s, bounds %s, coeffs %s)", filter,
+              (long long)N, out_size, kmax, in_sizes ? "given" : "NULL", bounds ? "given" : "NULL", coeffs ? "given" : "NULL");
+    return T2I_ERR_INVALID;
+  }
+  return check(pillow_tables_launch(filter, in_sizes, N, out_size, bounds, coeffs, kmax, (hipStream_t)stream), "t2i_pillow_tables");
+}
+
+// N * S (the vertical pass) and total_rows (the horizontal pass) are grid extents and int32 row indices
+static bool preprocess_shape_ok(int64_t N, int64_t total_rows, int32_t max_side, int32_t S) {
+  return N > 0 && N <= ((int64_t)1 << 24) && S > 0 && S <= T2I_PREPROCESS_MAX_OUT && N <= INT32_MAX / S && total_rows > 0 &&
+         total_rows <= INT32_MAX && max_side > 0 && max_side <= T2I_PREPROCESS_MAX_SIDE;
+}
+
+size_t t2i_preprocess_images_workspace_bytes(int64_t N, int64_t total_rows, int32_t max_side, int32_t S) {
+  return preprocess_shape_ok(N, total_rows, max_side, S) ? preprocess_images_ws(N, total_rows, max_side, S) : 0;
+}
+
+int t2i_preprocess_images(const uint8_t* packed, size_t packed_bytes, const t2i_image_desc* desc, int64_t N, int32_t S, uint8_t* y,
+                          void* ws, size_t ws_bytes, t2i_stream_t stream) {
+  if (!packed || !desc || !y || !preprocess_shape_ok(N, 1, 1, S)) {
+    set_error("t2i_preprocess_images: bad argument (N=%lld S=%d, packed %s, desc %s, y %s; N in 1..2^24, S in 1..%d, N * S < 2^31)",
+              (long long)N, S, packed ? "given" : "NULL", desc ? "given" : "NULL", y ? "given" : "NULL", T2I_PREPROCESS_MAX_OUT);
+    return T2I_ERR_INVALID;
+  }
+  int max_side = 0;
+  int64_t total_rows = 0;
+  for (int64_t n = 0; n < N; ++n) {
+    const t2i_image_desc& d = desc[n];
+    const char* why = nullptr;
+    if (d.channels != 1 && d.channels != 3 && d.channels != 4) why = "channels must be 1, 3 or 4";
+    else if (d.height <= 0 || d.width <= 0 || d.height > T2I_PREPROCESS_MAX_SIDE || d.width > T2I_PREPROCESS_MAX_SIDE) why = "side outside 1..T2I_PREPROCESS_MAX_SIDE";
+    else if (d.y1 < 0 || d.y1 >= d.y2 || d.y2 > d.height || d.x1 < 0 || d.x1 >= d.x2 || d.x2 > d.width) why = "crop empty or outside its image";
+    else if (d.offset < 0 || (uint64_t)d.offset > packed_bytes ||
+             (uint64_t)d.height * d.width * d.channels > packed_bytes - (uint64_t)d.offset) why = "image ends past the packed buffer";
+    if (why) {
+      set_error("t2i_preprocess_images: image %lld: %s (offset=%lld %dx%dx%d, rows %d:%d, columns %d:%d, buffer of %zu bytes)",
+                (long long)n, why, (long long)d.offset, d.height, d.width, d.channels, d.y1, d.y2, d.x1, d.x2, packed_bytes);
+      return T2I_ERR_INVALID;
+    }
+    total_rows += d.y2 - d.y1;
+    if (d.y2 - d.y1 > max_side) max_side = d.y2 - d.y1;
+    if (d.x2 - d.x1 > max_side) max_side = d.x2 - d.x1;
+  }
+  if (total_rows > INT32_MAX) {
+    set_error("t2i_preprocess_images: the crops of the batch have %lld rows in all, at most 2^31 - 1 per call: split the batch",
+              (long long)total_rows);
+    return T2I_ERR_INVALID;
+  }
+  const size_t need = preprocess_images_ws(N, total_rows, max_side, S);
+  if (!ws || ws_bytes < need || !aligned16(ws)) {
+    set_error("t2i_preprocess_images: workspace too small or misaligned (%zu bytes, need %zu)", ws_bytes, need);
+    return T2I_ERR_WORKSPACE;
+  }
+  return check(preprocess_images_launch(packed, desc, N, total_rows, max_side, S, y, ws, (hipStream_t)stream), "t2i_preprocess_images");
 }
 
 int t2i_pool_dropout(const float* x, int32_t B, int32_t HW, int32_t D, float keep, uint64_t seed, uint64_t step, float* pre,

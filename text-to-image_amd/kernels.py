@@ -12,7 +12,7 @@ import os
 
 import torch
 
-from ._lib import DT_BF16, DT_F32, XFORM_HAVE, XFORM_KEEP, ConvDesc, ConvOpts, check, lib
+from ._lib import DT_BF16, DT_F32, XFORM_HAVE, XFORM_KEEP, ConvDesc, ConvOpts, ImageDesc, check, lib
 
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH = 0, 1, 2, 3
 
@@ -1217,6 +1217,59 @@ def resample_u8(src, Ho, Wo, filter='bicubic', rows=None, out=None):
         wsp, wsn = _ws_args(src, int(lib.t2i_resample_bilinear_workspace_bytes(B, Hi, Wo)))
         check(lib.t2i_resample_bilinear(_ptr(src), 0, N, Hi, Wi, _ptr(r), B, Ho, Wo, _ptr(xb), _ptr(xk), xk.shape[1], _ptr(yb),
                                         _ptr(yk), yk.shape[1], _ptr(y), 1, wsp, wsn, _stream()), 't2i_resample_bilinear')
+    return y
+
+
+def pillow_tables(in_sizes, out_size, filter='bicubic', kmax=None):
+    """Pillow's resize tables formed on the device in fp64 (t2i_pillow_tables): in_sizes int32 [N] (device), one axis each,
+    resized to out_size -> (bounds int32 [N,out_size,2], coeffs int32 [N,out_size,kmax]), equal to evaluation/resize.py's
+    bicubic_tables / bilinear_tables (coeffs zero beyond an axis' own tap count).  kmax None: what the largest axis needs."""
+    if filter not in ('bicubic', 'bilinear'):
+        raise ValueError("pillow_tables: filter must be 'bicubic' or 'bilinear', got %r" % (filter,))
+    if in_sizes.dtype != torch.int32 or in_sizes.dim() != 1 or in_sizes.numel() == 0 or not in_sizes.is_contiguous():
+        raise ValueError('pillow_tables expects a contiguous int32 [N] tensor of axis sizes, got %s %s' % (in_sizes.dtype, tuple(in_sizes.shape)))
+    N, out_size = in_sizes.numel(), int(out_size)
+    if out_size <= 0:
+        raise ValueError('pillow_tables: out_size must be positive, got %d' % out_size)
+    if kmax is None:
+        from .evaluation import resize
+        big = max(int(in_sizes.max()), 1)
+        kmax = {'bicubic': resize.bicubic_tables, 'bilinear': resize.bilinear_tables}[filter](big, out_size)[1].shape[1]
+    bounds = torch.empty((N, out_size, 2), dtype=torch.int32, device=in_sizes.device)
+    coeffs = torch.empty((N, out_size, int(kmax)), dtype=torch.int32, device=in_sizes.device)
+    if _live(in_sizes):
+        check(lib.t2i_pillow_tables(int(filter == 'bicubic'), _ptr(in_sizes), N, out_size, _ptr(bounds), _ptr(coeffs), int(kmax),
+                                    _stream()), 't2i_pillow_tables')
+    return bounds, coeffs
+
+
+def image_descs(rows):
+    """rows: N x (offset, height, width, channels, y1, y2, x1, x2) integers -> the ctypes array t2i_preprocess_images reads."""
+    rows = [tuple(int(v) for v in r) for r in rows]
+    if not rows or any(len(r) != 8 for r in rows):
+        raise ValueError('image_descs expects N >= 1 rows of (offset, height, width, channels, y1, y2, x1, x2)')
+    return (ImageDesc * len(rows))(*[ImageDesc(*r, 0) for r in rows])
+
+
+def preprocess_images(packed, descs, size):
+    """The reference's load-size transform of a ragged batch in one call (t2i_preprocess_images): per image colorize and crop by
+    addressing, scipy's bytescale of the crop (its own min -> 0, max -> 255) and Pillow's 8-bit BICUBIC resize to size x size, bit
+    for bit with preprocess/utils.py transform.  packed: uint8 [bytes] (device), the decoded images back to back; descs: N rows
+    of (offset, height, width, channels, y1, y2, x1, x2) — image n is uint8 [height, width, channels] at packed[offset:], channels
+    1, 3 or 4, and rows y1:y2, columns x1:x2 of it are taken.  -> uint8 [N,size,size,3]."""
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+        raise ValueError('preprocess_images expects a contiguous uint8 [bytes] buffer, got %s %s' % (packed.dtype, tuple(packed.shape)))
+    d = descs if isinstance(descs, ctypes.Array) else image_descs(descs)
+    N, size = len(d), int(size)
+    if size <= 0:
+        raise ValueError('preprocess_images: size must be positive, got %d' % size)
+    y = torch.empty((N, size, size, 3), dtype=torch.uint8, device=packed.device)
+    if _live(packed):
+        rows = max(sum(r.y2 - r.y1 for r in d), 1)
+        side = max(max(max(r.y2 - r.y1, r.x2 - r.x1) for r in d), 1)
+        wsp, wsn = _ws_args(packed, int(lib.t2i_preprocess_images_workspace_bytes(N, rows, side, size)))
+        check(lib.t2i_preprocess_images(_ptr(packed), packed.numel(), ctypes.cast(d, ctypes.c_void_p), N, size, _ptr(y), wsp, wsn,
+                                        _stream()), 't2i_preprocess_images')
     return y
 
 
