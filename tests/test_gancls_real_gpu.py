@@ -319,7 +319,7 @@ def test_eval_inception_equals_scoring_the_unfused_images(eval_cfg):
     assert np.isfinite(r['mean']) and np.isfinite(r['std']) and r['mean'] >= 1.0 - 1e-9 and sorted(r['indices']) == list(range(16))
     ev = _evaluator(eval_cfg, 3, fused=False)             # the same draws, the generator on the unfused norm path
     net = ev._inception()
-    ev._restore_generator()
+    ev.restore()
     samples = ev._generate(is_training=False)
     assert tuple(samples.shape) == (16, 64, 64, 3)
     m, s, idx = inception_score.get_inception_score(samples, net, 4, 10)
@@ -338,12 +338,12 @@ def test_eval_fid_runs_the_generator_in_training_mode(eval_cfg):
     for n in ('g_net/BatchNorm/moving_mean', 'g_net/BatchNorm_9/moving_variance'):
         assert np.array_equal(ev.model.store.vars[n].detach().cpu().numpy(), ck[n]), n           # no update op ran
     ev2 = _evaluator(eval_cfg, 4)
-    ev2._restore_generator()
+    ev2.restore()
     eval_mode = ev2._generate(is_training=False)           # the same draws through the moving statistics
     assert tuple(eval_mode.shape) == tuple(f['samples'].shape) == (16, 64, 64, 3)
     assert float((eval_mode - f['samples']).abs().max()) > 1e-3
     ev3 = _evaluator(eval_cfg, 4)
-    ev3._restore_generator()
+    ev3.restore()
     assert torch.equal(ev3._generate(is_training=True), f['samples'])
 
 

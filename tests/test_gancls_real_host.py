@@ -106,10 +106,10 @@ def test_run_mode_errors_before_any_device_work(tmp_path):
 
 def test_the_three_modules_exist_with_the_reference_class_names():
     import t2i_amd  # noqa: F401
+    from t2i_amd.evaluation.evaluator import GeneratorEval
     from t2i_amd.models.gancls.eval_gancls import GanClsEval
     from t2i_amd.models.gancls.visualize_gancls import SPECIAL_POSITIONS, GanClsVisualizer
-    from t2i_amd.models.wgancls.eval_wgan import WGanClsEval
-    assert issubclass(GanClsEval, WGanClsEval) and all(hasattr(GanClsEval, f) for f in ('evaluate_inception', 'evaluate_fid', 'evaluate_imd'))
+    assert issubclass(GanClsEval, GeneratorEval) and all(hasattr(GanClsEval, f) for f in ('evaluate_inception', 'evaluate_fid', 'evaluate_imd'))
     assert tuple(SPECIAL_POSITIONS) == (1126, 908, 398) and hasattr(GanClsVisualizer, 'visualize')
 
 

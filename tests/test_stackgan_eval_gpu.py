@@ -300,6 +300,30 @@ def test_stage_i_eval_is_fid_imd_match_oracle(trained, eval_setup):
     _check_imd(r, arrays)
 
 
+def test_stored_and_streamed_modes_see_the_same_images(trained, eval_setup):
+    """The one evaluator core, stored and streamed: the same draws, the same kernels, the same order, so the generated images and
+    the global np.random state behind them are equal to the bit (FID's path: training-mode batch norm, no shuffle)."""
+    from t2i_amd.models.stackgan.stageI.eval_stagei import StageIEval
+    from t2i_amd.models.stackgan.stageI.model import ConditionalGan
+    from t2i_amd.models.wgancls.run import load_dataset
+    from t2i_amd.utils.config import config_from_yaml
+
+    class Streamed(StageIEval):
+        stored = False
+    assert StageIEval.stored
+    runs = []
+    for cls in (StageIEval, Streamed):
+        np.random.seed(6); random.seed(6); torch.manual_seed(6)
+        cfg = config_from_yaml(eval_setup[1]['stageI'])
+        mdl = ConditionalGan(cfg, build_model=False)
+        f = cls(None, mdl, load_dataset(cfg, mdl.device), cfg, incep_batch_size=2).evaluate_fid(keep_samples=True)
+        runs.append((f['samples'], np.random.get_state()))
+    (stored, state_a), (streamed, state_b) = runs
+    assert torch.is_tensor(stored) and stored.is_cuda and isinstance(streamed, np.ndarray)      # the device store / the host copies
+    assert streamed.shape == (12, 64, 64, 3) and np.array_equal(stored.cpu().numpy(), streamed)
+    assert state_a[0] == state_b[0] and np.array_equal(state_a[1], state_b[1]) and state_a[2:] == state_b[2:]
+
+
 def test_compute_imd_on_image_folders(eval_setup):
     from t2i_amd.evaluation import imd
     from t2i_amd.evaluation.fid import load_inception_data

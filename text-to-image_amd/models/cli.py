@@ -1,0 +1,59 @@
+"""What the entry points of GAN-CLS and the two StackGAN stages share: the argument parser, the mode rules (every argument error is
+raised before a directory is created or anything touches the GPU), the output directories and the evaluation switch."""
+import argparse
+import os
+
+EVAL_MODES = ('is', 'fid', 'imd')
+
+
+def make_parser(default_cfg):
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--cfg', default=default_cfg, help='Relative path to the config of the model')
+    mode = ap.add_mutually_exclusive_group()
+    mode.add_argument('--train', action='store_true', help='train even if the yml says TRAIN.FLAG: False')
+    mode.add_argument('--eval', choices=EVAL_MODES, default=None, help='Inception score, FID or Inception match distance of the '
+                      'latest checkpoint (needs the pickled dataset and an Inception checkpoint in EVAL.INCEP_CHECKPOINT_DIR)')
+    mode.add_argument('--visualize', action='store_true', help='run the caption visualiser on the latest checkpoint (needs the '
+                      'pickled dataset)')
+    ap.add_argument('--incep-batch', type=int, default=None, help='--eval: Inception batch size (default EVAL.INCEP_BATCH_SIZE)')
+    ap.add_argument('--interp', type=int, default=0, help='--visualize: rounds of interpolation / captioned sheets (default 0)')
+    ap.add_argument('--synthetic', action='store_true', help='--train: synthetic on-device dataset instead of cfg.DATASET_DIR')
+    ap.add_argument('--steps', type=int, default=None, help='--train: stop after this many updates')
+    ap.add_argument('--batch', type=int, default=None, help='override TRAIN.BATCH_SIZE')
+    ap.add_argument('--graphs', type=int, default=1, help='1: replay the iteration from hipGraphs once it has run eagerly (default)')
+    return ap
+
+
+def check_mode(args, cfg, visualiser):
+    """The mode errors, raised before any device work and before a directory is created."""
+    if args.incep_batch is not None and (not args.eval or args.incep_batch <= 0):
+        raise ValueError('--incep-batch takes a positive batch size and needs --eval (got %r)' % args.incep_batch)
+    if args.steps is not None and args.steps <= 0:
+        raise ValueError('--steps takes a positive number of updates (got %r)' % args.steps)
+    if args.interp < 0 or (args.interp and not args.visualize):
+        raise ValueError('--interp takes a non-negative number of rounds and needs --visualize (got %r)' % args.interp)
+    if args.eval:
+        if args.synthetic:
+            raise ValueError('--eval needs the pickled dataset (embeddings are drawn from its test split); the --synthetic data '
+                             'set has none')
+        return
+    if cfg.EVAL.FLAG:
+        raise NotImplementedError('EVAL.FLAG: pass --eval is, --eval fid or --eval imd to run the evaluation')
+    if args.visualize:
+        if args.synthetic:
+            raise ValueError('--visualize needs the pickled dataset (the neighbour search reads its uint8 image store); the '
+                             '--synthetic data set has none')
+        return
+    if not (cfg.TRAIN.FLAG or args.train):
+        raise NotImplementedError('TRAIN.FLAG is False: the reference would start its caption visualiser (%s); pass --visualize '
+                                  'for it, --train / TRAIN.FLAG: True to train or --eval to evaluate' % visualiser)
+
+
+def make_dirs(cfg):
+    for d in (cfg.CHECKPOINT_DIR, cfg.SAMPLE_DIR, cfg.LOGS_DIR):
+        if not os.path.exists(d):
+            os.makedirs(d)
+
+
+def run_eval(ev, mode):
+    return {'is': ev.evaluate_inception, 'fid': ev.evaluate_fid, 'imd': ev.evaluate_imd}[mode]()

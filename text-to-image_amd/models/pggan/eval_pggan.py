@@ -8,7 +8,8 @@ of `--batch` (EVAL.SIZE // batch batches; 50 000 // 64 in the reference's config
 np.random stream: z ~ N(0, 1) [batch, 128], then `dataset.test.next_batch(batch, 4, embeddings=True)` (the means of four caption
 embeddings), the generator with conditioning noise on (the reference's `gen_op`), clip to [-1, 1], the resize to 299 x 299 by
 t2i_resample_bilinear straight from the fp32 images (denormalize_images + prep_incep_img, bit for bit), InceptionV3 and a float32
-softmax.  Nothing is kept between batches: 50 000 images of 256 x 256 would take 39 GB in fp32.
+softmax.  Nothing is kept between batches: evaluation/evaluator.py's streamed evaluator, IS and FID both in chunks of the Inception
+batch (default: `--batch`).
 
 - evaluate_inception: the predictions in generation order, with NO shuffle, then get_inception_from_predictions(preds, 10), as
   the reference's evaluator does.
@@ -21,16 +22,14 @@ import argparse
 import os
 import sys
 
-import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))))
 
 import t2i_amd  # noqa: E402,F401
 from t2i_amd import kernels as K  # noqa: E402
-from t2i_amd.evaluation import fid, inception_score  # noqa: E402
-from t2i_amd.models.inception.model import IMAGE_SIZE, load_inception_inference  # noqa: E402
-from t2i_amd.utils.saver import Saver, load  # noqa: E402
+from t2i_amd.evaluation.evaluator import GeneratorEval  # noqa: E402
+from t2i_amd.utils.saver import restore_scopes  # noqa: E402
 
 
 def stage_model(cfg, stage, batch_size, dataset, device, **widths):
@@ -48,9 +47,7 @@ def stage_model(cfg, stage, batch_size, dataset, device, **widths):
 
 
 def restore_generator(m):
-    could_load, _ = load(Saver(m.store, var_list=['g_net']), None, m.check_dir_read)
-    if not could_load:
-        raise RuntimeError('Could not load stage %d' % m.stage)
+    restore_scopes(m.store, [('g_net', m.check_dir_read)], error=lambda scope: RuntimeError('Could not load stage %d' % m.stage), verbose=False)
 
 
 def generate(m, z, cond, cond_noise=True):
@@ -61,90 +58,23 @@ def generate(m, z, cond, cond_noise=True):
         return torch.clamp(img.float(), -1.0, 1.0).contiguous()
 
 
-class PGGANEval(object):
-    def __init__(self, sess, model, dataset, cfg, incep_batch_size=None):
-        self.sess = sess                   # unused: there is no TF session
-        self.model = model
-        self.dataset = dataset
-        self.cfg = cfg
-        self.bs = model.batch_size
-        self.incep_batch_size = incep_batch_size or self.bs      # eval_pggan.py: incep_batch_size = batch_size
+class PGGANEval(GeneratorEval):
+    stored = False
+    keep_preds = True
+    size_error = 'EVAL.SIZE %d is smaller than the batch %d'
+    announce = {}
 
-    def _inception(self):
-        return load_inception_inference(self.cfg.EVAL.NUM_CLASSES, self.cfg.EVAL.INCEP_CHECKPOINT_DIR, self.model.device)
+    def batch_size(self):
+        return self.model.batch_size
 
-    def _n_batches(self):
-        n = self.cfg.EVAL.SIZE // self.bs
-        if n == 0:
-            raise ValueError('EVAL.SIZE %d is smaller than the batch %d' % (self.cfg.EVAL.SIZE, self.bs))
-        return n
+    def default_incep_batch_size(self):
+        return self.bs                     # eval_pggan.py: incep_batch_size = batch_size
 
-    def _stream(self, keep_samples):
-        """Yields each clipped generated batch (device float32 [bs, S, S, 3]); keeps a host copy when asked."""
-        m, dev = self.model, self.model.device
-        n_batches = self._n_batches()
-        self._kept = []
-        for i in range(n_batches):
-            print('\rGenerating batch %d/%d' % (i + 1, n_batches), end='', flush=True)
-            sample_z = np.random.normal(0, 1, size=(self.bs, m.z_dim))
-            _, _, embed, _, _ = self.dataset.test.next_batch(self.bs, 4, embeddings=True)
-            z = torch.as_tensor(sample_z, dtype=torch.float32).to(dev)
-            cond = embed if torch.is_tensor(embed) else torch.as_tensor(np.asarray(embed), dtype=torch.float32)
-            img = generate(m, z, cond.to(device=dev, dtype=torch.float32).reshape(self.bs, m.embed_dim))
-            if keep_samples:
-                self._kept.append(img.cpu().numpy())
-            yield img
-        print()
-
-    def _chunks(self, img):
-        c = self.incep_batch_size
-        for s in range(0, img.shape[0], c):
-            yield K.resample_bilinear(img[s:s + c], IMAGE_SIZE, IMAGE_SIZE)
-
-    def _samples(self, keep_samples):
-        return dict(samples=np.concatenate(self._kept)) if keep_samples else {}
-
-    def evaluate_inception(self, keep_samples=False):
-        """-> dict(mean, std, preds: float32 [n, classes] in generation order) (+ samples, host, with keep_samples)."""
-        net = self._inception()
+    def restore(self):
         restore_generator(self.model)
-        preds = []
-        for img in self._stream(keep_samples):
-            for x in self._chunks(img):
-                logits, _ = net(x)
-                preds.append(inception_score.softmax32(logits.cpu().numpy()))
-        print('Computing inception score...')
-        preds = np.concatenate(preds, 0)
-        mean, std = inception_score.get_inception_from_predictions(preds, 10)
-        print('Inception Score | mean:', '%.2f' % mean, 'std:', '%.2f' % std)
-        return dict(mean=mean, std=std, preds=preds, **self._samples(keep_samples))
 
-    def evaluate_fid(self, keep_samples=False):
-        """-> dict(fid, mu_gen, sigma_gen, mu_real, sigma_real) (+ samples with keep_samples)."""
-        net = self._inception()
-        path = self.cfg.EVAL.ACT_STAT_PATH
-        if not os.path.exists(path):
-            print('Computing activation statistics for real x')
-            fid.compute_and_save_activation_statistics(self.cfg.EVAL.R_IMG_PATH, net, self.incep_batch_size, path,
-                                                       self.model.device, verbose=True)
-        print('Loading activation statistics for the real x')
-        mu_real, sigma_real = fid.load_activation_statistics(path)
-        restore_generator(self.model)
-        stats = fid.ActivationStatistics(device=self.model.device)
-        for img in self._stream(keep_samples):
-            for x in self._chunks(img):
-                _, pre = net(x)
-                stats.add(pre.reshape(x.shape[0], -1))
-        mu_gen, sigma_gen = stats.finalize()
-        print('calculate FID:', end=' ', flush=True)
-        try:
-            value = fid.calculate_frechet_distance(mu_gen, sigma_gen, mu_real, sigma_real)
-        except Exception as e:          # the other evaluators' fallback
-            print(e)
-            value = 500
-        print(value)
-        return dict(fid=value, mu_gen=mu_gen, sigma_gen=sigma_gen, mu_real=mu_real, sigma_real=sigma_real,
-                    **self._samples(keep_samples))
+    def generate_batch(self, z, cond, is_training):
+        return generate(self.model, z, cond)          # no batch norm: no mode
 
 
 def load_stage_dataset(cfg, stage, device):

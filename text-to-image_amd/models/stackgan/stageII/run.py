@@ -14,7 +14,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))))
 
 import t2i_amd  # noqa: E402,F401
-from t2i_amd.models.stackgan.stageI.run import check_mode, make_dirs, make_parser, run_eval  # noqa: E402
+from t2i_amd.models.cli import check_mode, make_dirs, make_parser, run_eval  # noqa: E402
 from t2i_amd.utils.config import config_from_yaml  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))

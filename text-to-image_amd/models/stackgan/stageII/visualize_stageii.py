@@ -13,13 +13,10 @@ The special positions follow DATASET_NAME (the reference always uses its birds l
 the reference, is built: the 304 x 304 train store searched with 256 x 256 crops by one t2i_nearest_images launch (8 queries: the
 crop table and the workspace hold 8 x N_train entries each, a few hundred KB for either data set)."""
 import numpy as np
-import torch
 
-from .... import kernels as K
-from ....scope import trainable_variables
 from ....utils import visualize as V
-from ....utils.saver import Saver, load
 from ..stageI.visualize_stagei import StageIVisualizer
+from .eval_stageii import restore_chain
 
 STAGES_TEXT = 'Stage I and Stage II'
 
@@ -37,19 +34,8 @@ class StageIIVisualizer(StageIVisualizer):
         return self.model.generator(self._stage_i_images(z, cond), cond, reuse=True, is_training=False, cond_noise=cond_noise)[0]
 
     def _restore_generator(self):
-        m, s1 = self.model, self.model.stagei
-        if not trainable_variables('stageII_g_net'):
-            with K.dry_run(), torch.no_grad():
-                z = torch.empty(m.batch_size, s1.z_dim, device=m.device)
-                phi = torch.empty(m.batch_size, s1.embed_dim, device=m.device)
-                img64, _, _ = s1.generator(z, phi, reuse=bool(trainable_variables('g_net')), is_training=False)
-                m.generator(img64, phi, reuse=False, is_training=False)
-        for scope, directory, what in (('g_net', s1.cfg.CHECKPOINT_DIR, 'stage I'), ('stageII_g_net', self.config.CHECKPOINT_DIR, 'stage II')):
-            could_load, _ = load(Saver(m.store, var_list=[scope]), None, directory)
-            if not could_load:
-                print(' [!] Load failed...')
-                raise LookupError('Could not load any checkpoints for %s' % what)
-            print(' [*] Load SUCCESS')
+        restore_chain(self.model, self.config.CHECKPOINT_DIR, self.model.batch_size,
+                      lambda what: LookupError('Could not load any checkpoints for %s' % what))
 
     def _second_position(self, dataset_pos):
         return np.random.randint(0, self.dataset.test.num_examples)          # visualize_stageiI.py:44

@@ -135,3 +135,30 @@ def load(saver, sess, checkpoint_dir):
             return True, counter
     print(' [*] Failed to find checkpoints')
     return False, 0
+
+
+def restore_scopes(store, pairs, create=None, error=RuntimeError, verbose=True):
+    """Restores each (scope, directory) of `pairs` in order: tf.train.Saver(tf.global_variables(scope)) + load in the reference.
+    When the last scope has no trainable variables yet, `create()` builds the generators once, launch-free (K.dry_run, no gradient).
+    The first directory without a checkpoint ends it: ` [!] Load failed...` and `raise error(scope)` (the caller's exception); a
+    restored one prints ` [*] Load SUCCESS`.  verbose=False drops those two lines (load's own remain)."""
+    if create is not None and not store.trainable_variables(pairs[-1][0]):
+        from .. import kernels as K
+        with K.dry_run(), torch.no_grad():
+            create()
+    for scope, directory in pairs:
+        could_load, _ = load(Saver(store, var_list=[scope]), None, directory)
+        if not could_load:
+            if verbose:
+                print(' [!] Load failed...')
+            raise error(scope)
+        if verbose:
+            print(' [*] Load SUCCESS')
+
+
+def restore_g_net(model, directory, batch, error):
+    """`g_net` of a model whose generator takes (z [batch, z_dim], embedding [batch, embed_dim]), from `directory`."""
+    def create():
+        model.generator(torch.empty(batch, model.z_dim, device=model.device), torch.empty(batch, model.embed_dim, device=model.device),
+                        reuse=False, is_training=False)
+    restore_scopes(model.store, [('g_net', directory)], create, lambda scope: error)
