@@ -319,14 +319,12 @@ __global__ __launch_bounds__(64 * NW) void bgemm_kernel(BgemmParams p) {
 // Work items: phases x tiles_m x tiles_n (9 x coarser than bgemm_kernel's): the caller takes this path only where that still fills the chip.
 //   LAY 0  forward:        A = V[xi] [T][4 Cin] K-inner, B = U[xi] [4 Cin][Cout] N-inner, plane slot = xi
 //   LAY 1  input gradient: A = V[slot] [T][Cout] K-inner, B = U[slot] [Cin][Cout] K-inner, slot = ((2 - r) 3 + (2 - c)) 4 + (3 - phase)
-// XF (LAY 1 only, round 5): the INPUT transform in the A loader too.  The unfused form writes V = B^T d B of the incoming gradient once per output
-// phase (9 x |dy| through the workspace, the largest single stream of this layer class) and reads it back here.  With XF the loader fetches the
-// (up to) four dy pixels a V element is made of — V(r,c) = (d[r][c] - d[1][c]) - (d[r][1] - d[1][1]), with the taps of row / column 1 absent for
-// r = 1 / c = 1 — straight from dy (which stays in L2 / MALL: 1/9 of V's size) and forms the element in registers, in wino2b_input_kernel's order:
-// x - 0 is exact, so the bits are the same.  Padding taps and rows beyond T read zero through the buffer range check, as everywhere here.
+// XF (LAY 1 only): the INPUT transform in the A loader too, so that the V planes (9 x |dy| through the workspace, the largest single stream of
+// this layer class) never exist either: the specialisation bgemm9_kernel<1, true> further down, which walks K-tile outer / positions inner and
+// fetches every dy pixel of a tile's 3 x 3 window once per K-tile.  The primary template below reads V planes.
 template <int LAY, bool XF = false>
 __global__ __launch_bounds__(256, 2) void bgemm9_kernel(Bgemm9Params q) {
-  static_assert(!XF || LAY == 1, "the in-loader input transform exists for the input-gradient form");
+  static_assert(!XF, "the in-loader input transform is the specialisation bgemm9_kernel<1, true> below");
   const BgemmParams& p = q.g;
   using S = BSmem<LAY, 1, 1, 4>;
   constexpr bool B_KIN = S::B_KIN;                          // A is K-inner in both layouts
@@ -370,63 +368,30 @@ __global__ __launch_bounds__(256, 2) void bgemm9_kernel(Bgemm9Params q) {
   __amdgpu_buffer_rsrc_t ra, rb;
   int a_off[A_LD], b_off[B_LD];
   bool a_ok[A_LD], b_ok[B_LD];
-  unsigned a_win[A_LD];           // XF: which of the 3 x 3 window pixels of the row's tile lie inside the dy map (bit r' * 3 + c')
-  int x_tap[4];                   // XF: element offsets of the position's four taps relative to the window origin; x_bit: their window bits, 0 = tap absent
-  unsigned x_bit[4];
   int l_item = -1, l_pos = 8, l_t = 0, l_phs = 0, l_bm = 0, l_bn = 0;
-  if (XF) ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(q.dy), (short)0, (int)p.a_bytes, 0x00020000);
 
   auto next_sub = [&]() __attribute__((always_inline)) {          // the loader moves on to the next (item, position)
     l_t = 0;
-    bool new_item = false;
     if (++l_pos == 9) {
       l_pos = 0;
       ++l_item;
-      new_item = true;
       if (l_item < n_items) coords(run0 + slot + l_item * nslot, l_phs, l_bm, l_bn);
     }
     if (l_item >= n_items) {
 #pragma unroll
-      for (int i = 0; i < A_LD; ++i) { a_ok[i] = false; a_win[i] = 0u; }
+      for (int i = 0; i < A_LD; ++i) a_ok[i] = false;
 #pragma unroll
       for (int i = 0; i < B_LD; ++i) b_ok[i] = false;
       return;
     }
     const int ps = plane_slot(l_pos, l_phs);
-    if (!XF) ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.a + (int64_t)ps * p.sa), (short)0, (int)p.a_bytes, 0x00020000);
+    ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.a + (int64_t)ps * p.sa), (short)0, (int)p.a_bytes, 0x00020000);
     rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.b + (int64_t)ps * p.sb), (short)0, (int)p.b_bytes, 0x00020000);
-    if (XF) {
-      const int r = l_pos / 3, c = l_pos - 3 * r;
-      const int rowpx = q.dWo * p.K;                      // elements per dy row
-      x_tap[0] = r * rowpx + c * p.K;  x_bit[0] = 1u << (r * 3 + c);
-      x_tap[1] = 1 * rowpx + c * p.K;  x_bit[1] = r != 1 ? 1u << (3 + c) : 0u;
-      x_tap[2] = r * rowpx + 1 * p.K;  x_bit[2] = c != 1 ? 1u << (r * 3 + 1) : 0u;
-      x_tap[3] = 1 * rowpx + 1 * p.K;  x_bit[3] = (r != 1 && c != 1) ? 1u << 4 : 0u;
-      if (new_item) {
-        const int ph = l_phs >> 1, pw = l_phs & 1;
 #pragma unroll
-        for (int i = 0; i < A_LD; ++i) {
-          const int m = l_bm + r0 + 32 * i;
-          const int b = m / (q.Th * q.Tw), rem = m - b * (q.Th * q.Tw);
-          const int ty = rem / q.Tw, tx = rem - ty * q.Tw;
-          const int oh0 = 2 * ty + ph - 1, ow0 = 2 * tx + pw - 1;
-          a_off[i] = ((b * q.dHo + oh0) * q.dWo + ow0) * p.K + kq * 4;       // may point before the row / the map: only used under its window bit
-          unsigned w = 0u;
-#pragma unroll
-          for (int rr2 = 0; rr2 < 3; ++rr2)
-#pragma unroll
-            for (int cc2 = 0; cc2 < 3; ++cc2)
-              if ((unsigned)(oh0 + rr2) < (unsigned)q.dHo && (unsigned)(ow0 + cc2) < (unsigned)q.dWo) w |= 1u << (rr2 * 3 + cc2);
-          a_win[i] = m < p.M ? w : 0u;
-        }
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < A_LD; ++i) {
-        const int m = l_bm + r0 + 32 * i;
-        a_ok[i] = m < p.M;
-        a_off[i] = m * p.K + kq * 4;
-      }
+    for (int i = 0; i < A_LD; ++i) {
+      const int m = l_bm + r0 + 32 * i;
+      a_ok[i] = m < p.M;
+      a_off[i] = m * p.K + kq * 4;
     }
 #pragma unroll
     for (int i = 0; i < B_LD; ++i) {
@@ -446,21 +411,8 @@ __global__ __launch_bounds__(256, 2) void bgemm9_kernel(Bgemm9Params q) {
   auto load_into = [&](float4* ar, float4* br) __attribute__((always_inline)) {
     const int k0 = l_t * BK;
     ++l_t;
-    if (XF) {
-      const bool kin = k0 + kq * 4 < p.K;
 #pragma unroll
-      for (int i = 0; i < A_LD; ++i) {
-        const float4 ta = bl4(ra, a_off[i] + x_tap[0] + k0, kin & ((a_win[i] & x_bit[0]) != 0u));
-        const float4 tb = bl4(ra, a_off[i] + x_tap[1] + k0, kin & ((a_win[i] & x_bit[1]) != 0u));
-        const float4 tc = bl4(ra, a_off[i] + x_tap[2] + k0, kin & ((a_win[i] & x_bit[2]) != 0u));
-        const float4 td = bl4(ra, a_off[i] + x_tap[3] + k0, kin & ((a_win[i] & x_bit[3]) != 0u));
-        // (d[r][c] - d[1][c]) - (d[r][1] - d[1][1]): wino2b_input_kernel's tt / V arithmetic; absent taps are zeros
-        ar[i] = make_float4((ta.x - tb.x) - (tc.x - td.x), (ta.y - tb.y) - (tc.y - td.y), (ta.z - tb.z) - (tc.z - td.z), (ta.w - tb.w) - (tc.w - td.w));
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < A_LD; ++i) ar[i] = bl4(ra, a_off[i] + k0, a_ok[i] & (k0 + kq * 4 < p.K));
-    }
+    for (int i = 0; i < A_LD; ++i) ar[i] = bl4(ra, a_off[i] + k0, a_ok[i] & (k0 + kq * 4 < p.K));
 #pragma unroll
     for (int i = 0; i < B_LD; ++i) {
       if (B_KIN) br[i] = bl4(rb, b_off[i] + k0, b_ok[i] & (k0 + kq * 4 < p.K));
@@ -604,6 +556,281 @@ __global__ __launch_bounds__(256, 2) void bgemm9_kernel(Bgemm9Params q) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------------------
+// bgemm9_kernel<1, true>: the input-gradient form with the INPUT transform in the A loader — V never exists either.  A V element is made of
+// up to four pixels of the tile's 3x3 dy window, V(r,c) = (d[r][c] - d[1][c]) - (d[r][1] - d[1][1]) with the taps of row / column 1 absent for
+// r = 1 / c = 1 (wino2b_input_kernel's arithmetic; an absent tap is an exact zero and x - 0 is exact, so the bits are those of the unfused path).
+// Fetching the taps per position costs 25 tap loads for 9 distinct pixels; here every pixel is fetched ONCE PER K-TILE:
+//   loop order   K-tile outer, the nine positions inner, in the stage order 4 1 3 0 5 2 7 6 8: in that order position P needs exactly one
+//                pixel that no earlier stage of the K-tile has seen — pixel P itself — so a stage (position, K-tile) loads one dy pixel
+//                (64 rows x 32 k, whole 128-byte lines) and one U tile, the plain kernel's 1 + 1 operand tiles, and every accumulator still sees
+//                its k in ascending order (acc[P] meets K-tile t at stage 9 t + i): bit-identical to the position-outer loop.
+//   the window   the centre pixel (a tap of every position) stays in 8 registers for the K-tile; pixels 1, 3, 5, 7 (taps of two later stages each)
+//                are parked in LDS in THREAD-PRIVATE slots (the thread that loaded a piece is the one that forms with it: no barrier, no
+//                sharing, consecutive lanes 16 bytes apart); the corner pixels are used by their own stage only.  4 parked float4 x 2 rows per
+//                thread = 32 KB; per K-tile 8 ds_write_b128 + 16 ds_read_b128 per thread on top of the 36 + 72 of the images and fragments.
+//   pipeline     bgemm_kernel's: the loads of stage g + 2 are issued while stage g multiplies, stage g + 1 is formed and stored to LDS in
+//                between, one barrier per stage.  9 stages per K-tile is odd, so the body is two K-tiles (18 stages) with compile-time buffer
+//                parity and accumulator index; the loader moves to the next K-tile / item between stages 6 and 7.
+//   resources    (hipcc --offload-arch=gfx950 -O3 --save-temps) 252 VGPRs of which 144 are the accumulators, 0 AGPRs, scratch 0, no spills,
+//                occupancy 2 waves per SIMD = two workgroups per CU as before; LDS 36,864 B of images + 32,768 B of parked pixels = 69,632 B per
+//                workgroup (two fit a CU's 160 KB).  18 stages: 288 MFMAs, 18 barriers, 72 buffer_load_dwordx4 (was 180 with a load per tap).
+namespace {
+__host__ __device__ constexpr int w9_pos(int i) {     // position of stage i of a K-tile
+  return i == 0 ? 4 : i == 1 ? 1 : i == 2 ? 3 : i == 3 ? 0 : i == 4 ? 5 : i == 5 ? 2 : i == 6 ? 7 : i == 7 ? 6 : 8;
+}
+constexpr int W9_PARK_BYTES = 4 * 2 * 256 * 16;       // pixels 1, 3, 5, 7 x 2 rows x 256 threads x float4
+__device__ __forceinline__ float4 sub4(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
+}  // namespace
+
+template <>
+__global__ __launch_bounds__(256, 2) void bgemm9_kernel<1, true>(Bgemm9Params q) {
+  const BgemmParams& p = q.g;
+  using S = BSmem<1, 1, 1, 4>;
+  constexpr int BM = 64, BN = 64;
+  extern __shared__ __attribute__((aligned(16))) float smem_b[];
+  float* As = smem_b;
+  float* Bs = smem_b + 2 * S::A_ELEMS;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int l31 = lane & 31, lh = lane >> 5;
+  float4* park = reinterpret_cast<float4*>(smem_b + 2 * (S::A_ELEMS + S::B_ELEMS)) + tid;   // [(pixel - 1) / 2][row piece][thread]
+
+  const int nslot = gridDim.x >> 3;
+  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+  const int qq = p.items >> 3, rr_ = p.items & 7;
+  const int run0 = xcd * qq + min(xcd, rr_), runlen = qq + (xcd < rr_ ? 1 : 0);
+  if (slot >= runlen) return;
+  const int n_items = (runlen - slot + nslot - 1) / nslot;
+  const int tiles = p.tiles_m * p.tiles_n;
+
+  auto coords = [&](int w, int& phs, int& bm, int& bn) __attribute__((always_inline)) {
+    phs = w / tiles;
+    const int t = w - phs * tiles;
+    const int g = p.group_n, per_group = g * p.tiles_m;
+    const int grp = t / per_group, rr = t - grp * per_group, n0 = grp * g;
+    const int width = min(g, p.tiles_n - n0);
+    const int tm = rr / width;
+    bm = tm * BM;
+    bn = (n0 + rr - tm * width) * BN;
+  };
+
+  // ---- loader state: the K-tile (l_t) of the item (l_item) whose stages are being fetched ------------------------------------------------
+  const int kq = tid & 7, r0 = tid >> 3;
+  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(q.dy), (short)0, (int)p.a_bytes, 0x00020000);
+  const int rowpx = q.dWo * p.K;      // elements per dy row
+  int a_off[2], b_off[2];             // a_off: the window origin (pixel (0,0)) of the row's tile; may point before the row / the map: only used under its window bit
+  unsigned a_win[2];                  // which of the 3 x 3 window pixels lie inside the dy map (bit r * 3 + c); 0 for rows beyond T
+  bool b_ok[2];
+  int l_item = -1, l_t = p.ntiles - 1, l_phs = 0;
+
+  auto advance = [&]() __attribute__((always_inline)) {
+    if (++l_t < p.ntiles) return;
+    l_t = 0;
+    ++l_item;
+    if (l_item >= n_items) {          // past the last item: the look-ahead fetches zeros
+#pragma unroll
+      for (int i = 0; i < 2; ++i) { a_win[i] = 0u; b_ok[i] = false; }
+      return;
+    }
+    int bm, bn;
+    coords(run0 + slot + l_item * nslot, l_phs, bm, bn);
+    const int ph = l_phs >> 1, pw = l_phs & 1;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int m = bm + r0 + 32 * i;
+      const int b = m / (q.Th * q.Tw), rem = m - b * (q.Th * q.Tw);
+      const int ty = rem / q.Tw, tx = rem - ty * q.Tw;
+      const int oh0 = 2 * ty + ph - 1, ow0 = 2 * tx + pw - 1;
+      a_off[i] = ((b * q.dHo + oh0) * q.dWo + ow0) * p.K + kq * 4;
+      unsigned w = 0u;
+#pragma unroll
+      for (int rr2 = 0; rr2 < 3; ++rr2)
+#pragma unroll
+        for (int cc2 = 0; cc2 < 3; ++cc2)
+          if ((unsigned)(oh0 + rr2) < (unsigned)q.dHo && (unsigned)(ow0 + cc2) < (unsigned)q.dWo) w |= 1u << (rr2 * 3 + cc2);
+      a_win[i] = m < p.M ? w : 0u;
+      const int n = bn + r0 + 32 * i;
+      b_ok[i] = n < p.N;
+      b_off[i] = n * p.K + kq * 4;
+    }
+  };
+
+  // stage I of the loader's K-tile: the one new pixel of position w9_pos(I) (raw, two row pieces) and that position's U tile
+  float4 areg[2], breg[2];
+  auto load_stage = [&](auto I_, float4* ar, float4* br) __attribute__((always_inline)) {
+    constexpr int P = w9_pos(decltype(I_)::value), r = P / 3, c = P - 3 * r;
+    const int k0 = l_t * BK;
+    const bool kin = k0 + kq * 4 < p.K;
+    const int tap = r * rowpx + c * p.K + k0;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) ar[i] = bl4(ra, a_off[i] + tap, kin & (((a_win[i] >> P) & 1u) != 0u));
+    const int ps = ((2 - r) * 3 + (2 - c)) * 4 + (3 - l_phs);
+    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.b + (int64_t)ps * p.sb), (short)0, (int)p.b_bytes, 0x00020000);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) br[i] = bl4(rb, b_off[i] + k0, b_ok[i] & kin);
+  };
+
+  // the parked taps a corner position is formed with: tb = d[1][c] (pixel 3 or 5), tc = d[r][1] (pixel 1 or 7)
+  float4 c4[2];                                                            // the centre pixel of the K-tile being formed
+  auto park_read = [&](auto I_, float4* tb, float4* tc) __attribute__((always_inline)) {
+    constexpr int P = w9_pos(decltype(I_)::value), r = P / 3, c = P - 3 * r;
+    if (r != 1 && c != 1) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        tb[i] = park[(((3 + c) - 1) / 2 * 2 + i) * 256];
+        tc[i] = park[(((3 * r + 1) - 1) / 2 * 2 + i) * 256];
+      }
+    }
+  };
+  // forms V of stage I from its new pixel (ar), the centre and the parked taps, and writes the stage's two LDS images
+  auto form_store = [&](auto I_, int buf, const float4* ar, const float4* br, const float4* pb, const float4* pc) __attribute__((always_inline)) {
+    constexpr int P = w9_pos(decltype(I_)::value), r = P / 3, c = P - 3 * r;
+    float* as = As + buf * S::A_ELEMS;
+    float* bs = Bs + buf * S::B_ELEMS;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) *reinterpret_cast<float4*>(&bs[(r0 + 32 * i) * KSTRIDE + kq * 4]) = br[i];
+    if (P == 4) { c4[0] = ar[0]; c4[1] = ar[1]; }
+    if ((P & 1) != 0) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) park[((P - 1) / 2 * 2 + i) * 256] = ar[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const float4 tb = r == 1 ? zero : c == 1 ? c4[i] : pb[i];
+      const float4 tc = c == 1 ? zero : r == 1 ? c4[i] : pc[i];
+      const float4 td = (r != 1 && c != 1) ? c4[i] : zero;
+      *reinterpret_cast<float4*>(&as[(r0 + 32 * i) * KSTRIDE + kq * 4]) = sub4(sub4(ar[i], tb), sub4(tc, td));
+    }
+  };
+
+  struct Frag { float a[4]; float b[4]; };
+  auto read_frag = [&](Frag& f, const float* as, const float* bs, int c) __attribute__((always_inline)) {
+    const float4 va = *reinterpret_cast<const float4*>(&as[(wm * 32 + l31) * KSTRIDE + c * 8 + lh * 4]);
+    f.a[0] = va.x; f.a[1] = va.y; f.a[2] = va.z; f.a[3] = va.w;
+    const float4 vb = *reinterpret_cast<const float4*>(&bs[(wn * 32 + l31) * KSTRIDE + c * 8 + lh * 4]);
+    f.b[0] = vb.x; f.b[1] = vb.y; f.b[2] = vb.z; f.b[3] = vb.w;
+  };
+
+  f32x16 acc[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
+
+  // stage I of a K-tile, LDS buffer t (bgemm_kernel's schedule): multiplies into acc[w9_pos(I)], forms and stores stage I + 1, loads stage I + 2
+  auto k_tile = [&](auto I_, int t, Frag& c0, Frag& c1, Frag& n0, Frag& n1) __attribute__((always_inline)) {
+    constexpr int I = decltype(I_)::value, P = w9_pos(I);
+    using IN = std::integral_constant<int, (I + 1) % 9>;
+    using IL = std::integral_constant<int, (I + 2) % 9>;
+    const float* as = As + (t & 1) * S::A_ELEMS;
+    const float* bs = Bs + (t & 1) * S::B_ELEMS;
+    const float* an = As + ((t + 1) & 1) * S::A_ELEMS;
+    const float* bn_ = Bs + ((t + 1) & 1) * S::B_ELEMS;
+    auto mma = [&](const Frag& f) __attribute__((always_inline)) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[P] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[j], f.b[j], acc[P], 0, 0, 0);
+    };
+    float4 pb[2], pc[2];
+    __builtin_amdgcn_sched_barrier(0);
+    mma(c0);
+    __builtin_amdgcn_sched_barrier(0);
+    read_frag(c0, as, bs, 2);
+    park_read(IN{}, pb, pc);
+    __builtin_amdgcn_sched_barrier(0);
+    mma(c1);
+    form_store(IN{}, (t + 1) & 1, areg, breg, pb, pc);
+#pragma unroll
+    for (int q2 = 0; q2 < 4; ++q2) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
+      __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);   // VALU (the subtractions of the transform)
+      __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);   // DS write
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    read_frag(c1, as, bs, 3);
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();
+    read_frag(n0, an, bn_, 0);
+    read_frag(n1, an, bn_, 1);
+    __builtin_amdgcn_sched_barrier(0);
+    load_stage(IL{}, areg, breg);
+    mma(c0);
+#pragma unroll
+    for (int q2 = 0; q2 < 4; ++q2) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    mma(c1);
+  };
+
+  advance();                                              // the first item's first K-tile
+  {
+    float4 a0[2], b0[2];
+    load_stage(std::integral_constant<int, 0>{}, a0, b0);
+    load_stage(std::integral_constant<int, 1>{}, areg, breg);
+    form_store(std::integral_constant<int, 0>{}, 0, a0, b0, a0, a0);   // (stage 0 is the centre position: no parked taps)
+  }
+  __syncthreads();
+  Frag fa0, fa1, fb0, fb1;
+  read_frag(fa0, As, Bs, 0);
+  read_frag(fa1, As, Bs, 1);
+  // one K-tile = nine stages; u = parity of its first stage's buffer.  Stages 7 and 8 already load stages 0 and 1 of the NEXT K-tile (of the next
+  // item after the last one): the loader moves on between stages 6 and 7 — between two stages, never inside one (see bgemm_kernel).
+#define T2I_W9_STAGE(I, u) \
+  if ((((u) + (I)) & 1) == 0) k_tile(std::integral_constant<int, I>{}, 0, fa0, fa1, fb0, fb1); \
+  else k_tile(std::integral_constant<int, I>{}, 1, fb0, fb1, fa0, fa1);
+#define T2I_W9_KTILE(u) \
+  T2I_W9_STAGE(0, u) T2I_W9_STAGE(1, u) T2I_W9_STAGE(2, u) T2I_W9_STAGE(3, u) T2I_W9_STAGE(4, u) T2I_W9_STAGE(5, u) T2I_W9_STAGE(6, u) \
+  advance(); \
+  T2I_W9_STAGE(7, u) T2I_W9_STAGE(8, u)
+  const int plane_px = q.Th * q.Tw;
+  for (int it = 0; it < n_items; ++it) {
+    for (int t = 0; t < p.ntiles; t += 2) {              // ntiles is even (host side): buffer parity restarts at 0 for every item
+      T2I_W9_KTILE(0)
+      T2I_W9_KTILE(1)
+    }
+#undef T2I_W9_KTILE
+#undef T2I_W9_STAGE
+    // ---- A^T M A + bias + activation on the accumulators (the arithmetic, and its order, of wino2b_output_kernel)
+    int phs, bm, bn;
+    coords(run0 + slot + it * nslot, phs, bm, bn);
+    const int ph = phs >> 1, pw = phs & 1;
+    const int n = bn + wn * 32 + l31;
+    const float bs_ = (q.bias && n < p.N) ? q.bias[n] : 0.f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int m = bm + wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
+      float z[2][3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        z[0][c] = acc[0 * 3 + c][e] + acc[1 * 3 + c][e];
+        z[1][c] = acc[1 * 3 + c][e] + acc[2 * 3 + c][e];
+      }
+      if (m < p.M && n < p.N) {
+        const int b = m / plane_px, rem = m - b * plane_px;
+        const int ty = rem / q.Tw, tx = rem - ty * q.Tw;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          const float y0 = apply_act((z[r][0] + z[r][1]) + bs_, q.act, q.alpha);
+          const float y1 = apply_act((z[r][1] + z[r][2]) + bs_, q.act, q.alpha);
+          const size_t oh = (size_t)q.sr * (2 * ty + r) + ph, ow0 = (size_t)q.sr * (2 * tx) + pw;
+          float* o = q.out + (((size_t)b * q.OH + oh) * q.OW + ow0) * p.N + n;
+          o[0] = y0;
+          o[(size_t)q.sr * p.N] = y1;
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
+  }
+}
+
 hipError_t bgemm9_launch(int lay, const Bgemm9Params& q, hipStream_t stream) {
   if (lay != 0 && lay != 1) return hipErrorInvalidValue;
   const int bytes = lay == 0 ? BSmem<0, 1, 1, 4>::BYTES : BSmem<1, 1, 1, 4>::BYTES;
@@ -611,8 +838,16 @@ hipError_t bgemm9_launch(int lay, const Bgemm9Params& q, hipStream_t stream) {
   int nslot = per_xcd < 32 * 2 ? per_xcd : 32 * 2;             // two workgroups per CU (144 accumulator registers per lane)
   if (nslot < 1) nslot = 1;
   if (lay == 0) hipLaunchKernelGGL((bgemm9_kernel<0, false>), dim3(nslot * 8), dim3(256), bytes, stream, q);
-  else if (q.dy) hipLaunchKernelGGL((bgemm9_kernel<1, true>), dim3(nslot * 8), dim3(256), bytes, stream, q);
-  else hipLaunchKernelGGL((bgemm9_kernel<1, false>), dim3(nslot * 8), dim3(256), bytes, stream, q);
+  else if (q.dy) {
+    constexpr int wbytes = BSmem<1, 1, 1, 4>::BYTES + W9_PARK_BYTES;      // images + parked window pixels: 68 KB, two workgroups in a CU's 160 KB
+    static bool attr_done = false;   // benign race: idempotent
+    if (!attr_done) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(bgemm9_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, wbytes);
+      if (e != hipSuccess) return e;
+      attr_done = true;
+    }
+    hipLaunchKernelGGL((bgemm9_kernel<1, true>), dim3(nslot * 8), dim3(256), wbytes, stream, q);
+  } else hipLaunchKernelGGL((bgemm9_kernel<1, false>), dim3(nslot * 8), dim3(256), bytes, stream, q);
   return hipGetLastError();
 }
 

@@ -591,10 +591,12 @@ static int wino2_fused_gemm(int lay, int phases, size_t T, int N, int K, const f
   // dy_raw != NULL (input gradient): the loader transforms dy itself; V is not read (and need not have been written)
   const int mode = tuning().wino_fuse;
   if (!mode || !tuning().bgemm) return -1;
-  const int ntiles = (K + 31) / 32;
+  // K-tiles of 32, an even number of them.  The loader transform pads an odd count with one K-tile that reads zeros through the range
+  // check (acc + 0 * 0 = acc) and addresses dy by pixel, so it takes any T; the V-plane forms keep their conditions
+  const int ntiles = dy_raw ? ((K + 31) / 32 + 1) & ~1 : (K + 31) / 32;
   const int64_t a_elems = dy_raw ? dy_elems : (int64_t)T * K, b_elems = (int64_t)N * K;
   if (dy_raw) V = dy_raw;       // (alignment / extent checks below apply to the operand actually read)
-  if ((ntiles & 1) || (T & 3) || (N & 3) || (K & 3) || (reinterpret_cast<uintptr_t>(V) & 15) || (reinterpret_cast<uintptr_t>(U) & 15) || (sa & 3) || (sb & 3) ||
+  if ((ntiles & 1) || (!dy_raw && (T & 3)) || (N & 3) || (K & 3) || (reinterpret_cast<uintptr_t>(V) & 15) || (reinterpret_cast<uintptr_t>(U) & 15) || (sa & 3) || (sb & 3) ||
       a_elems >= (1LL << 30) || b_elems >= (1LL << 30) || T >= (1u << 30))
     return -1;
   Bgemm9Params q;
