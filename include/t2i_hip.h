@@ -602,6 +602,50 @@ int t2i_pooled_grad_scatter(const float* g, const float* mask, int32_t B, int32_
 int t2i_rmsprop_tf(float* w, const float* g, float* ms, float* mom, int64_t n, float lr, float rho, float momentum, float eps,
                    t2i_stream_t stream);
 
+/* ---- the rest of the operator surface: reference utils/ops.py:94-97 (pixel_norm), :100-101 (pool, any window), :104-116
+ * (resize_nearest_neighbor / upscale / downscale), :145-148 (gn).  Added within ABI v13: no existing argument list changed.
+ * fp32 tensors; 16-byte accesses when C % 4 == 0 and the tensors are 16-byte aligned, a scalar form for any other C; no atomics,
+ * every sum in a fixed order: results repeat bit for bit. ---------------------------------------------------------------- */
+/* u = act(x), y = u / sqrt(mean_c(u^2) + eps) over x [rows, C]; rnorm[rows] = 1 / sqrt(mean_c(u^2) + eps) is kept for the
+ * backward.  One launch: a row is reduced by a power-of-two group of lanes of one wave through cross-lane shuffles and stays
+ * in registers up to the scaling (rows of up to 2048 floats in the 16-byte form; wider rows are read twice). */
+int t2i_pixel_norm_fwd(const float* x, int64_t rows, int32_t C, float eps, int act, float alpha, float* y, float* rnorm,
+                       t2i_stream_t stream);
+/* dx = du * act'(.), du = s (g - y mean_c(g y)), s = rnorm: u is recovered as y / s, so no x is needed (lrelu / relu read the
+ * derivative from the sign of y, tanh is 1 - u^2).  The sign of y is the sign of x only for a slope alpha >= 0: both entry
+ * points return T2I_ERR_INVALID for T2I_ACT_LRELU with alpha < 0.  One launch. */
+int t2i_pixel_norm_bwd(const float* g, const float* y, const float* rnorm, int64_t rows, int32_t C, int act, float alpha, float* dx,
+                       t2i_stream_t stream);
+/* tf.image.resize_nearest_neighbor(align_corners = False): y[b,r,q,:] = x[b, src_h(r), src_w(q), :] with
+ * src_h(r) = min(int(floorf(r * hs)), H - 1), hs = float(H) / float(Ho) in fp32, columns alike.  x [B,H,W,C] -> y [B,Ho,Wo,C]. */
+int t2i_resize_nearest(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t Ho, int32_t Wo, float* y, t2i_stream_t stream);
+/* Its adjoint, also a gather (the map is monotone): dx[b,h,w,:] = the sum of g [B,Ho,Wo,C] over the contiguous block of output
+ * rows and columns whose source is (h, w), rows outer, columns inner. */
+int t2i_resize_nearest_adj(const float* g, int32_t B, int32_t H, int32_t W, int32_t C, int32_t Ho, int32_t Wo, float* dx,
+                           t2i_stream_t stream);
+/* tf.nn.pool, window = stride = s (1 <= s <= 32768), SAME: x [B,H,W,C] -> y [B,Ho,Wo,C], Ho = ceil(H / s), the padding
+ * Ho s - H split with the smaller half in front.  op = T2I_POOL_AVG: sum of the taps inside the image (row-major) / their
+ * count; idx must be NULL.  T2I_POOL_MAX: padding ignored; idx (int32 [B,Ho,Wo,C] or NULL) receives the window offset
+ * ky * s + kx of the FIRST maximum in row-major window order. */
+int t2i_pool_same_fwd(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t s, int32_t op, float* y, int32_t* idx,
+                      t2i_stream_t stream);
+/* Backward as a per-input gather (windows do not overlap): g [B,Ho,Wo,C] -> dx [B,H,W,C]; AVG: g of the pixel's window / that
+ * window's count; MAX: g of the pixel's window where idx holds this pixel's offset, else 0. */
+int t2i_pool_same_bwd(const float* g, const int32_t* idx, int32_t B, int32_t H, int32_t W, int32_t C, int32_t s, int32_t op, float* dx,
+                      t2i_stream_t stream);
+/* y[b,oh,ow,c] = x at offset idx[b,oh,ow,c] of that window (0 where the offset leaves the image): MAX pooling as the linear map
+ * it is for fixed offsets — the backward of the MAX backward. */
+int t2i_pool_same_take(const float* x, const int32_t* idx, int32_t B, int32_t H, int32_t W, int32_t C, int32_t s, float* y,
+                       t2i_stream_t stream);
+/* y = x * f, f = exp(nrm * log_m), nrm ~ N(0, 1) per element (log_m = log(noise magnitude) >= 0; 0 gives f = 1 and y = x bit
+ * for bit).  Normals by Box-Muller from Philox4x32-10 keyed by seed and counted by (offset + i / 4) in a counter subsequence of
+ * its own (third counter word non-zero; t2i_trunc_normal uses 0): a pure function of (seed, offset, i).  The caller advances
+ * offset by (n + 3) / 4 per call.  f may be NULL (no backward will follow): the factor is then not written, y is the same.
+ * One launch. */
+int t2i_gn_fwd(const float* x, int64_t n, float log_m, uint64_t seed, uint64_t offset, float* y, float* f, t2i_stream_t stream);
+/* y = a * b, n elements: the backward (and every further derivative) of gn. */
+int t2i_mul(const float* a, const float* b, int64_t n, float* y, t2i_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

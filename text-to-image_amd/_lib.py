@@ -131,6 +131,15 @@ SIGNATURES = {
     't2i_pooled_grad_scatter': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _f, _i32, ctypes.POINTER(ctypes.c_void_p),
                                                ctypes.POINTER(_i32), ctypes.POINTER(_i32), _p]),
     't2i_rmsprop_tf': (ctypes.c_int, [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _p]),
+    't2i_pixel_norm_fwd': (ctypes.c_int, [_p, _i64, _i32, _f, ctypes.c_int, _f, _p, _p, _p]),
+    't2i_pixel_norm_bwd': (ctypes.c_int, [_p, _p, _p, _i64, _i32, ctypes.c_int, _f, _p, _p]),
+    't2i_resize_nearest': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p]),
+    't2i_resize_nearest_adj': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p]),
+    't2i_pool_same_fwd': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p]),
+    't2i_pool_same_bwd': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p]),
+    't2i_pool_same_take': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p]),
+    't2i_gn_fwd': (ctypes.c_int, [_p, _i64, _f, ctypes.c_uint64, ctypes.c_uint64, _p, _p, _p]),
+    't2i_mul': (ctypes.c_int, [_p, _p, _i64, _p, _p]),
 }
 
 if not os.path.exists(LIB_PATH):

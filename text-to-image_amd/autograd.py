@@ -702,3 +702,210 @@ class LerpDevFn(Function):
             gb = LerpDevFn.apply(g, None, ctx.t_dev, 1) if ctx.needs_input_grad[1] else None
             return ga, gb, None, None
         return (LerpDevFn.apply(g, None, ctx.t_dev, ctx.mode) if ctx.needs_input_grad[0] else None), None, None, None
+
+
+# ---- the rest of the operator surface (reference utils/ops.py:94-116,145-148) ---------------------------------------------
+class PixelNormFn(Function):
+    """y = u / sqrt(mean_c(u^2) + eps), u = act(x), over the last axis (reference utils/ops.py:94-97): one launch forward, one backward.
+    The backward works from y and the saved per-pixel 1 / norm alone (u = y * norm), so x is not kept.  A generator-side operator in
+    the PGGAN paper, as LayerNormFn is here => first order."""
+
+    @staticmethod
+    def forward(ctx, x, eps, act, alpha):
+        y, rnorm = K.pixel_norm_fwd(x, eps, act, alpha)
+        ctx.save_for_backward(y, rnorm)
+        ctx.act, ctx.alpha = act, alpha
+        ctx.set_materialize_grads(False)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        if gy is None:
+            return None, None, None, None
+        y, rnorm = ctx.saved_tensors
+        return K.pixel_norm_bwd(_c(gy), y, rnorm, ctx.act, ctx.alpha), None, None, None
+
+
+class ResizeNearestFn(Function):
+    """tf.image.resize_nearest_neighbor (reference utils/ops.py:104-116), [B,H,W,C] -> [B,Ho,Wo,C].  Linear; its backward is
+    ResizeNearestAdjFn, whose backward is this Function again: closed under differentiation of any order (usable inside the critic
+    under the gradient penalty, like Pool2Fn / Upscale2Fn)."""
+
+    @staticmethod
+    def forward(ctx, x, Ho, Wo):
+        ctx.hw = (x.shape[1], x.shape[2])
+        ctx.set_materialize_grads(False)
+        return K.resize_nearest(_c(x), Ho, Wo)
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None
+        return ResizeNearestAdjFn.apply(g, ctx.hw[0], ctx.hw[1]), None, None
+
+
+class ResizeNearestAdjFn(Function):
+    """The adjoint of the nearest resize from an [B,H,W,C] map: every input pixel gathers the sum of its block of output pixels."""
+
+    @staticmethod
+    def forward(ctx, g, H, W):
+        ctx.out_hw = (g.shape[1], g.shape[2])
+        ctx.set_materialize_grads(False)
+        return K.resize_nearest_adj(_c(g), H, W)
+
+    @staticmethod
+    def backward(ctx, gg):
+        if gg is None:
+            return None, None, None
+        return ResizeNearestFn.apply(gg, ctx.out_hw[0], ctx.out_hw[1]), None, None
+
+
+class PoolAvgFn(Function):
+    """tf.nn.pool AVG, window = stride = s, SAME, any extents (the mean of the taps inside the image).  Linear; adjoint: PoolAvgAdjFn."""
+
+    @staticmethod
+    def forward(ctx, x, s):
+        ctx.s, ctx.hw = s, (x.shape[1], x.shape[2])
+        ctx.set_materialize_grads(False)
+        return K.pool_same_fwd(_c(x), s, K.POOL_AVG)[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None
+        return PoolAvgAdjFn.apply(g, ctx.hw[0], ctx.hw[1], ctx.s), None
+
+
+class PoolAvgAdjFn(Function):
+    """dx[pixel] = g[its window] / count(its window); its backward is the average pool again."""
+
+    @staticmethod
+    def forward(ctx, g, H, W, s):
+        ctx.s = s
+        ctx.set_materialize_grads(False)
+        return K.pool_same_bwd(_c(g), None, H, W, s, K.POOL_AVG)
+
+    @staticmethod
+    def backward(ctx, gg):
+        if gg is None:
+            return None, None, None, None
+        return PoolAvgFn.apply(gg, ctx.s), None, None, None
+
+
+class PoolMaxFn(Function):
+    """tf.nn.pool MAX, window = stride = s, SAME (padding ignored).  The forward records the window offset of each first maximum;
+    with those fixed the pool is the linear map PoolMaxTakeFn, and the derivatives are that map's (PoolMaxPutFn <-> PoolMaxTakeFn).
+    The offsets are written only when x asks for a gradient (nothing produced under no_grad does): inference pays for y alone."""
+
+    @staticmethod
+    def forward(ctx, x, s):
+        y, idx = K.pool_same_fwd(_c(x), s, K.POOL_MAX, want_idx=ctx.needs_input_grad[0])
+        ctx.s, ctx.hw, ctx.idx = s, (x.shape[1], x.shape[2]), idx
+        ctx.set_materialize_grads(False)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None
+        return PoolMaxPutFn.apply(g, ctx.idx, ctx.hw[0], ctx.hw[1], ctx.s), None
+
+
+class PoolMaxPutFn(Function):
+    """dx[pixel] = g[its window] where the window's recorded offset is this pixel's, else 0."""
+
+    @staticmethod
+    def forward(ctx, g, idx, H, W, s):
+        ctx.s, ctx.idx = s, idx
+        ctx.set_materialize_grads(False)
+        return K.pool_same_bwd(_c(g), idx, H, W, s, K.POOL_MAX)
+
+    @staticmethod
+    def backward(ctx, gg):
+        if gg is None:
+            return None, None, None, None, None
+        return PoolMaxTakeFn.apply(gg, ctx.idx, ctx.s), None, None, None, None
+
+
+class PoolMaxTakeFn(Function):
+    """y[window] = x at the window's recorded offset."""
+
+    @staticmethod
+    def forward(ctx, x, idx, s):
+        ctx.s, ctx.idx, ctx.hw = s, idx, (x.shape[1], x.shape[2])
+        ctx.set_materialize_grads(False)
+        return K.pool_same_take(_c(x), idx, s)
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None
+        return PoolMaxPutFn.apply(g, ctx.idx, ctx.hw[0], ctx.hw[1], ctx.s), None, None
+
+
+class MulFn(Function):
+    """a * f with a constant factor tensor f (no gradient to f): its own adjoint, so differentiable to any order."""
+
+    @staticmethod
+    def forward(ctx, a, f):
+        ctx.f = f
+        ctx.set_materialize_grads(False)
+        return K.mul(_c(a), f)
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None
+        return MulFn.apply(g, ctx.f), None
+
+
+class GnFn(Function):
+    """y = x * m^n, n ~ N(0, 1) per element (reference utils/ops.py:145-148): one launch writes y and the factor f = m^n; the
+    backward is g * f (MulFn), which is its own adjoint.  f is written only when x asks for a gradient; the draw is the same either way."""
+
+    @staticmethod
+    def forward(ctx, x, log_m):
+        y, f = K.gn_fwd(_c(x), log_m, want_f=ctx.needs_input_grad[0])
+        ctx.f = f
+        ctx.set_materialize_grads(False)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None
+        return MulFn.apply(g, ctx.f), None
+
+
+class BatchRenormTrainFn(Function):
+    """Training-mode batch renormalisation (tf.contrib.layers.batch_norm(renorm=True), non-fused path; reference utils/ops.py:32-55):
+    y = act(((x - mu) / sigma * r + d) * gamma + beta) with r, d [C] constants for the gradient.  Built from the batch-norm kernels:
+    the caller supplies mu and rstd = 1 / sigma (kernels.bn_stats); the forward is one bn_apply with scale = gamma r / sigma, the
+    backward is the batch-norm backward with gamma r in place of gamma for dx, dbeta = sum g, dgamma = r sum g xhat + d sum g.
+    First order, like BatchNormTrainFn."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, mean, rstd, r, d, act, alpha):
+        x = _c(x)
+        scale = gamma * r * rstd
+        shift = beta + gamma * d - mean * scale
+        y = K.bn_apply(x, scale.contiguous(), shift.contiguous(), act, alpha)
+        ctx.save_for_backward(x, gamma, mean, rstd, r, d, y if act != K.ACT_NONE else None)
+        ctx.act, ctx.alpha = act, alpha
+        ctx.set_materialize_grads(False)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        if gy is None:
+            return (None,) * 9
+        x, gamma, mean, rstd, r, d, y = ctx.saved_tensors
+        gy = _c(gy)
+        if ctx.act != K.ACT_NONE:
+            gy = K.act_bwd(gy, y, ctx.act, ctx.alpha)
+        sum_dy, sum_dy_x = K.col_reduce(gy, x, True, center=mean)         # sum g, sum g * (x - mu)
+        dx, g_xhat, dbeta = K.bn_bwd(gy, x, mean, rstd, (gamma * r).contiguous(), sum_dy, sum_dy_x)      # g_xhat = sum g * xhat
+        dgamma = r * g_xhat + d * dbeta
+        return (dx, dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None) + (None,) * 6

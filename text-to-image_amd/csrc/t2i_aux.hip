@@ -1616,18 +1616,9 @@ __global__ void kt_sgd_kernel(float* __restrict__ kt, const float* __restrict__ 
 // every run): out = mean + std * t with t ~ N(0,1) restricted to [lo, hi] — by inverting the normal CDF on a uniform draw in
 // (Phi(lo), Phi(hi)), the same construction torch.nn.init.trunc_normal_ uses (8 tensor-library launches per draw: uniform, two scalings,
 // erfinv, two more scalings, clamp).  Uniforms come from Philox4x32-10 keyed by (seed, offset + element / 4): counter-based, so the draw
-// is a pure function of (seed, offset, index) — reproducible whatever the launch geometry.
+// is a pure function of (seed, offset, index) — reproducible whatever the launch geometry (philox4x32_10 and the counter-word
+// conventions: t2i_internal.h).
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned* out) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 
 __global__ __launch_bounds__(256) void trunc_normal_kernel(float* __restrict__ out, size_t n, unsigned long long seed, unsigned long long offset,
                                                            float mean, float std, float lo, float hi, float cdf_lo, float cdf_span) {
@@ -1635,7 +1626,7 @@ __global__ __launch_bounds__(256) void trunc_normal_kernel(float* __restrict__ o
   for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (size_t)gridDim.x * blockDim.x) {
     const unsigned long long ctr = offset + q;
     unsigned r[4];
-    philox4x32_10((unsigned)ctr, (unsigned)(ctr >> 32), 0u, 0u, (unsigned)seed, (unsigned)(seed >> 32), r);
+    philox4x32_10((unsigned)ctr, (unsigned)(ctr >> 32), kPhiloxTruncNormal, 0u, (unsigned)seed, (unsigned)(seed >> 32), r);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const size_t i = q * 4 + e;

@@ -26,19 +26,7 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kMaxScatterBranches = T2I_MAX_SCATTER_BRANCHES;
 
-// Philox4x32-10 (Salmon et al., SC'11) — the generator of t2i_trunc_normal, restated for this translation unit.
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned* out) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-// One thread per 4 consecutive (b, d) elements (D % 4 == 0): the four uniforms of one Philox call.
+// One thread per 4 consecutive (b, d) elements (D % 4 == 0): the four uniforms of one Philox call (philox4x32_10: t2i_internal.h).
 __global__ __launch_bounds__(kThreads) void pool_dropout_kernel(const float* __restrict__ x, int B, int HW, int D, float keep,
                                                                 unsigned long long seed, unsigned long long step,
                                                                 float* __restrict__ pre, float* __restrict__ mask,

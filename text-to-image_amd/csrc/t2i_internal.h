@@ -81,6 +81,27 @@ __device__ __forceinline__ float apply_act(float v, int act, float alpha) {
   }
 }
 
+// Philox4x32-10 (Salmon et al., SC'11), the one counter-based generator of the library.  Every user keys it with a 64-bit seed
+// (k0, k1) and puts a 64-bit running count in counter words c0, c1; words c2, c3 tell the users apart, and the conventions live here
+// so that no two of them can draw from the same counter under the same seed:
+//   t2i_trunc_normal (t2i_aux.hip)          c0, c1 = offset + element / 4     c2 = kPhiloxTruncNormal   c3 = 0
+//   t2i_gn_fwd (t2i_ops.hip)                c0, c1 = offset + element / 4     c2 = kPhiloxGn            c3 = 0
+//   pool_dropout (t2i_incep_train.hip)      c0, c1 = element / 4              c2, c3 = the trainer's step; keyed by the trainer's own
+//                                           seed, never by the device generator the two above share
+constexpr unsigned kPhiloxTruncNormal = 0u;
+constexpr unsigned kPhiloxGn = 0x676e0001u;
+
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned* out) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
+    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
 // Winograd F(2x2, 3x3) for 3x3 stride-1 SAME convolutions with many channels (t2i_winograd.hip)
 bool winograd_eligible(const t2i_conv_desc& d, bool bwd_data);
 bool winograd_filter_eligible(const t2i_conv_desc& d);      // the filter gradient's own size rule on top of winograd_eligible(d, false)

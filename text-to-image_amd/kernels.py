@@ -1690,3 +1690,112 @@ def rmsprop_tf(w, g, ms, mom, lr, rho=0.9, momentum=0.0, eps=1e-10):
     if _live(w):
         check(lib.t2i_rmsprop_tf(_ptr(w), _ptr(g), _ptr(ms), _ptr(mom), w.numel(), float(lr), float(rho), float(momentum), float(eps),
                                  _stream()), 't2i_rmsprop_tf')
+
+
+# ---- the rest of the operator surface (reference utils/ops.py:94-116,145-148; csrc/t2i_ops.hip) --------------------------
+POOL_MAX, POOL_AVG = 0, 1         # T2I_POOL_MAX / T2I_POOL_AVG
+
+
+def pixel_norm_fwd(x, eps, act=ACT_NONE, alpha=0.2):
+    """x [..., C] -> (y = u / sqrt(mean_c(u^2) + eps) with u = act(x), rnorm [rows] = 1 / sqrt(mean_c(u^2) + eps)); one launch."""
+    _chk(x, 'x', f32=True)
+    C = x.shape[-1]
+    rows = x.numel() // C
+    y = torch.empty_like(x)
+    rnorm = torch.empty(rows, dtype=torch.float32, device=x.device)
+    if _live(x) and rows > 0:
+        check(lib.t2i_pixel_norm_fwd(_ptr(x), rows, C, float(eps), act, alpha, _ptr(y), _ptr(rnorm), _stream()), 't2i_pixel_norm_fwd')
+    return y, rnorm
+
+
+def pixel_norm_bwd(g, y, rnorm, act=ACT_NONE, alpha=0.2):
+    """-> dx of pixel_norm_fwd from the upstream gradient g, the output y and rnorm; one launch."""
+    _chk(g, 'g', f32=True); _chk(y, 'y', f32=True); _chk(rnorm, 'rnorm', f32=True)
+    assert g.shape == y.shape
+    C = y.shape[-1]
+    rows = y.numel() // C
+    dx = torch.empty_like(y)
+    if _live(y) and rows > 0:
+        check(lib.t2i_pixel_norm_bwd(_ptr(g), _ptr(y), _ptr(rnorm), rows, C, act, alpha, _ptr(dx), _stream()), 't2i_pixel_norm_bwd')
+    return dx
+
+
+def resize_nearest(x, Ho, Wo):
+    """x [B,H,W,C] -> [B,Ho,Wo,C], tf.image.resize_nearest_neighbor (align_corners=False)."""
+    _chk(x, 'x', f32=True)
+    B, H, W, C = x.shape
+    y = torch.empty((B, Ho, Wo, C), dtype=torch.float32, device=x.device)
+    if _live(x) and y.numel() > 0:
+        check(lib.t2i_resize_nearest(_ptr(x), B, H, W, C, Ho, Wo, _ptr(y), _stream()), 't2i_resize_nearest')
+    return y
+
+
+def resize_nearest_adj(g, H, W):
+    """The adjoint of resize_nearest from [B,H,W,C]: g [B,Ho,Wo,C] -> [B,H,W,C], each input pixel the sum of its output block."""
+    _chk(g, 'g', f32=True)
+    B, Ho, Wo, C = g.shape
+    dx = torch.empty((B, H, W, C), dtype=torch.float32, device=g.device)
+    if _live(g) and dx.numel() > 0:
+        check(lib.t2i_resize_nearest_adj(_ptr(g), B, H, W, C, Ho, Wo, _ptr(dx), _stream()), 't2i_resize_nearest_adj')
+    return dx
+
+
+def pool_same_fwd(x, s, op, want_idx=False):
+    """tf.nn.pool(window = stride = s, SAME) of x [B,H,W,C] -> (y [B,ceil(H/s),ceil(W/s),C], idx or None); idx (MAX only): int32
+    window offset of the first maximum."""
+    _chk(x, 'x', f32=True)
+    B, H, W, C = x.shape
+    y = torch.empty((B, -(-H // s), -(-W // s), C), dtype=torch.float32, device=x.device)
+    idx = torch.empty(y.shape, dtype=torch.int32, device=x.device) if (want_idx and op == POOL_MAX) else None
+    if _live(x) and y.numel() > 0:
+        check(lib.t2i_pool_same_fwd(_ptr(x), B, H, W, C, s, op, _ptr(y), _ptr(idx), _stream()), 't2i_pool_same_fwd')
+    return y, idx
+
+
+def pool_same_bwd(g, idx, H, W, s, op):
+    """g [B,Ho,Wo,C] -> dx [B,H,W,C]: AVG g / count of the pixel's window; MAX g where idx holds the pixel's offset, else 0."""
+    _chk(g, 'g', f32=True)
+    B, Ho, Wo, C = g.shape
+    assert (Ho, Wo) == (-(-H // s), -(-W // s)) and (idx is None) == (op == POOL_AVG)
+    if idx is not None:
+        assert idx.dtype == torch.int32 and idx.shape == g.shape and idx.is_contiguous()
+    dx = torch.empty((B, H, W, C), dtype=torch.float32, device=g.device)
+    if _live(g) and dx.numel() > 0:
+        check(lib.t2i_pool_same_bwd(_ptr(g), _ptr(idx), B, H, W, C, s, op, _ptr(dx), _stream()), 't2i_pool_same_bwd')
+    return dx
+
+
+def pool_same_take(x, idx, s):
+    """y[b,oh,ow,c] = x [B,H,W,C] at window offset idx[b,oh,ow,c]: MAX pooling with its offsets fixed (a linear map)."""
+    _chk(x, 'x', f32=True)
+    B, H, W, C = x.shape
+    assert idx.dtype == torch.int32 and tuple(idx.shape) == (B, -(-H // s), -(-W // s), C) and idx.is_contiguous()
+    y = torch.empty(idx.shape, dtype=torch.float32, device=x.device)
+    if _live(x) and y.numel() > 0:
+        check(lib.t2i_pool_same_take(_ptr(x), _ptr(idx), B, H, W, C, s, _ptr(y), _stream()), 't2i_pool_same_take')
+    return y
+
+
+def gn_fwd(x, log_m, want_f=True):
+    """-> (y = x * f, f = exp(n * log_m) or None) with n ~ N(0, 1) per element; one launch.  The Philox (seed, offset) come from — and
+    advance — the device's torch generator, as in trunc_normal_ (another counter subsequence: the two never draw the same numbers).
+    want_f=False skips writing the factor (no backward will ask for it); y is the same bits."""
+    _chk(x, 'x', f32=True)
+    y, f = torch.empty_like(x), (torch.empty_like(x) if want_f else None)
+    if _live(x) and x.numel() > 0:
+        gen = torch.cuda.default_generators[x.device.index if x.device.index is not None else torch.cuda.current_device()]
+        seed, off = int(gen.initial_seed()) & 0xFFFFFFFFFFFFFFFF, int(gen.get_offset())
+        quads = (x.numel() + 3) // 4
+        gen.set_offset(off + 4 * ((quads + 3) // 4))              # (torch wants multiples of 4)
+        check(lib.t2i_gn_fwd(_ptr(x), x.numel(), float(log_m), seed, off, _ptr(y), _ptr(f), _stream()), 't2i_gn_fwd')
+    return y, f
+
+
+def mul(a, b):
+    """a * b elementwise (same shape), one launch."""
+    _chk(a, 'a', f32=True); _chk(b, 'b', f32=True)
+    assert a.shape == b.shape
+    y = torch.empty_like(a)
+    if _live(a) and a.numel() > 0:
+        check(lib.t2i_mul(_ptr(a), _ptr(b), a.numel(), _ptr(y), _stream()), 't2i_mul')
+    return y

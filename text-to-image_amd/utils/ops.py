@@ -10,7 +10,14 @@ instead of tf.contrib.layers.  Differences that follow from "eager torch instead
   * data is physically NHWC always.  ``df=NCHW`` tensors are *logical* NCHW views (a permute of NHWC storage), so
     ``to_nchw`` / ``to_nhwc`` cost nothing and the result is layout-independent (SURVEY.md §7 last bullet).
 north_star's ``deconv2d / linear / bn`` do not exist in the reference; they are exported as aliases.
+Every public name of the reference's utils/ops.py exists here with its signature and defaults.  What remains different:
+  * ``pixel_norm``, ``resize_nearest_neighbor``, ``upscale`` (s != 2), ``downscale``, ``pool`` (anything but the 2x2 average on even
+    extents), ``gn`` and ``batch_renorm`` take fp32 tensors only: a bf16 tensor (bf16 storage) is refused with ValueError and a
+    stacked pass (``stacked.Stacked``) with NotImplementedError, both before any launch and naming the operator;
+  * ``batch_renorm`` and ``gn`` restate TF 1.4 as read from its sources; like the rest of the oracle they are not pinned against TF.
 """
+import math
+
 import torch
 
 from .. import autograd as A
@@ -225,6 +232,72 @@ def batch_norm(x, train, init=None, act=None, name=None, eps=1e-5, decay=0.9, df
     return post(y) if post else y
 
 
+RENORM_DECAY = 0.99          # tf.contrib.layers.batch_norm's renorm_decay default, which the reference leaves alone
+
+
+def batch_renorm(x, train, init=None, act=None, name=None, eps=1e-5, decay=0.9, df=NHWC):
+    """reference utils/ops.py:32-55 (tf.contrib.layers.batch_norm(renorm=True), renorm_clipping=None, renorm_decay=0.99; TF takes
+    its non-fused path).  Rank 4 or rank 2, fp32, no groups / fused_infer / stacked passes.  Variables: <scope>/BatchNorm[_k]/{beta,
+    gamma, moving_mean, moving_variance} as batch_norm, and the non-trainable renorm_mean [C], renorm_stddev [C], renorm_mean_weight (),
+    renorm_stddev_weight (), all starting at zero as in TF 1.4 (the zero-debiased averages need that: renorm_stddev / weight is the
+    running sigma, and the first step has r = 1, d = 0).
+    Training: mu, sigma = sqrt(biased variance + eps) of the batch; mixed = renorm + (1 - weight) * batch value; r = sigma / mixed_std,
+    d = (mu - mixed_mean) / mixed_std, both from the variables as they are before this call and constants for the gradient;
+    y = act(((x - mu) / sigma * r + d) * gamma + beta).  Inside update_ops() (times times): renorm <- renorm * 0.99 + value * 0.01,
+    weight <- weight * 0.99 + 0.01 for mean and stddev, and the moving statistics move with `decay` towards renorm_mean / weight
+    and (renorm_stddev / weight)^2 - eps.  Inference is batch_norm's.  Restated from TF 1.4's sources; not pinned against TF."""
+    st = S.default_store()
+    _check_df(df)
+    _fp32_plain(x, 'batch_renorm', rank=None)
+    if x.dim() == 4:
+        xp = _phys(x, df)
+    elif x.dim() == 2:
+        xp = x
+    else:
+        raise ValueError('batch_renorm expects rank 2 or 4, got shape %s' % (tuple(x.shape),))
+    C = xp.shape[-1]
+    kind, alpha, post = _split_act(act)
+    init = init or {}
+    with st.variable_scope(name or st.unique_op_name('BatchNorm'), reuse=st.reuse()):
+        beta = st.get_variable('beta', (C,), init.get('beta', S.constant_init(0.0)))
+        gamma = st.get_variable('gamma', (C,), init.get('gamma', S.constant_init(1.0)))
+        mm = st.get_variable('moving_mean', (C,), S.constant_init(0.0), trainable=False)
+        mv = st.get_variable('moving_variance', (C,), S.constant_init(1.0), trainable=False)
+        rm = st.get_variable('renorm_mean', (C,), S.constant_init(0.0), trainable=False)
+        rmw = st.get_variable('renorm_mean_weight', (), S.constant_init(0.0), trainable=False)
+        rs = st.get_variable('renorm_stddev', (C,), S.constant_init(0.0), trainable=False)
+        rsw = st.get_variable('renorm_stddev_weight', (), S.constant_init(0.0), trainable=False)
+    if train:
+        xc = xp.contiguous()
+        rows = xc.numel() // C
+        s0, m2 = K.bn_stats(xc)                      # sum, centred second moment: [C]-sized vector math from here on
+        with torch.no_grad():
+            mu = s0 / rows
+            sigma = torch.sqrt(m2 / rows + eps)
+            mixed_mean = rm + (1.0 - rmw) * mu
+            mixed_std = rs + (1.0 - rsw) * sigma
+            r = sigma / mixed_std
+            d = (mu - mixed_mean) / mixed_std
+            rstd = 1.0 / sigma
+            for _ in range(0 if K.is_dry() else int(_UPDATE_OPS[0])):       # (a dry pass holds no values)
+                rm.mul_(RENORM_DECAY).add_(mu, alpha=1.0 - RENORM_DECAY)
+                rmw.mul_(RENORM_DECAY).add_(1.0 - RENORM_DECAY)
+                rs.mul_(RENORM_DECAY).add_(sigma, alpha=1.0 - RENORM_DECAY)
+                rsw.mul_(RENORM_DECAY).add_(1.0 - RENORM_DECAY)
+                new_std = rs / rsw
+                mm.mul_(decay).add_(rm / rmw, alpha=1.0 - decay)
+                mv.mul_(decay).add_(new_std * new_std - eps, alpha=1.0 - decay)
+        y = A.BatchRenormTrainFn.apply(xc, gamma, beta, mu, rstd, r, d, kind, alpha)
+    else:
+        with torch.no_grad():
+            scale = gamma / torch.sqrt(mv + eps)
+            shift = beta - mm * scale
+        y = K.bn_apply(xp.contiguous(), scale.contiguous(), shift.contiguous(), kind, alpha)
+    if x.dim() == 4:
+        y = _logical(y, df)
+    return post(y) if post else y
+
+
 def layer_norm(x, act=None, scope=None, df=NHWC):
     """reference utils/ops.py:74-81 (tf.contrib.layers.layer_norm, begin_params_axis = channel axis).  Rank-4 NHWC or
     rank-2.  Variables: <scope>/LayerNorm[_k]/{beta [C] zeros, gamma [C] ones}."""
@@ -247,20 +320,104 @@ def layer_norm(x, act=None, scope=None, df=NHWC):
     return post(y) if post else y
 
 
+def _fp32_plain(x, op, rank=4):
+    """The refusals shared by the operators of csrc/t2i_ops.hip, all before any launch."""
+    if isinstance(x, ST.Stacked):
+        raise NotImplementedError('%s: a stacked pass (stacked.Stacked) is not supported' % op)
+    if x.dtype != torch.float32:
+        raise ValueError('%s: expected a float32 tensor, got %s (bf16 storage is not supported here)' % (op, x.dtype))
+    if rank is not None and x.dim() != rank:
+        raise ValueError('%s: expected a rank-%d tensor, got shape %s' % (op, rank, tuple(x.shape)))
+
+
+def pixel_norm(x, eps=1e-8, act=None):
+    """reference utils/ops.py:94-97: u = act(x), then u / sqrt(mean(u^2, axis=3) + eps) — the PGGAN paper's pixelwise feature
+    normalisation.  Rank 4, normalised over axis 3 of the tensor as given, which must be contiguous (a logical NCHW view is not:
+    pass to_nhwc(x)).  An ops.Activation is fused into the kernel; any other callable is applied first, unfused.  One launch forward,
+    one backward.  A generator-side operator, as layer_norm is: first order only (not usable under the gradient penalty).
+    The backward reads the derivative of lrelu / relu from the sign of y (as every Activation's backward in this package does), which
+    is the sign of x only for a slope >= 0: an lrelu_act with a negative slope is refused with ValueError."""
+    _fp32_plain(x, 'pixel_norm')
+    kind, alpha, pre = _split_act(act)
+    if kind == K.ACT_LRELU and alpha < 0.0:
+        raise ValueError('pixel_norm: lrelu_act(%g) has a negative slope; the backward takes the derivative from the sign of the output, '
+                         'which needs a slope >= 0' % alpha)
+    if pre is not None:
+        x = pre(x)
+        _fp32_plain(x, 'pixel_norm')
+    if not x.is_contiguous():
+        raise ValueError('pixel_norm normalises over the last axis of physically NHWC data; got a non-contiguous tensor (shape %s, strides %s) '
+                         '- convert a logical NCHW view with to_nhwc first' % (tuple(x.shape), x.stride()))
+    return A.PixelNormFn.apply(x, float(eps), kind, alpha)
+
+
 def pool(x, s=2, p_type='AVG', df=NHWC):
-    """reference utils/ops.py:100-101 (tf.nn.pool, window = stride = s, SAME).  The reference only calls pool(x, 2) with
-    the default average type on power-of-two maps: that case is built."""
-    if s != 2 or p_type != 'AVG':
-        raise NotImplementedError('pool: only the 2x2 average pool the reference uses is built (got s=%r, %r)' % (s, p_type))
+    """reference utils/ops.py:100-101 (tf.nn.pool, window = stride = s, SAME): any integer s >= 1, 'AVG' or 'MAX', any extents.
+    The output extent is ceil(H / s); the padding is split with the smaller half in front; AVG divides by the number of taps inside
+    the image and MAX ignores the padding.  Differentiable to any order.  pool(x, 2) on even extents — all the reference's models
+    use — is the 2x2 kernel pair Pool2Fn / Upscale2Fn as before."""
+    if p_type not in ('AVG', 'MAX'):
+        raise ValueError("pool: p_type must be 'AVG' or 'MAX', got %r" % (p_type,))
+    if int(s) != s or s < 1:
+        raise ValueError('pool: s must be an integer >= 1, got %r' % (s,))
+    s = int(s)
     _check_df(df)
-    return _logical(A.Pool2Fn.apply(_phys(x, df), 0.25), df)
+    xp = _phys(x, df)
+    if s == 2 and p_type == 'AVG' and xp.shape[1] % 2 == 0 and xp.shape[2] % 2 == 0:
+        return _logical(A.Pool2Fn.apply(xp, 0.25), df)
+    _fp32_plain(xp, 'pool')
+    # From s = max(H, W) on, one window holds the whole map and the padding only grows, so the result no longer depends on s: clamp it
+    # (the kernels bound s).  MAX offsets are then ky * s + kx in the CLAMPED window's coordinates; that is consistent because the
+    # clamped s is the one PoolMaxFn keeps in ctx, and every consumer of the offsets (PoolMaxPutFn, PoolMaxTakeFn) gets s from there.
+    s = min(s, max(int(xp.shape[1]), int(xp.shape[2]), 1))
+    y = A.PoolAvgFn.apply(xp, s) if p_type == 'AVG' else A.PoolMaxFn.apply(xp, s)
+    return _logical(y, df)
+
+
+def resize_nearest_neighbor(x, new_size):
+    """reference utils/ops.py:104-106 (tf.image.resize_nearest_neighbor, align_corners=False), NHWC: output row r reads source row
+    min(int(floor(r * scale)), H - 1) with scale = float32(H) / float32(H_out), columns alike.  A gather kernel whose adjoint is a
+    gather too: differentiable to any order."""
+    _fp32_plain(x, 'resize_nearest_neighbor')
+    Ho, Wo = int(new_size[0]), int(new_size[1])
+    if Ho < 1 or Wo < 1:
+        raise ValueError('resize_nearest_neighbor: empty output %dx%d' % (Ho, Wo))
+    return A.ResizeNearestFn.apply(x, Ho, Wo)
 
 
 def upscale(x, s=2):
-    """reference utils/ops.py:109-111: nearest-neighbour resize to (h*s, w*s), NHWC."""
-    if s != 2:
-        raise NotImplementedError('upscale: only the factor 2 the reference uses is built (got %r)' % (s,))
-    return A.Upscale2Fn.apply(x, 1.0)
+    """reference utils/ops.py:109-111: nearest-neighbour resize to (h*s, w*s), NHWC, any integer s >= 1."""
+    if int(s) != s or s < 1:
+        raise ValueError('upscale: s must be an integer >= 1, got %r' % (s,))
+    if s == 2:
+        return A.Upscale2Fn.apply(x, 1.0)
+    _fp32_plain(x, 'upscale')
+    return A.ResizeNearestFn.apply(x, int(x.shape[1]) * int(s), int(x.shape[2]) * int(s))
+
+
+def downscale(x, s=2):
+    """reference utils/ops.py:114-116: nearest-neighbour resize to (h // s, w // s), NHWC."""
+    if int(s) != s or s < 1:
+        raise ValueError('downscale: s must be an integer >= 1, got %r' % (s,))
+    _fp32_plain(x, 'downscale')
+    Ho, Wo = int(x.shape[1]) // int(s), int(x.shape[2]) // int(s)
+    if Ho < 1 or Wo < 1:
+        raise ValueError('downscale: a %dx%d map scaled down by %d is empty' % (x.shape[1], x.shape[2], s))
+    return A.ResizeNearestFn.apply(x, Ho, Wo)
+
+
+def gn(x, mag):
+    """reference utils/ops.py:145-148: x * m^n with m = 1 + 0.2 * max(0, mag - 0.5)^2 and n ~ N(0, 1) drawn per element (the
+    multiplicative critic noise of the PGGAN paper).  mag is a Python float or a 0-d tensor that is READ ON THE HOST: no gradient
+    flows to mag.  One launch; the draw is keyed by — and advances — the device's torch generator (torch.cuda.manual_seed makes it
+    reproducible).  mag <= 0.5 returns x bit for bit.  Differentiable in x to any order.  Raises RuntimeError under graph capture:
+    the host-side seed and offset would be baked into the graph and every replay would draw the same noise."""
+    _fp32_plain(x, 'gn', rank=None)
+    if x.is_cuda and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError('gn: cannot be captured into a graph (its Philox seed and offset are host values: every replay would repeat the noise)')
+    mag = float(mag.item()) if isinstance(mag, torch.Tensor) else float(mag)
+    m = 1.0 + 0.2 * max(0.0, mag - 0.5) ** 2
+    return A.GnFn.apply(x, math.log(m))
 
 
 def lerp(a, b, t):

@@ -1,0 +1,96 @@
+#!/usr/bin/env python
+"""The memory-bound kernels of csrc/t2i_ops.hip (pixel_norm, nearest resize and its adjoint, pool AVG / MAX with their backward maps,
+gn) at PGGAN-sized tensors: one JSON line per kernel with the time per call, the bytes the algorithm moves (reads + writes, from the
+shapes), bytes per second, and the ratio of that rate to a device-to-device copy that moves the SAME number of bytes (half read, half
+written), timed in the same process.  Per measurement: 10 warm-up launches, then REPS rounds of 100 back-to-back launches between
+device events, kernel and copy rounds alternating; the median round is reported.  Read the ratio, not the absolute rate, as the share
+of what the memory system gives: a kernel and its copy touch the same number of bytes, so they sit in the same cache regime.  The
+regime differs BETWEEN lines, though, and each line says which it is in: 'working_set_MB' is what one call touches and
+'in_infinity_cache' whether that fits the 256 MiB Infinity Cache with room to spare (at most half of it).  Most lines do (a 34 MB
+tensor and its results: repeated calls are served from the cache, kernel and copy alike); the x2 upscale and its adjoint touch 168 MB
+per call, their copy likewise, and run at the rate of HBM.  Ratios are comparable within a regime, not across the two.
+
+    python tools/bench_ops.py [--reps 5] [--iters 100]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+import t2i_amd  # noqa: E402,F401
+from t2i_amd import kernels as K  # noqa: E402
+
+
+INFINITY_CACHE = 256 << 20
+
+
+def _round(fn, iters):
+    s, e = torch.cuda.Event(True), torch.cuda.Event(True)
+    s.record()
+    for _ in range(iters):
+        fn()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / iters * 1e-3
+
+
+def measure(name, shape, nbytes, fn, reps, iters):
+    src = torch.empty(nbytes // 8, dtype=torch.float32, device='cuda').normal_()
+    dst = torch.empty_like(src)
+    copy = lambda: dst.copy_(src)          # moves nbytes: nbytes / 2 read + nbytes / 2 written
+    for _ in range(10):
+        fn(); copy()
+    torch.cuda.synchronize()
+    tk, tc = [], []
+    for _ in range(reps):
+        tk.append(_round(fn, iters))
+        tc.append(_round(copy, iters))
+    t, c = statistics.median(tk), statistics.median(tc)
+    print(json.dumps({'kernel': name, 'shape': list(shape), 'us_per_call': round(t * 1e6, 2), 'bytes': nbytes,
+                      'working_set_MB': round(nbytes / 1e6, 1), 'in_infinity_cache': nbytes <= INFINITY_CACHE // 2,
+                      'GB_per_s': round(nbytes / t / 1e9, 1), 'copy_us': round(c * 1e6, 2), 'copy_GB_per_s': round(nbytes / c / 1e9, 1),
+                      'ratio_to_copy': round(c / t, 3), 'spread_us': [round(min(tk) * 1e6, 2), round(max(tk) * 1e6, 2)]}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--iters', type=int, default=100)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), 'bench_ops.py measures on the GPU; there is nothing to measure without one'
+    m = lambda name, shape, nbytes, fn: measure(name, shape, nbytes, fn, a.reps, a.iters)
+    for shape in ((8, 128, 128, 64), (64, 16, 16, 512)):
+        B, H, W, C = shape
+        x = torch.randn(shape, device='cuda')
+        g = torch.randn(shape, device='cuda')
+        n = x.numel()
+        rows = n // C
+        y, rn = K.pixel_norm_fwd(x, 1e-8, K.ACT_LRELU, 0.2)
+        m('pixel_norm_fwd lrelu (r + w + rnorm)', shape, 8 * n + 4 * rows, lambda: K.pixel_norm_fwd(x, 1e-8, K.ACT_LRELU, 0.2))
+        m('pixel_norm_bwd lrelu (2r + rnorm + w)', shape, 12 * n + 4 * rows, lambda: K.pixel_norm_bwd(g, y, rn, K.ACT_LRELU, 0.2))
+        up = K.resize_nearest(x, 2 * H, 2 * W)
+        m('resize_nearest x2 up (r + 4w)', shape, 20 * n, lambda: K.resize_nearest(x, 2 * H, 2 * W))
+        m('resize_nearest_adj of x2 up (4r + w)', shape, 20 * n, lambda: K.resize_nearest_adj(up, H, W))
+        m('resize_nearest /2 down (r/4 + w/4)', shape, 2 * n, lambda: K.resize_nearest(x, H // 2, W // 2))
+        for op, nm in ((K.POOL_AVG, 'AVG'), (K.POOL_MAX, 'MAX')):
+            yo, idx = K.pool_same_fwd(x, 2, op, want_idx=True)
+            go = torch.randn_like(yo)
+            extra = n if op == K.POOL_MAX else 0          # the int32 offsets, n / 4 of them
+            m('pool_same_fwd %s s=2 (r + w/4%s)' % (nm, ' + idx/4' if extra else ''), shape, 5 * n + extra,
+              lambda: K.pool_same_fwd(x, 2, op, want_idx=True))
+            m('pool_same_bwd %s s=2 (r/4%s + w)' % (nm, ' + idx/4' if extra else ''), shape, 5 * n + extra,
+              lambda: K.pool_same_bwd(go, idx, H, W, 2, op))
+            if op == K.POOL_MAX:
+                m('pool_same_take s=2 (r/4 + idx/4 + w/4)', shape, 3 * n, lambda: K.pool_same_take(x, idx, 2))
+        yo3, _ = K.pool_same_fwd(x, 3, K.POOL_AVG)
+        m('pool_same_fwd AVG s=3, padded (r + w/9)', shape, 4 * n + 4 * yo3.numel(), lambda: K.pool_same_fwd(x, 3, K.POOL_AVG))
+        _, f = K.gn_fwd(x, 0.18)
+        m('gn_fwd (r + 2w)', shape, 12 * n, lambda: K.gn_fwd(x, 0.18))
+        m('mul, the gn backward (2r + w)', shape, 12 * n, lambda: K.mul(g, f))
+
+
+if __name__ == '__main__':
+    main()
