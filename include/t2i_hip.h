@@ -616,6 +616,26 @@ int t2i_pixel_norm_fwd(const float* x, int64_t rows, int32_t C, float eps, int a
  * points return T2I_ERR_INVALID for T2I_ACT_LRELU with alpha < 0.  One launch. */
 int t2i_pixel_norm_bwd(const float* g, const float* y, const float* rnorm, int64_t rows, int32_t C, int act, float alpha, float* dx,
                        t2i_stream_t stream);
+/* The double backward of pixel_norm: for the cotangent v of dx (t2i_pixel_norm_bwd) it writes dg = dL/dg and dxx = dL/dx of
+ * L = <v, dx>, from v, g, y and rnorm alone.  With d = act'(.) read from the sign of y, w = v d and the per-pixel means m_wy, m_gy, m_wg:
+ * dg = s (w - y m_wy), dxx = -s^2 (y m_wg + w m_gy + g m_wy - 3 y m_wy m_gy) d.  act: T2I_ACT_NONE, T2I_ACT_RELU or T2I_ACT_LRELU
+ * with alpha >= 0 (piecewise linear: no second-derivative term); T2I_ACT_TANH and a negative slope return T2I_ERR_INVALID.
+ * One launch, the lane-group scheme of the two kernels above. */
+int t2i_pixel_norm_bwd2(const float* v, const float* g, const float* y, const float* rnorm, int64_t rows, int32_t C, int act, float alpha,
+                        float* dg, float* dx, t2i_stream_t stream);
+/* The double backward of layer_norm (per sample over per_sample elements, per-channel gamma over the last axis of C channels;
+ * xhat and rstd as the forward left them, y = the activation's output or NULL for T2I_ACT_NONE, act as for t2i_pixel_norm_bwd2).
+ * With g = gamma_c gy act'(.):  _sums writes sums [B,5] = per-sample (sum v, sum v xhat, sum g, sum g xhat, sum v g), each sample
+ * split over up to 256 workgroups and finished in a fixed order (workspace: t2i_layer_norm_bwd2_workspace_bytes(B); two launches);
+ * _apply reads the same tensors plus rstd and sums and writes dgy = dL/dgy and dx = dL/dx of L = <v, dx_first_order> in one launch,
+ * and, if hgz is not NULL, hgz = (dL/dg) gy act'(.), whose column sums (t2i_col_reduce) are dL/dgamma.  B <= 65535. */
+size_t t2i_layer_norm_bwd2_workspace_bytes(int32_t B);
+int t2i_layer_norm_bwd2_sums(const float* v, const float* gy, const float* xhat, const float* y, const float* gamma, int32_t B,
+                             int64_t per_sample, int32_t C, int act, float alpha, float* sums, void* ws, size_t ws_bytes,
+                             t2i_stream_t stream);
+int t2i_layer_norm_bwd2_apply(const float* v, const float* gy, const float* xhat, const float* y, const float* gamma, const float* rstd,
+                              const float* sums, int32_t B, int64_t per_sample, int32_t C, int act, float alpha, float* dgy, float* dx,
+                              float* hgz, t2i_stream_t stream);
 /* tf.image.resize_nearest_neighbor(align_corners = False): y[b,r,q,:] = x[b, src_h(r), src_w(q), :] with
  * src_h(r) = min(int(floorf(r * hs)), H - 1), hs = float(H) / float(Ho) in fp32, columns alike.  x [B,H,W,C] -> y [B,Ho,Wo,C]. */
 int t2i_resize_nearest(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t Ho, int32_t Wo, float* y, t2i_stream_t stream);

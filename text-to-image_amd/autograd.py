@@ -2,8 +2,9 @@
 
 The critic's gradient penalty (reference models/wgancls/model.py:62-70) differentiates through a gradient, so every
 Function on the critic path has a backward that is itself composed of Functions (conv <-> conv^T <-> filter-gradient
-form a closed family: the double backward needs no new kernel type).  Generator-only ops (batch norm, tanh, slope
-norm) are first-order (``once_differentiable``), exactly what the reference's two optimizers need.
+form a closed family: the double backward needs no new kernel type; layer norm and pixel norm carry a double-backward kernel
+of their own).  Generator-only ops (batch norm, tanh, slope norm) are first-order (``once_differentiable``), exactly what the
+reference's two optimizers need.
 
 ``input_grads_only()`` marks the first-order pass of the gradient penalty (tf.gradients(y, [x]) at model.py:63,68):
 there only d/d(input) is wanted, so filter / bias gradients are not launched.
@@ -629,10 +630,12 @@ class AxpbyFn(Function):
 class LayerNormFn(Function):
     """tf.contrib.layers.layer_norm(x, begin_norm_axis=1, begin_params_axis=-1) + activation (reference utils/ops.py:74-81):
     each sample is normalised over all of its elements (biased variance, eps = 1e-12), then scaled and shifted per
-    last-axis channel.  Generator only in the reference (models/pggan/pggan.py:289-309) => first order."""
+    last-axis channel.  The backward is LayerNormBwdFn, which has a backward of its own: usable in a critic under the gradient
+    penalty.  x itself is saved only as the graph handle through which d2L/dx reaches the input."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, act, alpha):
+        x_in = x
         x = _c(x)
         B = x.shape[0]
         n = x.numel() // B
@@ -642,22 +645,56 @@ class LayerNormFn(Function):
         rstd = torch.rsqrt(var + eps)
         xhat = K.row_fma2(x, rstd, delta=-mean * rstd)
         y = K.bn_apply(xhat, gamma, beta, act, alpha)               # per-channel affine + activation
-        ctx.save_for_backward(xhat, rstd, gamma, y if act != K.ACT_NONE else None)
+        ctx.save_for_backward(x_in, xhat, rstd, gamma, y if act != K.ACT_NONE else None)
         ctx.act, ctx.alpha, ctx.n = act, alpha, n
         return y
 
     @staticmethod
-    @once_differentiable
     def backward(ctx, gy):
-        xhat, rstd, gamma, y = ctx.saved_tensors
-        gy = _c(gy)
-        if ctx.act != K.ACT_NONE:
-            gy = K.act_bwd(gy, y, ctx.act, ctx.alpha)
-        dbeta, dgamma = K.col_reduce(gy, xhat, True)                  # sum gy, sum gy * xhat over rows of [*, C]
-        g = K.bn_apply(gy, gamma, torch.zeros_like(gamma), K.ACT_NONE, 0.0)
-        t1, t2 = K.row_moments(g, xhat)
-        dx = K.row_fma2(g, rstd, xhat, -rstd * t2 / ctx.n, -rstd * t1 / ctx.n)
+        x, xhat, rstd, gamma, y = ctx.saved_tensors
+        dx, dgamma, dbeta = LayerNormBwdFn.apply(gy, x, gamma, xhat, rstd, y.detach() if y is not None else None, ctx.act, ctx.alpha, ctx.n,
+                                                 not _INPUTS_ONLY[0])
         return dx, dgamma, dbeta, None, None, None
+
+
+class LayerNormBwdFn(Function):
+    """(dx, dgamma, dbeta) of LayerNormFn from gy; x is only the handle that carries this Function's own gradient to the forward's
+    input (xhat and rstd are kernel outputs without a graph).  want_params = False (the first-order pass of the gradient penalty,
+    input_grads_only): the dgamma / dbeta column reductions are not launched and None is returned for them.
+    backward = the double backward, for the cotangent v of dx: the five per-sample sums (two launches), one elementwise launch that
+    writes dL/dgy and dL/dx, and the column reduction for dL/dgamma when gamma asks for it.  The penalty differentiates a gradient
+    once => once_differentiable; cotangents for dgamma / dbeta (the gradient of a parameter gradient) are refused."""
+
+    @staticmethod
+    def forward(ctx, gy, x, gamma, xhat, rstd, y, act, alpha, n, want_params):
+        gy = _c(gy)
+        gz = K.act_bwd(gy, y, act, alpha) if act != K.ACT_NONE else gy
+        dbeta = dgamma = None
+        if want_params:
+            dbeta, dgamma = K.col_reduce(gz, xhat, True)                # sum gz, sum gz * xhat over rows of [*, C]
+        g = K.bn_apply(gz, gamma, torch.zeros_like(gamma), K.ACT_NONE, 0.0)
+        t1, t2 = K.row_moments(g, xhat)
+        dx = K.row_fma2(g, rstd, xhat, -rstd * t2 / n, -rstd * t1 / n)
+        ctx.save_for_backward(gy, xhat, rstd, gamma, y)
+        ctx.act, ctx.alpha = act, alpha
+        ctx.set_materialize_grads(False)
+        return dx, dgamma, dbeta
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, v, v_dgamma, v_dbeta):
+        if v_dgamma is not None or v_dbeta is not None:
+            raise NotImplementedError('layer_norm: the gradient of a parameter gradient (dgamma / dbeta) is not implemented; the second '
+                                      'order covers the input gradient dx, which is what a gradient penalty differentiates')
+        if v is None:
+            return (None,) * 10
+        if ctx.act == K.ACT_TANH:
+            raise NotImplementedError('layer_norm: second order through a fused tanh is not implemented (lrelu, relu or no activation)')
+        gy, xhat, rstd, gamma, y = ctx.saved_tensors
+        want_gamma = ctx.needs_input_grad[2]
+        dgy, dx, hgz = K.layer_norm_bwd2(_c(v), gy, xhat, y, gamma, rstd, ctx.act, ctx.alpha, want_hgz=want_gamma)
+        dgamma = K.col_reduce(hgz)[0] if want_gamma else None
+        return (dgy if ctx.needs_input_grad[0] else None, dx if ctx.needs_input_grad[1] else None, dgamma) + (None,) * 7
 
 
 class CaSampleKlFn(Function):
@@ -707,24 +744,47 @@ class LerpDevFn(Function):
 # ---- the rest of the operator surface (reference utils/ops.py:94-116,145-148) ---------------------------------------------
 class PixelNormFn(Function):
     """y = u / sqrt(mean_c(u^2) + eps), u = act(x), over the last axis (reference utils/ops.py:94-97): one launch forward, one backward.
-    The backward works from y and the saved per-pixel 1 / norm alone (u = y * norm), so x is not kept.  A generator-side operator in
-    the PGGAN paper, as LayerNormFn is here => first order."""
+    The backward (PixelNormBwdFn) works from y and the saved per-pixel 1 / norm alone (u = y * norm) and has a backward of its own: usable
+    in a critic under the gradient penalty.  x is saved only as the graph handle for d2L/dx."""
 
     @staticmethod
     def forward(ctx, x, eps, act, alpha):
         y, rnorm = K.pixel_norm_fwd(x, eps, act, alpha)
-        ctx.save_for_backward(y, rnorm)
+        ctx.save_for_backward(x, y, rnorm)
         ctx.act, ctx.alpha = act, alpha
         ctx.set_materialize_grads(False)
         return y
 
     @staticmethod
-    @once_differentiable
     def backward(ctx, gy):
         if gy is None:
             return None, None, None, None
-        y, rnorm = ctx.saved_tensors
-        return K.pixel_norm_bwd(_c(gy), y, rnorm, ctx.act, ctx.alpha), None, None, None
+        x, y, rnorm = ctx.saved_tensors
+        return PixelNormBwdFn.apply(gy, x, y.detach(), rnorm, ctx.act, ctx.alpha), None, None, None
+
+
+class PixelNormBwdFn(Function):
+    """dx of PixelNormFn from gy (one launch); x is only the handle that carries this Function's own gradient to the forward's input.
+    backward = the double backward, one launch: dL/dgy and dL/dx for the cotangent v of dx, from v, gy, y and rnorm."""
+
+    @staticmethod
+    def forward(ctx, gy, x, y, rnorm, act, alpha):
+        gy = _c(gy)
+        ctx.save_for_backward(gy, y, rnorm)
+        ctx.act, ctx.alpha = act, alpha
+        ctx.set_materialize_grads(False)
+        return K.pixel_norm_bwd(gy, y, rnorm, act, alpha)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, v):
+        if v is None:
+            return (None,) * 6
+        if ctx.act == K.ACT_TANH:
+            raise NotImplementedError('pixel_norm: second order through a fused tanh is not implemented (lrelu, relu or no activation)')
+        gy, y, rnorm = ctx.saved_tensors
+        dgy, dx = K.pixel_norm_bwd2(_c(v), gy, y, rnorm, ctx.act, ctx.alpha)
+        return (dgy if ctx.needs_input_grad[0] else None, dx if ctx.needs_input_grad[1] else None) + (None,) * 4
 
 
 class ResizeNearestFn(Function):

@@ -1,6 +1,7 @@
 // t2i_ops.hip — the rest of the reference's operator surface (reference utils/ops.py:94-116,145-148): pixel_norm, nearest-neighbour
 // resize (upscale / downscale by any factor) and its adjoint, tf.nn.pool with window = stride = s under SAME padding (AVG / MAX, any
-// extents) with its backward and second-order maps, and the multiplicative noise gn.  All of them are memory-bound single passes:
+// extents) with its backward and second-order maps, the multiplicative noise gn, and the double backward of pixel_norm and layer_norm
+// (normalised critics under the gradient penalty).  All of them are memory-bound single passes:
 // 16-byte accesses where C % 4 == 0 and the tensors are 16-byte aligned, a scalar form for any other C (C = 3 and C = 9 occur); no
 // atomics anywhere, every sum has a fixed order, so results repeat bit for bit.  The entry points (declared in include/t2i_hip.h)
 // are at the end of this file: they validate, pick the form and enqueue on the caller's stream — no allocation, no synchronisation.
@@ -205,6 +206,220 @@ inline int group_lanes(int units) {
   int G = 1;
   while (G < units && G < 64) G <<= 1;
   return G;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Second order of the two normalisations: the derivatives of L = <v, dx> for the cotangent v of a first-order
+// input gradient dx.  lrelu / relu are piecewise linear, so only their slope d = act'(.) enters, read from the sign of the output
+// like everywhere else; tanh has a second derivative of its own and is refused by the entry points.
+// ---------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float act_slope(float yv, int act, float alpha) {
+  return (act == T2I_ACT_NONE || yv > 0.f) ? 1.f : (act == T2I_ACT_LRELU ? alpha : 0.f);
+}
+
+// pixel_norm: dx = s (g - y mean_c(g y)) d.  With w = v d and the per-pixel means m_wy, m_gy, m_wg:
+//   dL/dg = s (w - y m_wy),   dL/dx = -s^2 (y m_wg + w m_gy + g m_wy - 3 y m_wy m_gy) d.
+// Same lane-group scheme as the first-order pair; three tensors stay in registers for rows of up to 2048 floats.  The register arrays
+// are sized by the row (PER units per lane and tensor): with the full kPer = 8 the 16-byte form needs 134 VGPRs (3 waves per SIMD), and
+// the rows a critic has (C <= 512: at most 2 units per lane) would pay for registers they never fill.
+template <typename T, int PER>       // PER: units a lane keeps in registers (1, 2, 4 or kPer); 0: the row is read twice
+__global__ __launch_bounds__(kThreads) void pixel_norm_bwd2_kernel(const T* __restrict__ v, const T* __restrict__ g, const T* __restrict__ y,
+                                                                    const float* __restrict__ rnorm, long long R, int units, int C, int G,
+                                                                    int act, float alpha, T* __restrict__ dg, T* __restrict__ dx) {
+  const int lane = threadIdx.x & (G - 1);
+  const long long row = (long long)blockIdx.x * (kThreads / G) + threadIdx.x / G;
+  const bool live = row < R;
+  const size_t base = (size_t)(live ? row : 0) * units;
+  const T* vr = v + base;
+  const T* gr = g + base;
+  const T* yr = y + base;
+  constexpr bool IN_REG = PER > 0;
+  constexpr int NK = PER > 0 ? PER : 1;
+  T wv[NK], gv[NK], yv[NK];
+  float swy = 0.f, sgy = 0.f, swg = 0.f;
+  if (IN_REG) {
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+      const int j = lane + k * G;
+      if (live && j < units) {
+        T a = vr[j];
+        gv[k] = gr[j];
+        yv[k] = yr[j];
+#pragma unroll
+        for (int e = 0; e < Lanes<T>::N; ++e) {
+          const float yy = Lanes<T>::get(yv[k], e), gg = Lanes<T>::get(gv[k], e);
+          const float w = Lanes<T>::get(a, e) * act_slope(yy, act, alpha);
+          Lanes<T>::set(a, e, w);
+          swy += w * yy; sgy += gg * yy; swg += w * gg;
+        }
+        wv[k] = a;
+      }
+    }
+  } else {
+    for (int j = lane; live && j < units; j += G) {
+      const T a = vr[j], b = gr[j], c = yr[j];
+#pragma unroll
+      for (int e = 0; e < Lanes<T>::N; ++e) {
+        const float yy = Lanes<T>::get(c, e), gg = Lanes<T>::get(b, e);
+        const float w = Lanes<T>::get(a, e) * act_slope(yy, act, alpha);
+        swy += w * yy; sgy += gg * yy; swg += w * gg;
+      }
+    }
+  }
+  swy = group_sum(swy, G); sgy = group_sum(sgy, G); swg = group_sum(swg, G);
+  if (!live) return;
+  const float m_wy = swy / (float)C, m_gy = sgy / (float)C, m_wg = swg / (float)C;
+  const float s = rnorm[row];
+  const float ns2 = -s * s, m3 = 3.f * m_wy * m_gy;
+  T* dgr = dg + base;
+  T* dxr = dx + base;
+  if (IN_REG) {
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+      const int j = lane + k * G;
+      if (j < units) {
+        T o, p;
+#pragma unroll
+        for (int e = 0; e < Lanes<T>::N; ++e) {
+          const float yy = Lanes<T>::get(yv[k], e), gg = Lanes<T>::get(gv[k], e), w = Lanes<T>::get(wv[k], e);
+          Lanes<T>::set(o, e, s * (w - yy * m_wy));
+          Lanes<T>::set(p, e, ns2 * (yy * m_wg + w * m_gy + gg * m_wy - yy * m3) * act_slope(yy, act, alpha));
+        }
+        dgr[j] = o;
+        dxr[j] = p;
+      }
+    }
+  } else {
+    for (int j = lane; j < units; j += G) {
+      const T a = vr[j], b = gr[j], c = yr[j];
+      T o, p;
+#pragma unroll
+      for (int e = 0; e < Lanes<T>::N; ++e) {
+        const float yy = Lanes<T>::get(c, e), gg = Lanes<T>::get(b, e);
+        const float d = act_slope(yy, act, alpha), w = Lanes<T>::get(a, e) * d;
+        Lanes<T>::set(o, e, s * (w - yy * m_wy));
+        Lanes<T>::set(p, e, ns2 * (yy * m_wg + w * m_gy + gg * m_wy - yy * m3) * d);
+      }
+      dgr[j] = o;
+      dxr[j] = p;
+    }
+  }
+}
+
+// layer_norm: per sample of n elements, xhat = (x - mu) r, g = gamma_c gz, gz = gy d, dx = r (g - mean(g) - xhat mean(g xhat)).
+// Five per-sample sums S = (sum v, sum v xhat, sum g, sum g xhat, sum v g) give everything (means m_* = S_* / n):
+//   hg = dL/dg = r (v - m_v - xhat m_vx),   dL/dgy = hg gamma_c d,   dL/dgamma_c = sum over rows of hg gz,
+//   q = -r (v m_gx + m_vx g),   dL/dx = r (q - mean(q) - xhat mean(q xhat)) - r^2 xhat (S_vg - m_g S_v - m_gx S_vx) / n
+//   with mean(q) = -r (m_gx m_v + m_vx m_g) and mean(q xhat) = -2 r m_gx m_vx.
+// A sample is a whole image (up to ~1 M floats at a handful of samples), so the sums are taken in two fixed-order levels like
+// row_moments (t2i_aux.hip): grid (chunks, B) partials of five floats (up to 256 chunks of at least 4096 floats), then one wave
+// per sample adds its chunks in a fixed order.
+// The channel of a row element is i % C: a multiply-high (FastDiv), not an integer division per element.
+constexpr int kLnChunksMax = 256;
+constexpr int kLnChunkFloats = 4096;        // a sample longer than this is split over several workgroups (16 floats per thread; at
+                                            // 16384 per workgroup and 64 chunks, 512 workgroups left the 256 CUs at 0.65 of a copy)
+constexpr int kLnSums = 5;
+
+struct LnSplit { int chunks; size_t per_chunk; };
+inline LnSplit ln_split(int64_t per, bool vec) {        // per, per_chunk in floats; per_chunk a multiple of 4 in the 16-byte form
+  int64_t c = (per + kLnChunkFloats - 1) / kLnChunkFloats;
+  if (c > kLnChunksMax) c = kLnChunksMax;
+  if (c < 1) c = 1;
+  size_t per_chunk = ((size_t)per + (size_t)c - 1) / (size_t)c;
+  if (vec) per_chunk = (per_chunk + 3) & ~(size_t)3;
+  LnSplit s;
+  s.per_chunk = per_chunk;
+  s.chunks = (int)(((size_t)per + per_chunk - 1) / per_chunk);
+  return s;
+}
+
+template <typename T>       // per, per_chunk, Cu counted in units of T
+__global__ __launch_bounds__(kThreads) void layer_norm_bwd2_sums_kernel(const T* __restrict__ v, const T* __restrict__ gy,
+                                                                         const T* __restrict__ xhat, const T* __restrict__ y,
+                                                                         const T* __restrict__ gamma, int per, int per_chunk, int Cu,
+                                                                         FastDiv div_c, int act, float alpha, float* __restrict__ part) {
+  __shared__ float red[kLnSums][kThreads / 64];
+  const int beg = blockIdx.x * per_chunk;
+  const int end = beg + per_chunk < per ? beg + per_chunk : per;
+  const size_t rb = (size_t)blockIdx.y * per;
+  float acc[kLnSums] = {0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+  for (int i = beg + threadIdx.x; i < end; i += kThreads) {
+    const int c = i - div_c.div(i) * Cu;
+    const T a = v[rb + i], b = gy[rb + i], x = xhat[rb + i], ga = gamma[c];
+    const T yy = y ? y[rb + i] : a;
+#pragma unroll
+    for (int e = 0; e < Lanes<T>::N; ++e) {
+      const float d = y ? act_slope(Lanes<T>::get(yy, e), act, alpha) : 1.f;
+      const float gg = Lanes<T>::get(ga, e) * (Lanes<T>::get(b, e) * d), vv = Lanes<T>::get(a, e), xx = Lanes<T>::get(x, e);
+      acc[0] += vv; acc[1] += vv * xx; acc[2] += gg; acc[3] += gg * xx; acc[4] += vv * gg;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < kLnSums; ++q) {
+    const float s = group_sum(acc[q], 64);
+    if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < kLnSums)
+    part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kLnSums + threadIdx.x] =
+        (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+}
+
+// one wave per sample: lane l adds the chunks l, l + 64, ... in order, then the butterfly joins the 64 lanes — a fixed order, and no
+// chain of up to 256 dependent loads (one thread per sum took 50 us over 256 chunks: each load waited for the one before it)
+__global__ __launch_bounds__(64) void layer_norm_bwd2_sums_stage2(const float* __restrict__ part, int chunks, float* __restrict__ sums) {
+  const int r = blockIdx.x;
+  float a[kLnSums] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int k = threadIdx.x; k < chunks; k += 64) {
+    const float* p = part + ((size_t)r * chunks + k) * kLnSums;
+#pragma unroll
+    for (int q = 0; q < kLnSums; ++q) a[q] += p[q];
+  }
+#pragma unroll
+  for (int q = 0; q < kLnSums; ++q) a[q] = group_sum(a[q], 64);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int q = 0; q < kLnSums; ++q) sums[(size_t)r * kLnSums + q] = a[q];
+  }
+}
+
+template <typename T>       // n, per, Cu counted in units of T; p may be NULL
+__global__ __launch_bounds__(kThreads) void layer_norm_bwd2_apply_kernel(const T* __restrict__ v, const T* __restrict__ gy,
+                                                                          const T* __restrict__ xhat, const T* __restrict__ y,
+                                                                          const T* __restrict__ gamma, const float* __restrict__ rstd,
+                                                                          const float* __restrict__ sums, int n, int per, int Cu,
+                                                                          FastDiv div_per, FastDiv div_c, float inv_n, int act, float alpha,
+                                                                          T* __restrict__ dgy, T* __restrict__ dx, T* __restrict__ p) {
+  for (size_t it = (size_t)blockIdx.x * kThreads + threadIdx.x; it < (size_t)n; it += (size_t)gridDim.x * kThreads) {
+    const int i = (int)it;
+    const int row = div_per.div(i);
+    const int j = i - row * per;
+    const int c = j - div_c.div(j) * Cu;
+    const float* S = sums + (size_t)row * kLnSums;
+    const float r = rstd[row];
+    const float m_v = S[0] * inv_n, m_vx = S[1] * inv_n, m_g = S[2] * inv_n, m_gx = S[3] * inv_n;
+    const float sva = (S[4] - m_g * S[0] - m_gx * S[1]) * inv_n;           // <v, a> / n,  a = g - m_g - xhat m_gx
+    const float mq = -r * (m_gx * m_v + m_vx * m_g), mqx = -2.f * r * m_gx * m_vx;
+    const float r2sva = r * r * sva;
+    const T a = v[i], b = gy[i], x = xhat[i], ga = gamma[c];
+    const T yy = y ? y[i] : a;
+    T o, w, z;
+#pragma unroll
+    for (int e = 0; e < Lanes<T>::N; ++e) {
+      const float d = y ? act_slope(Lanes<T>::get(yy, e), act, alpha) : 1.f;
+      const float gam = Lanes<T>::get(ga, e), gz = Lanes<T>::get(b, e) * d, gg = gam * gz;
+      const float vv = Lanes<T>::get(a, e), xx = Lanes<T>::get(x, e);
+      const float hg = r * (vv - m_v - xx * m_vx);
+      const float q = -r * (vv * m_gx + m_vx * gg);
+      Lanes<T>::set(o, e, hg * gam * d);
+      Lanes<T>::set(w, e, r * (q - mq - xx * mqx) - xx * r2sva);
+      Lanes<T>::set(z, e, hg * gz);
+    }
+    dgy[i] = o;
+    dx[i] = w;
+    if (p) p[i] = z;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -471,6 +686,104 @@ int t2i_pixel_norm_bwd(const float* g, const float* y, const float* rnorm, int64
   else { if (reg) T2I_PN(float, true); else T2I_PN(float, false); }
 #undef T2I_PN
   return launched("t2i_pixel_norm_bwd");
+}
+
+// second order: lrelu (slope >= 0) and relu only — tanh has a second derivative these kernels do not carry
+static bool act2_ok(int act, float alpha) { return act_ok(act, alpha) && act != T2I_ACT_TANH; }
+
+int t2i_pixel_norm_bwd2(const float* v, const float* g, const float* y, const float* rnorm, int64_t rows, int32_t C, int act, float alpha,
+                        float* dg, float* dx, t2i_stream_t stream) {
+  if (!v || !g || !y || !rnorm || !dg || !dx || rows <= 0 || C <= 0 || !act2_ok(act, alpha) || rows > kMaxElems / C) {
+    set_error("t2i_pixel_norm_bwd2: bad argument (rows=%lld C=%d act=%d alpha=%g; none, relu or an lrelu slope >= 0)", (long long)rows, C, act,
+              (double)alpha);
+    return T2I_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const bool v4 = (C & 3) == 0 && al16(v) && al16(g) && al16(y) && al16(dg) && al16(dx);
+  const int units = v4 ? C >> 2 : C;
+  const int G = group_lanes(units);
+  const int per_lane = (units + G - 1) / G;
+  const dim3 grid((unsigned)((rows + kThreads / G - 1) / (kThreads / G)));
+#define T2I_PN(TT, PP)                                                                                                                    \
+  hipLaunchKernelGGL((pixel_norm_bwd2_kernel<TT, PP>), grid, dim3(kThreads), 0, st, reinterpret_cast<const TT*>(v),                       \
+                     reinterpret_cast<const TT*>(g), reinterpret_cast<const TT*>(y), rnorm, (long long)rows, units, C, G, act, alpha,     \
+                     reinterpret_cast<TT*>(dg), reinterpret_cast<TT*>(dx))
+#define T2I_PN_PER(TT)                                                                                                                    \
+  do {                                                                                                                                    \
+    if (per_lane <= 1) T2I_PN(TT, 1); else if (per_lane <= 2) T2I_PN(TT, 2); else if (per_lane <= 4) T2I_PN(TT, 4);                       \
+    else if (per_lane <= kPer) T2I_PN(TT, kPer); else T2I_PN(TT, 0);                                                                      \
+  } while (0)
+  if (v4) T2I_PN_PER(float4); else T2I_PN_PER(float);
+#undef T2I_PN_PER
+#undef T2I_PN
+  return launched("t2i_pixel_norm_bwd2");
+}
+
+static bool ln2_args_ok(const void* v, const void* gy, const void* xhat, const void* y, const void* gamma, int32_t B, int64_t per, int32_t C,
+                        int act, float alpha) {
+  return v && gy && xhat && gamma && B > 0 && B <= 65535 && C > 0 && per > 0 && per % C == 0 && per <= kMaxElems / B && act2_ok(act, alpha) &&
+         (act == T2I_ACT_NONE || y);
+}
+
+size_t t2i_layer_norm_bwd2_workspace_bytes(int32_t B) { return B > 0 ? (size_t)B * kLnChunksMax * kLnSums * sizeof(float) : 0; }
+
+int t2i_layer_norm_bwd2_sums(const float* v, const float* gy, const float* xhat, const float* y, const float* gamma, int32_t B,
+                             int64_t per_sample, int32_t C, int act, float alpha, float* sums, void* ws, size_t ws_bytes,
+                             t2i_stream_t stream) {
+  if (!ln2_args_ok(v, gy, xhat, y, gamma, B, per_sample, C, act, alpha) || !sums) {
+    set_error("t2i_layer_norm_bwd2_sums: bad argument (B=%d per_sample=%lld C=%d act=%d alpha=%g)", B, (long long)per_sample, C, act, (double)alpha);
+    return T2I_ERR_INVALID;
+  }
+  if (!ws || ws_bytes < t2i_layer_norm_bwd2_workspace_bytes(B)) { set_error("t2i_layer_norm_bwd2_sums: workspace too small"); return T2I_ERR_WORKSPACE; }
+  hipStream_t st = (hipStream_t)stream;
+  if (act == T2I_ACT_NONE) y = nullptr;
+  const bool v4 = (C & 3) == 0 && al16(v) && al16(gy) && al16(xhat) && al16(y) && al16(gamma);
+  const LnSplit sp = ln_split(per_sample, v4);
+  float* part = reinterpret_cast<float*>(ws);
+  FastDiv div_c;
+  const dim3 grid((unsigned)sp.chunks, (unsigned)B);
+  if (v4) {
+    div_c.set((uint32_t)(C >> 2));
+    hipLaunchKernelGGL(layer_norm_bwd2_sums_kernel<float4>, grid, dim3(kThreads), 0, st, reinterpret_cast<const float4*>(v),
+                       reinterpret_cast<const float4*>(gy), reinterpret_cast<const float4*>(xhat), reinterpret_cast<const float4*>(y),
+                       reinterpret_cast<const float4*>(gamma), (int)(per_sample >> 2), (int)(sp.per_chunk >> 2), C >> 2, div_c, act, alpha, part);
+  } else {
+    div_c.set((uint32_t)C);
+    hipLaunchKernelGGL(layer_norm_bwd2_sums_kernel<float>, grid, dim3(kThreads), 0, st, v, gy, xhat, y, gamma, (int)per_sample,
+                       (int)sp.per_chunk, C, div_c, act, alpha, part);
+  }
+  hipLaunchKernelGGL(layer_norm_bwd2_sums_stage2, dim3((unsigned)B), dim3(64), 0, st, part, sp.chunks, sums);
+  return launched("t2i_layer_norm_bwd2_sums");
+}
+
+int t2i_layer_norm_bwd2_apply(const float* v, const float* gy, const float* xhat, const float* y, const float* gamma, const float* rstd,
+                              const float* sums, int32_t B, int64_t per_sample, int32_t C, int act, float alpha, float* dgy, float* dx,
+                              float* hgz, t2i_stream_t stream) {
+  if (!ln2_args_ok(v, gy, xhat, y, gamma, B, per_sample, C, act, alpha) || !rstd || !sums || !dgy || !dx) {
+    set_error("t2i_layer_norm_bwd2_apply: bad argument (B=%d per_sample=%lld C=%d act=%d alpha=%g)", B, (long long)per_sample, C, act, (double)alpha);
+    return T2I_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (act == T2I_ACT_NONE) y = nullptr;
+  const bool v4 = (C & 3) == 0 && al16(v) && al16(gy) && al16(xhat) && al16(y) && al16(gamma) && al16(dgy) && al16(dx) && al16(hgz);
+  const float inv_n = 1.0f / (float)per_sample;
+  FastDiv div_per, div_c;
+  if (v4) {
+    const size_t n = (size_t)B * (size_t)(per_sample >> 2);
+    div_per.set((uint32_t)(per_sample >> 2));
+    div_c.set((uint32_t)(C >> 2));
+    hipLaunchKernelGGL(layer_norm_bwd2_apply_kernel<float4>, dim3(blocks_for(n)), dim3(kThreads), 0, st, reinterpret_cast<const float4*>(v),
+                       reinterpret_cast<const float4*>(gy), reinterpret_cast<const float4*>(xhat), reinterpret_cast<const float4*>(y),
+                       reinterpret_cast<const float4*>(gamma), rstd, sums, (int)n, (int)(per_sample >> 2), C >> 2, div_per, div_c, inv_n, act,
+                       alpha, reinterpret_cast<float4*>(dgy), reinterpret_cast<float4*>(dx), reinterpret_cast<float4*>(hgz));
+  } else {
+    const size_t n = (size_t)B * (size_t)per_sample;
+    div_per.set((uint32_t)per_sample);
+    div_c.set((uint32_t)C);
+    hipLaunchKernelGGL(layer_norm_bwd2_apply_kernel<float>, dim3(blocks_for(n)), dim3(kThreads), 0, st, v, gy, xhat, y, gamma, rstd, sums, (int)n,
+                       (int)per_sample, C, div_per, div_c, inv_n, act, alpha, dgy, dx, hgz);
+  }
+  return launched("t2i_layer_norm_bwd2_apply");
 }
 
 static bool resize_args_ok(const void* a, const void* b, int32_t B, int32_t H, int32_t W, int32_t C, int32_t Ho, int32_t Wo) {

@@ -1720,6 +1720,63 @@ def pixel_norm_bwd(g, y, rnorm, act=ACT_NONE, alpha=0.2):
     return dx
 
 
+def pixel_norm_bwd2(v, g, y, rnorm, act=ACT_NONE, alpha=0.2):
+    """The double backward of pixel_norm: -> (dL/dg, dL/dx) of L = <v, pixel_norm_bwd(g, y, rnorm)>; one launch."""
+    for t, name in ((v, 'v'), (g, 'g'), (y, 'y'), (rnorm, 'rnorm')):
+        _chk(t, name, f32=True)
+    assert v.shape == y.shape and g.shape == y.shape
+    C = y.shape[-1]
+    rows = y.numel() // C
+    dg, dx = torch.empty_like(y), torch.empty_like(y)
+    if _live(y) and rows > 0:
+        check(lib.t2i_pixel_norm_bwd2(_ptr(v), _ptr(g), _ptr(y), _ptr(rnorm), rows, C, act, alpha, _ptr(dg), _ptr(dx), _stream()),
+              't2i_pixel_norm_bwd2')
+    return dg, dx
+
+
+def _ln2_args(v, gy, xhat, y, gamma):
+    for t, name in ((v, 'v'), (gy, 'gy'), (xhat, 'xhat'), (gamma, 'gamma')):
+        _chk(t, name, f32=True)
+    if y is not None:
+        _chk(y, 'y', f32=True)
+    assert v.shape == xhat.shape and gy.shape == xhat.shape and (y is None or y.shape == xhat.shape)
+    B, C = xhat.shape[0], xhat.shape[-1]
+    assert gamma.numel() == C
+    return B, xhat.numel() // B, C
+
+
+def layer_norm_bwd2_sums(v, gy, xhat, y, gamma, act=ACT_NONE, alpha=0.2):
+    """-> [B, 5] per-sample (sum v, sum v xhat, sum g, sum g xhat, sum v g), g = gamma_c gy act'(.): partials over up to 256 workgroups
+    per sample, then their fixed-order sum (two launches)."""
+    B, per, C = _ln2_args(v, gy, xhat, y, gamma)
+    sums = torch.empty((B, 5), dtype=torch.float32, device=xhat.device)
+    if _live(xhat) and xhat.numel() > 0:
+        wsp, wsn = _ws_args(xhat, int(lib.t2i_layer_norm_bwd2_workspace_bytes(B)))
+        check(lib.t2i_layer_norm_bwd2_sums(_ptr(v), _ptr(gy), _ptr(xhat), _ptr(y), _ptr(gamma), B, per, C, act, alpha, _ptr(sums), wsp, wsn,
+                                           _stream()), 't2i_layer_norm_bwd2_sums')
+    return sums
+
+
+def layer_norm_bwd2_apply(v, gy, xhat, y, gamma, rstd, sums, act=ACT_NONE, alpha=0.2, want_hgz=False):
+    """-> (dL/dgy, dL/dx, hgz or None) from the sums of layer_norm_bwd2_sums; one elementwise launch."""
+    B, per, C = _ln2_args(v, gy, xhat, y, gamma)
+    _chk(rstd, 'rstd', f32=True); _chk(sums, 'sums', f32=True)
+    assert rstd.numel() == B and sums.numel() == 5 * B
+    dgy, dx = torch.empty_like(xhat), torch.empty_like(xhat)
+    hgz = torch.empty_like(xhat) if want_hgz else None
+    if _live(xhat) and xhat.numel() > 0:
+        check(lib.t2i_layer_norm_bwd2_apply(_ptr(v), _ptr(gy), _ptr(xhat), _ptr(y), _ptr(gamma), _ptr(rstd), _ptr(sums), B, per, C, act, alpha,
+                                            _ptr(dgy), _ptr(dx), _ptr(hgz), _stream()), 't2i_layer_norm_bwd2_apply')
+    return dgy, dx, hgz
+
+
+def layer_norm_bwd2(v, gy, xhat, y, gamma, rstd, act=ACT_NONE, alpha=0.2, want_hgz=False):
+    """The double backward of layer_norm ([B, ..., C], normalised per sample, gamma [C]; y = the activation's output or None):
+    -> (dL/dgy, dL/dx, hgz or None) of L = <v, dx_first_order>; colsum(hgz) is dL/dgamma (col_reduce)."""
+    sums = layer_norm_bwd2_sums(v, gy, xhat, y, gamma, act, alpha)
+    return layer_norm_bwd2_apply(v, gy, xhat, y, gamma, rstd, sums, act, alpha, want_hgz)
+
+
 def resize_nearest(x, Ho, Wo):
     """x [B,H,W,C] -> [B,Ho,Wo,C], tf.image.resize_nearest_neighbor (align_corners=False)."""
     _chk(x, 'x', f32=True)

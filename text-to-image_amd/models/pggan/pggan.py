@@ -6,7 +6,8 @@ schedule in train_pggan.py:17-69: output size 4 * 2^(stage-1); with `trans` the 
 alpha = iter / steps next to the up-scaled previous `to_rgb` (generator) / the pooled-input `from_rgb` (critic).
 The losses reuse the hot path's WGAN-GP machinery (gradient penalty through a double-differentiable critic); new
 here: per-sample layer norm (generator only), 2x2 average pool and nearest x2 upscale (a pair of adjoint kernels, closed
-under differentiation — the critic is differentiated twice), the fade-in mix.  Reference specifics kept: penalty
+under differentiation — the critic is differentiated twice), the fade-in mix; `critic_norm='layer' | 'pixel'` (not in the
+reference; default None = the reference's critic) normalises the critic's 3x3 / 4x4 convolutions per sample.  Reference specifics kept: penalty
 coefficient 200, no kt term, G = -D_fake + 5 KL, Adam(2e-6, beta1=0, beta2=0.99) hard-coded (pggan.py:104-110; the
 `learning_rate` placeholder is fed but unused), eps of x_hat drawn in-graph (pggan.py:68 overrides the placeholder),
 `to_rgb` = k2 s1 SAME 9-channel relu conv + 1x1, every kernel He-initialised by utils/ops.py's defaults.
@@ -24,13 +25,16 @@ from ... import autograd as A
 from ... import kernels as K
 from ... import optim
 from ... import scope as S
-from ...utils.ops import concat_tile, conv2d, fc, layer_norm, lerp, lrelu_act, pool, relu, upscale
+from ...utils.ops import concat_tile, conv2d, fc, layer_norm, lerp, lrelu_act, pixel_norm, pool, relu, upscale
 
 
 class PGGAN(object):
     def __init__(self, batch_size, steps, check_dir_write, check_dir_read, dataset, sample_path, log_dir, stage, trans,
                  build_model=True, device=None, seed=0, store=None, fmap_base=1024, fmap_max=512, z_dim=128, embed_dim=1024,
-                 compr_embed_dim=128, dp=None):
+                 compr_embed_dim=128, dp=None, critic_norm=None):
+        if critic_norm not in (None, 'layer', 'pixel'):
+            raise ValueError("critic_norm must be None, 'layer' or 'pixel', got %r" % (critic_norm,))
+        self.critic_norm = critic_norm
         self.batch_size, self.steps = batch_size, steps
         self.check_dir_write, self.check_dir_read = check_dir_write, check_dir_read
         self.dataset, self.sample_path, self.log_dir = dataset, sample_path, log_dir
@@ -238,18 +242,27 @@ class PGGAN(object):
             x = self.from_rgb(inp, stages - 1)
             for i in range(stages - 1, 0, -1):
                 with S.variable_scope(self.get_conv_scope_name(i), reuse=reuse):
-                    x = conv2d(x, f=self.get_dnf(i), ks=(3, 3), s=(1, 1), act=act)
-                    x = conv2d(x, f=self.get_dnf(i - 1), ks=(3, 3), s=(1, 1), act=act)
+                    x = self._d_conv(x, self.get_dnf(i), (3, 3), 'SAME', act)
+                    x = self._d_conv(x, self.get_dnf(i - 1), (3, 3), 'SAME', act)
                     x = pool(x, 2)
                 if i == stages - 1 and t:
                     x = lerp(x_iden, x, alpha_trans)              # alpha * x + (1 - alpha) * x_iden
             with S.variable_scope(self.get_conv_scope_name(0), reuse=reuse):
                 cond_compress = fc(cond, units=self.compr_embed_dim, act=act)
                 concat = self.concat_cond4(x, cond_compress)
-                x_b1 = conv2d(concat, f=self.get_dnf(0), ks=(3, 3), s=(1, 1), act=act)
-                x_b1 = conv2d(x_b1, f=self.get_dnf(0), ks=(4, 4), s=(1, 1), padding='VALID', act=act)
+                x_b1 = self._d_conv(concat, self.get_dnf(0), (3, 3), 'SAME', act)
+                x_b1 = self._d_conv(x_b1, self.get_dnf(0), (4, 4), 'VALID', act)
                 output_b1 = fc(x_b1.reshape(x_b1.shape[0], -1), units=1)      # dense on the [B,1,1,C] map
             return output_b1.reshape(-1)
+
+    def _d_conv(self, x, f, ks, padding, act):
+        """A 3x3 / 4x4 convolution of the critic.  critic_norm = None: conv + lrelu (the reference).  'layer' / 'pixel': the conv
+        without activation, then the per-sample normalisation with the lrelu fused — the normalised critic of the WGAN-GP and PGGAN
+        papers (batch norm would couple the samples under the per-sample penalty); both are differentiable twice."""
+        if self.critic_norm is None:
+            return conv2d(x, f=f, ks=ks, s=(1, 1), padding=padding, act=act)
+        x = conv2d(x, f=f, ks=ks, s=(1, 1), padding=padding, act=None)
+        return layer_norm(x, act=act) if self.critic_norm == 'layer' else pixel_norm(x, act=act)
 
     def generator(self, z_var, cond_inp, stages, t, reuse=False, cond_noise=True):
         """-> (image NHWC, mean, log_sigma)  (pggan.py:283-316)"""

@@ -91,6 +91,8 @@ def main(argv=None):
     ap.add_argument('--first', type=int, default=0, help='index into the 15-entry schedule to start from')
     ap.add_argument('--last', type=int, default=len(STAGE) - 1)
     ap.add_argument('--math', choices=['f32', 'bf16'], default='f32')
+    ap.add_argument('--critic-norm', choices=['layer', 'pixel'], default=None,
+                    help="normalise the critic's 3x3 / 4x4 convolutions per sample (default: the reference's un-normalised critic)")
     ap.add_argument('--eager', action='store_true', help='--bench: keep eager launches instead of hipGraph replay')
     ap.add_argument('--bench', action='store_true', help='time `--iters` iterations of each entry instead of training with side effects')
     args = ap.parse_args(argv)
@@ -126,7 +128,7 @@ def main(argv=None):
         size = 4 * 2 ** (STAGE[i] - 1)
         pggan = PGGAN(batch_size=batch_size, steps=max_iters, check_dir_write=wdir, check_dir_read=rdir,
                       dataset=dataset_for(size, dev) if cfg is None else real_dataset(cfg, STAGE[i], dev), sample_path=sample_path,
-                      log_dir=logs_dir, stage=STAGE[i], trans=t, device=dev)
+                      log_dir=logs_dir, stage=STAGE[i], trans=t, device=dev, critic_norm=args.critic_norm)
         if args.bench:
             gen = torch.Generator(device=dev).manual_seed(0)
             feed = pggan.make_feed(gen)

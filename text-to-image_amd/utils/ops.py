@@ -15,6 +15,8 @@ Every public name of the reference's utils/ops.py exists here with its signature
     extents), ``gn`` and ``batch_renorm`` take fp32 tensors only: a bf16 tensor (bf16 storage) is refused with ValueError and a
     stacked pass (``stacked.Stacked``) with NotImplementedError, both before any launch and naming the operator;
   * ``batch_renorm`` and ``gn`` restate TF 1.4 as read from its sources; like the rest of the oracle they are not pinned against TF.
+``layer_norm`` and ``pixel_norm`` are differentiable twice (the per-sample normalisations of a critic under the gradient penalty),
+like ``pool``, ``resize_nearest_neighbor``, ``gn``, ``lerp``, ``add`` and the convolutions; ``batch_norm`` / ``batch_renorm`` are first order.
 """
 import math
 
@@ -300,7 +302,9 @@ def batch_renorm(x, train, init=None, act=None, name=None, eps=1e-5, decay=0.9, 
 
 def layer_norm(x, act=None, scope=None, df=NHWC):
     """reference utils/ops.py:74-81 (tf.contrib.layers.layer_norm, begin_params_axis = channel axis).  Rank-4 NHWC or
-    rank-2.  Variables: <scope>/LayerNorm[_k]/{beta [C] zeros, gamma [C] ones}."""
+    rank-2.  Variables: <scope>/LayerNorm[_k]/{beta [C] zeros, gamma [C] ones}.  Differentiable twice with respect to its input
+    (no activation, relu or lrelu; reaching the second order through a fused tanh raises NotImplementedError), so it may sit in a
+    critic under the gradient penalty; under autograd.input_grads_only() the first-order pass returns no gamma / beta gradients."""
     st = S.default_store()
     _check_df(df)
     if x.dim() == 4:
@@ -334,7 +338,8 @@ def pixel_norm(x, eps=1e-8, act=None):
     """reference utils/ops.py:94-97: u = act(x), then u / sqrt(mean(u^2, axis=3) + eps) — the PGGAN paper's pixelwise feature
     normalisation.  Rank 4, normalised over axis 3 of the tensor as given, which must be contiguous (a logical NCHW view is not:
     pass to_nhwc(x)).  An ops.Activation is fused into the kernel; any other callable is applied first, unfused.  One launch forward,
-    one backward.  A generator-side operator, as layer_norm is: first order only (not usable under the gradient penalty).
+    one backward, one for the backward of the backward: differentiable twice, so it may sit in a critic under the gradient penalty
+    (no activation, relu or lrelu; reaching the second order through a fused tanh raises NotImplementedError).
     The backward reads the derivative of lrelu / relu from the sign of y (as every Activation's backward in this package does), which
     is the sign of x only for a slope >= 0: an lrelu_act with a negative slope is refused with ValueError."""
     _fp32_plain(x, 'pixel_norm')

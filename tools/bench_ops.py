@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """The memory-bound kernels of csrc/t2i_ops.hip (pixel_norm, nearest resize and its adjoint, pool AVG / MAX with their backward maps,
-gn) at PGGAN-sized tensors: one JSON line per kernel with the time per call, the bytes the algorithm moves (reads + writes, from the
+gn, the double backward of pixel_norm and layer_norm) at PGGAN-sized tensors: one JSON line per kernel with the time per call, the bytes the algorithm moves (reads + writes, from the
 shapes), bytes per second, and the ratio of that rate to a device-to-device copy that moves the SAME number of bytes (half read, half
 written), timed in the same process.  Per measurement: 10 warm-up launches, then REPS rounds of 100 back-to-back launches between
 device events, kernel and copy rounds alternating; the median round is reported.  Read the ratio, not the absolute rate, as the share
@@ -10,7 +10,7 @@ regime differs BETWEEN lines, though, and each line says which it is in: 'workin
 tensor and its results: repeated calls are served from the cache, kernel and copy alike); the x2 upscale and its adjoint touch 168 MB
 per call, their copy likewise, and run at the rate of HBM.  Ratios are comparable within a regime, not across the two.
 
-    python tools/bench_ops.py [--reps 5] [--iters 100]
+    python tools/bench_ops.py [--reps 5] [--iters 100] [--only SUBSTRING]
 """
 import argparse
 import json
@@ -59,9 +59,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--iters', type=int, default=100)
+    ap.add_argument('--only', default='', help='measure only the kernels whose line name contains this')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'bench_ops.py measures on the GPU; there is nothing to measure without one'
-    m = lambda name, shape, nbytes, fn: measure(name, shape, nbytes, fn, a.reps, a.iters)
+    m = lambda name, shape, nbytes, fn: measure(name, shape, nbytes, fn, a.reps, a.iters) if a.only in name else None
     for shape in ((8, 128, 128, 64), (64, 16, 16, 512)):
         B, H, W, C = shape
         x = torch.randn(shape, device='cuda')
@@ -90,6 +91,19 @@ def main():
         _, f = K.gn_fwd(x, 0.18)
         m('gn_fwd (r + 2w)', shape, 12 * n, lambda: K.gn_fwd(x, 0.18))
         m('mul, the gn backward (2r + w)', shape, 12 * n, lambda: K.mul(g, f))
+        # second order of the two normalisations: v = the cotangent of the first-order input gradient
+        v = torch.randn(shape, device='cuda')
+        m('pixel_norm_bwd2 lrelu (3r + rnorm + 2w)', shape, 20 * n + 4 * rows, lambda: K.pixel_norm_bwd2(v, g, y, rn, K.ACT_LRELU, 0.2))
+        gamma = torch.rand(C, device='cuda') + 0.5
+        xhat = K.row_fma2(x, torch.ones(B, device='cuda'))                 # any [B, per] tensor serves as xhat for the timing
+        yl = K.bn_apply(xhat, gamma, torch.zeros_like(gamma), K.ACT_LRELU, 0.2)
+        rstd = torch.rand(B, device='cuda') + 0.5
+        sums = K.layer_norm_bwd2_sums(v, g, xhat, yl, gamma, K.ACT_LRELU, 0.2)
+        m('layer_norm_bwd2_sums lrelu (4r)', shape, 16 * n, lambda: K.layer_norm_bwd2_sums(v, g, xhat, yl, gamma, K.ACT_LRELU, 0.2))
+        m('layer_norm_bwd2_apply lrelu (4r + 2w)', shape, 24 * n,
+          lambda: K.layer_norm_bwd2_apply(v, g, xhat, yl, gamma, rstd, sums, K.ACT_LRELU, 0.2))
+        m('layer_norm_bwd2_apply lrelu + hgz for dgamma (4r + 3w)', shape, 28 * n,
+          lambda: K.layer_norm_bwd2_apply(v, g, xhat, yl, gamma, rstd, sums, K.ACT_LRELU, 0.2, want_hgz=True))
 
 
 if __name__ == '__main__':
