@@ -636,6 +636,24 @@ int t2i_layer_norm_bwd2_sums(const float* v, const float* gy, const float* xhat,
 int t2i_layer_norm_bwd2_apply(const float* v, const float* gy, const float* xhat, const float* y, const float* gamma, const float* rstd,
                               const float* sums, int32_t B, int64_t per_sample, int32_t C, int act, float alpha, float* dgy, float* dx,
                               float* hgz, t2i_stream_t stream);
+/* Minibatch standard deviation (the critic layer of the progressive-growing paper) over x [B,H,W,C], fp32: sample n belongs to group
+ * n / G (contiguous rows), channel c to chunk c / (C/F).  Per column (h, w, c) of a group: mu = mean_g x, d_g = x_g - mu,
+ * sigma = sqrt(mean_g d_g^2 + eps) (biased, two passes over registers); stat [B,F]: row n, chunk f = the mean of sigma over the
+ * Nf = H W C/F columns of chunk f of group n / G.  _bwd: dx_g = k d_g / sigma with k = (sum of gs over the group's rows) / (Nf G).
+ * _bwd2, for the cotangent v of dx: dgs = dL/dgs = (1 / (Nf G)) sum_{g,j} v_g d_g / sigma (the same in every row of a group) and
+ * dxx = dL/dx_g = k [(v_g - mean_g v) / sigma - d_g (sum_g v_g d_g) / (G sigma^3)].  G = 1: stat = sqrt(eps), dx = dxx = 0 exactly.
+ * 1 <= G <= 16 dividing B, F >= 1 dividing C, B / G and F <= 65535, eps > 0 (sigma is a divisor); anything else, a NULL pointer or a workspace smaller than
+ * t2i_minibatch_stddev_workspace_bytes (0 for a refused shape) returns T2I_ERR_INVALID before anything is launched.  A 16-byte form
+ * where (C/F) % 4 == 0 and the tensors are 16-byte aligned, a scalar form otherwise.  No atomics; a group's work is cut by the
+ * sample's shape alone, so the results for a batch are bit for bit those of its groups taken in separate calls.  _fwd and _bwd2
+ * are two launches (partials in the workspace, then their fixed-order sum), _bwd is one.  Added within ABI v13. */
+size_t t2i_minibatch_stddev_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C, int32_t G, int32_t F);
+int t2i_minibatch_stddev_fwd(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t G, int32_t F, float eps, float* stat,
+                             void* ws, size_t ws_bytes, t2i_stream_t stream);
+int t2i_minibatch_stddev_bwd(const float* gs, const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t G, int32_t F, float eps,
+                             float* dx, t2i_stream_t stream);
+int t2i_minibatch_stddev_bwd2(const float* v, const float* x, const float* gs, int32_t B, int32_t H, int32_t W, int32_t C, int32_t G,
+                              int32_t F, float eps, float* dxx, float* dgs, void* ws, size_t ws_bytes, t2i_stream_t stream);
 /* tf.image.resize_nearest_neighbor(align_corners = False): y[b,r,q,:] = x[b, src_h(r), src_w(q), :] with
  * src_h(r) = min(int(floorf(r * hs)), H - 1), hs = float(H) / float(Ho) in fp32, columns alike.  x [B,H,W,C] -> y [B,Ho,Wo,C]. */
 int t2i_resize_nearest(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t Ho, int32_t Wo, float* y, t2i_stream_t stream);

@@ -137,6 +137,10 @@ SIGNATURES = {
     't2i_layer_norm_bwd2_workspace_bytes': (_sz, [_i32]),
     't2i_layer_norm_bwd2_sums': (ctypes.c_int, [_p, _p, _p, _p, _p, _i32, _i64, _i32, ctypes.c_int, _f, _p, _p, _sz, _p]),
     't2i_layer_norm_bwd2_apply': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i32, _i64, _i32, ctypes.c_int, _f, _p, _p, _p, _p]),
+    't2i_minibatch_stddev_workspace_bytes': (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    't2i_minibatch_stddev_fwd': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _f, _p, _p, _sz, _p]),
+    't2i_minibatch_stddev_bwd': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _f, _p, _p]),
+    't2i_minibatch_stddev_bwd2': (ctypes.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _f, _p, _p, _p, _sz, _p]),
     't2i_resize_nearest': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p]),
     't2i_resize_nearest_adj': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p]),
     't2i_pool_same_fwd': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p]),

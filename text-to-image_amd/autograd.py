@@ -2,8 +2,8 @@
 
 The critic's gradient penalty (reference models/wgancls/model.py:62-70) differentiates through a gradient, so every
 Function on the critic path has a backward that is itself composed of Functions (conv <-> conv^T <-> filter-gradient
-form a closed family: the double backward needs no new kernel type; layer norm and pixel norm carry a double-backward kernel
-of their own).  Generator-only ops (batch norm, tanh, slope norm) are first-order (``once_differentiable``), exactly what the
+form a closed family: the double backward needs no new kernel type; layer norm, pixel norm and the minibatch standard deviation
+carry a double-backward kernel of their own).  Generator-only ops (batch norm, tanh, slope norm) are first-order (``once_differentiable``), exactly what the
 reference's two optimizers need.
 
 ``input_grads_only()`` marks the first-order pass of the gradient penalty (tf.gradients(y, [x]) at model.py:63,68):
@@ -785,6 +785,49 @@ class PixelNormBwdFn(Function):
         gy, y, rnorm = ctx.saved_tensors
         dgy, dx = K.pixel_norm_bwd2(_c(v), gy, y, rnorm, ctx.act, ctx.alpha)
         return (dgy if ctx.needs_input_grad[0] else None, dx if ctx.needs_input_grad[1] else None) + (None,) * 4
+
+
+class MinibatchStddevFn(Function):
+    """x [B,H,W,C] -> [B,F]: the minibatch standard deviation of the progressive-growing paper's critic —
+    per group of G contiguous samples and chunk of C/F channels, the mean over the chunk's columns of the standard deviation across
+    the group.  Only x is saved: the backward (MinibatchStddevBwdFn) recomputes mean and deviation from it, and has a backward of its
+    own, so the layer may sit in a critic under the gradient penalty."""
+
+    @staticmethod
+    def forward(ctx, x, group, features, eps):
+        ctx.save_for_backward(x)
+        ctx.group, ctx.features, ctx.eps = group, features, eps
+        ctx.set_materialize_grads(False)
+        return K.minibatch_stddev_fwd(_c(x), group, features, eps)
+
+    @staticmethod
+    def backward(ctx, gs):
+        if gs is None:
+            return None, None, None, None
+        x, = ctx.saved_tensors
+        return MinibatchStddevBwdFn.apply(gs, x, ctx.group, ctx.features, ctx.eps), None, None, None
+
+
+class MinibatchStddevBwdFn(Function):
+    """dx of MinibatchStddevFn from gs [B,F] (one launch).  backward = the double backward for the cotangent v of dx: dL/dgs and
+    dL/dx from v, x and gs (two launches).  The penalty differentiates a gradient once => once_differentiable."""
+
+    @staticmethod
+    def forward(ctx, gs, x, group, features, eps):
+        gs, x = _c(gs), _c(x)
+        ctx.save_for_backward(gs, x)
+        ctx.group, ctx.features, ctx.eps = group, features, eps
+        ctx.set_materialize_grads(False)
+        return K.minibatch_stddev_bwd(gs, x, group, features, eps)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, v):
+        if v is None:
+            return (None,) * 5
+        gs, x = ctx.saved_tensors
+        dxx, dgs = K.minibatch_stddev_bwd2(_c(v), x, gs, ctx.group, ctx.features, ctx.eps)
+        return (dgs if ctx.needs_input_grad[0] else None, dxx if ctx.needs_input_grad[1] else None, None, None, None)
 
 
 class ResizeNearestFn(Function):

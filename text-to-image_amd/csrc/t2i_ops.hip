@@ -635,7 +635,181 @@ __global__ __launch_bounds__(kThreads) void mul_kernel(const float* __restrict__
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Minibatch standard deviation (the PGGAN paper's critic layer) with its backward and double backward.
+// x [B,H,W,C]; sample n is in group n / G (contiguous rows), channel c in chunk c / (C/F).  Per column j = (h, w, c) of a group:
+//   mu = mean_g x,  d_g = x_g - mu,  sigma = sqrt(mean_g d_g^2 + eps);   stat[m, f] = mean of sigma over the Nf = H W C/F columns of chunk f.
+// With k = (sum_g gs[g, f]) / (Nf G), and v the cotangent of dx:
+//   dx_g = k d_g / sigma;   dL/dgs = (1 / (Nf G)) sum_{g, j} v_g d_g / sigma;
+//   dL/dx_g = k [(v_g - mean_g v) / sigma - d_g (sum_g v_g d_g) / (G sigma^3)].
+// A thread owns one unit (float4 or float) of a column block and holds it for the G samples of its group in registers (G <= 16:
+// 64 VGPRs of float4), so mu and the centred variance come from the registers in two passes — no E[x^2] - mu^2.  A workgroup
+// covers kMbBlockUnits units of one (group, chunk), grid (blocks, F, B / G): how a group is cut depends on the sample's shape
+// alone, never on the number of groups, so the statistic of a batch is bit for bit the statistics of its parts (the critic's 3B
+// pass relies on it).  Sums: the G samples in order in a thread, the wave's butterfly, the four waves in a fixed tree, then one wave
+// per (group, chunk) joins the workgroups' partials in a fixed order.  The register arrays are sized by GMAX in {2, 4, 8, 16}.
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int kMbGroupMax = 16;
+constexpr int kMbBlockUnits = kThreads;      // one unit per thread
+
+struct MbGeom {        // counted in units of T
+  int nfu;             // units of one (group, chunk) = H W cfu
+  int cfu, cu;         // units per pixel of a chunk / of all chunks
+  size_t pu;           // units per sample
+  FastDiv div_cf;
+};
+
+template <typename T, int GMAX>
+__device__ __forceinline__ void mb_load(const T* __restrict__ p, size_t base, size_t pu, int G, T (&r)[GMAX]) {
+#pragma unroll
+  for (int g = 0; g < GMAX; ++g) r[g] = g < G ? p[base + (size_t)g * pu] : splat<T>(0.f);
+}
+
+template <typename T, int GMAX>
+__device__ __forceinline__ void mb_store(T* __restrict__ p, size_t base, size_t pu, int G, const T (&r)[GMAX]) {
+#pragma unroll
+  for (int g = 0; g < GMAX; ++g)
+    if (g < G) p[base + (size_t)g * pu] = r[g];
+}
+
+template <typename T, int GMAX>
+__device__ __forceinline__ void mb_stats(const T (&r)[GMAX], int e, int G, float eps, float& mu, float& sigma) {
+  float s = 0.f;
+#pragma unroll
+  for (int g = 0; g < GMAX; ++g)
+    if (g < G) s += Lanes<T>::get(r[g], e);
+  mu = s / (float)G;
+  float q = 0.f;
+#pragma unroll
+  for (int g = 0; g < GMAX; ++g)
+    if (g < G) { const float d = Lanes<T>::get(r[g], e) - mu; q += d * d; }
+  sigma = sqrtf(q / (float)G + eps);
+}
+
+// the unit's offset inside its sample; q < nfu
+__device__ __forceinline__ size_t mb_offset(const MbGeom& ge, int q, int f) {
+  const int p = ge.div_cf.div(q);
+  return (size_t)p * ge.cu + (size_t)f * ge.cfu + (size_t)(q - p * ge.cfu);
+}
+
+__device__ __forceinline__ float mb_gbar(const float* __restrict__ gs, int m, int f, int G, int F) {
+  float s = 0.f;
+  for (int g = 0; g < G; ++g) s += gs[((size_t)m * G + g) * F + f];
+  return s;
+}
+
+// every thread of the workgroup calls this: the workgroup's sum, written by thread 0
+__device__ __forceinline__ void mb_block_partial(float acc, float* red, float* __restrict__ part) {
+  const float s = group_sum(acc, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) part[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+template <typename T, int GMAX>
+__global__ __launch_bounds__(kThreads) void mbstd_fwd_kernel(const T* __restrict__ x, MbGeom ge, int G, float eps, float* __restrict__ part) {
+  __shared__ float red[kThreads / 64];
+  const int q = blockIdx.x * kMbBlockUnits + threadIdx.x;
+  float acc = 0.f;
+  if (q < ge.nfu) {
+    const size_t base = (size_t)blockIdx.z * G * ge.pu + mb_offset(ge, q, blockIdx.y);
+    T r[GMAX];
+    mb_load<T, GMAX>(x, base, ge.pu, G, r);
+#pragma unroll
+    for (int e = 0; e < Lanes<T>::N; ++e) {
+      float mu, sigma;
+      mb_stats<T, GMAX>(r, e, G, eps, mu, sigma);
+      acc += sigma;
+    }
+  }
+  mb_block_partial(acc, red, part);
+}
+
+// grid (F, B / G), one wave: lane l adds the partials l, l + 64, ... in order, the butterfly joins the lanes; the G rows of the group
+// all receive sum / denom
+__global__ __launch_bounds__(64) void mbstd_join_kernel(const float* __restrict__ part, int nblk, int G, float denom, float* __restrict__ out) {
+  const int f = blockIdx.x, F = gridDim.x, m = blockIdx.y;
+  const float* p = part + ((size_t)m * F + f) * nblk;
+  float a = 0.f;
+  for (int k = threadIdx.x; k < nblk; k += 64) a += p[k];
+  a = group_sum(a, 64);
+  if ((int)threadIdx.x < G) out[((size_t)m * G + threadIdx.x) * F + f] = a / denom;
+}
+
+template <typename T, int GMAX>
+__global__ __launch_bounds__(kThreads) void mbstd_bwd_kernel(const float* __restrict__ gs, const T* __restrict__ x, MbGeom ge, int G, float eps,
+                                                              float denom, T* __restrict__ dx) {
+  const int q = blockIdx.x * kMbBlockUnits + threadIdx.x;
+  if (q >= ge.nfu) return;
+  const float k = mb_gbar(gs, blockIdx.z, blockIdx.y, G, gridDim.y) / denom;
+  const size_t base = (size_t)blockIdx.z * G * ge.pu + mb_offset(ge, q, blockIdx.y);
+  T r[GMAX];
+  mb_load<T, GMAX>(x, base, ge.pu, G, r);
+#pragma unroll
+  for (int e = 0; e < Lanes<T>::N; ++e) {
+    float mu, sigma;
+    mb_stats<T, GMAX>(r, e, G, eps, mu, sigma);
+    const float ks = k / sigma;
+#pragma unroll
+    for (int g = 0; g < GMAX; ++g)
+      if (g < G) Lanes<T>::set(r[g], e, ks * (Lanes<T>::get(r[g], e) - mu));
+  }
+  mb_store<T, GMAX>(dx, base, ge.pu, G, r);
+}
+
+template <typename T, int GMAX>
+__global__ __launch_bounds__(kThreads) void mbstd_bwd2_kernel(const T* __restrict__ v, const T* __restrict__ x, const float* __restrict__ gs,
+                                                               MbGeom ge, int G, float eps, float denom, T* __restrict__ dxx,
+                                                               float* __restrict__ part) {
+  __shared__ float red[kThreads / 64];
+  const int q = blockIdx.x * kMbBlockUnits + threadIdx.x;
+  float acc = 0.f;
+  if (q < ge.nfu) {
+    const float k = mb_gbar(gs, blockIdx.z, blockIdx.y, G, gridDim.y) / denom;
+    const size_t base = (size_t)blockIdx.z * G * ge.pu + mb_offset(ge, q, blockIdx.y);
+    T r[GMAX], w[GMAX];
+    mb_load<T, GMAX>(x, base, ge.pu, G, r);
+    mb_load<T, GMAX>(v, base, ge.pu, G, w);
+#pragma unroll
+    for (int e = 0; e < Lanes<T>::N; ++e) {
+      float mu, sigma;
+      mb_stats<T, GMAX>(r, e, G, eps, mu, sigma);
+      float sv = 0.f, t = 0.f;
+#pragma unroll
+      for (int g = 0; g < GMAX; ++g)
+        if (g < G) { const float vv = Lanes<T>::get(w[g], e); sv += vv; t += vv * (Lanes<T>::get(r[g], e) - mu); }
+      const float vbar = sv / (float)G, is = 1.0f / sigma;
+      const float a = k * is, b = k * t * (is * is * is) / (float)G;
+#pragma unroll
+      for (int g = 0; g < GMAX; ++g)
+        if (g < G) Lanes<T>::set(w[g], e, a * (Lanes<T>::get(w[g], e) - vbar) - b * (Lanes<T>::get(r[g], e) - mu));
+      acc += t * is;
+    }
+    mb_store<T, GMAX>(dxx, base, ge.pu, G, w);
+  }
+  mb_block_partial(acc, red, part);
+}
+
+inline MbGeom mb_geom(int H, int W, int C, int F, bool v4) {
+  const int sh = v4 ? 2 : 0;
+  MbGeom ge;
+  ge.cfu = (C / F) >> sh;
+  ge.cu = C >> sh;
+  ge.nfu = H * W * ge.cfu;
+  ge.pu = (size_t)H * W * ge.cu;
+  ge.div_cf.set((uint32_t)ge.cfu);
+  return ge;
+}
+
+inline int mb_blocks(int nfu) { return (nfu + kMbBlockUnits - 1) / kMbBlockUnits; }
+
 constexpr long long kMaxElems = (1ll << 30) - 16;        // include/t2i_hip.h: no tensor may exceed 2^30 - 16 elements
+
+// G in 1..16 dividing B, F >= 1 dividing C; the grid is (blocks, F, B / G)
+inline bool mb_shape_ok(int32_t B, int32_t H, int32_t W, int32_t C, int32_t G, int32_t F) {
+  return B > 0 && H > 0 && W > 0 && C > 0 && G >= 1 && G <= kMbGroupMax && B % G == 0 && F >= 1 && F <= 65535 && C % F == 0 &&
+         B / G <= 65535 && (long long)B * H * W <= kMaxElems / C;
+}
 
 inline bool act_ok(int act, float alpha) {       // lrelu: a slope >= 0 only (pixel_norm_dx)
   return act == T2I_ACT_NONE || (act == T2I_ACT_LRELU && alpha >= 0.f) || act == T2I_ACT_RELU || act == T2I_ACT_TANH;
@@ -929,3 +1103,89 @@ int t2i_mul(const float* a, const float* b, int64_t n, float* y, t2i_stream_t st
     hipLaunchKernelGGL(mul_kernel<false>, dim3(blocks_for(quads)), dim3(kThreads), 0, (hipStream_t)stream, a, b, (size_t)n, y);
   return launched("t2i_mul");
 }
+
+// ---- minibatch standard deviation ------------------------------------------------------------------------------------------------
+#define T2I_MB_GMAX(KERNEL, TT, ...)                                                                                                      \
+  do {                                                                                                                                    \
+    if (G <= 2) hipLaunchKernelGGL((KERNEL<TT, 2>), grid, dim3(kThreads), 0, st, __VA_ARGS__);                                            \
+    else if (G <= 4) hipLaunchKernelGGL((KERNEL<TT, 4>), grid, dim3(kThreads), 0, st, __VA_ARGS__);                                       \
+    else if (G <= 8) hipLaunchKernelGGL((KERNEL<TT, 8>), grid, dim3(kThreads), 0, st, __VA_ARGS__);                                       \
+    else hipLaunchKernelGGL((KERNEL<TT, kMbGroupMax>), grid, dim3(kThreads), 0, st, __VA_ARGS__);                                         \
+  } while (0)
+
+// the partials of the scalar form, which cuts a (group, chunk) into the most workgroups: the form is chosen at the call, by alignment
+size_t t2i_minibatch_stddev_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C, int32_t G, int32_t F) {
+  if (!mb_shape_ok(B, H, W, C, G, F)) return 0;
+  return (size_t)(B / G) * (size_t)F * (size_t)mb_blocks(H * W * (C / F)) * sizeof(float);
+}
+
+int t2i_minibatch_stddev_fwd(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t G, int32_t F, float eps, float* stat,
+                             void* ws, size_t ws_bytes, t2i_stream_t stream) {
+  if (!x || !stat || !mb_shape_ok(B, H, W, C, G, F) || !(eps > 0.f)) {
+    set_error("t2i_minibatch_stddev_fwd: bad argument (B=%d H=%d W=%d C=%d G=%d F=%d eps=%g; 1 <= G <= 16 divides B, F >= 1 divides C, eps > 0)", B, H,
+              W, C, G, F, (double)eps);
+    return T2I_ERR_INVALID;
+  }
+  if (!ws || ws_bytes < t2i_minibatch_stddev_workspace_bytes(B, H, W, C, G, F)) {
+    set_error("t2i_minibatch_stddev_fwd: workspace too small (%zu bytes, %zu needed)", ws ? ws_bytes : (size_t)0,
+              t2i_minibatch_stddev_workspace_bytes(B, H, W, C, G, F));
+    return T2I_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const bool v4 = ((C / F) & 3) == 0 && al16(x);
+  const MbGeom ge = mb_geom(H, W, C, F, v4);
+  const int nblk = mb_blocks(ge.nfu);
+  float* part = reinterpret_cast<float*>(ws);
+  const dim3 grid((unsigned)nblk, (unsigned)F, (unsigned)(B / G));
+  if (v4) T2I_MB_GMAX(mbstd_fwd_kernel, float4, reinterpret_cast<const float4*>(x), ge, G, eps, part);
+  else T2I_MB_GMAX(mbstd_fwd_kernel, float, x, ge, G, eps, part);
+  hipLaunchKernelGGL(mbstd_join_kernel, dim3((unsigned)F, (unsigned)(B / G)), dim3(64), 0, st, part, nblk, G,
+                     (float)((long long)H * W * (C / F)), stat);
+  return launched("t2i_minibatch_stddev_fwd");
+}
+
+int t2i_minibatch_stddev_bwd(const float* gs, const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t G, int32_t F, float eps,
+                             float* dx, t2i_stream_t stream) {
+  if (!gs || !x || !dx || !mb_shape_ok(B, H, W, C, G, F) || !(eps > 0.f)) {
+    set_error("t2i_minibatch_stddev_bwd: bad argument (B=%d H=%d W=%d C=%d G=%d F=%d eps=%g; 1 <= G <= 16 divides B, F >= 1 divides C, eps > 0)", B, H,
+              W, C, G, F, (double)eps);
+    return T2I_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const bool v4 = ((C / F) & 3) == 0 && al16(x) && al16(dx);
+  const MbGeom ge = mb_geom(H, W, C, F, v4);
+  const float denom = (float)((long long)H * W * (C / F)) * (float)G;
+  const dim3 grid((unsigned)mb_blocks(ge.nfu), (unsigned)F, (unsigned)(B / G));
+  if (v4) T2I_MB_GMAX(mbstd_bwd_kernel, float4, gs, reinterpret_cast<const float4*>(x), ge, G, eps, denom, reinterpret_cast<float4*>(dx));
+  else T2I_MB_GMAX(mbstd_bwd_kernel, float, gs, x, ge, G, eps, denom, dx);
+  return launched("t2i_minibatch_stddev_bwd");
+}
+
+int t2i_minibatch_stddev_bwd2(const float* v, const float* x, const float* gs, int32_t B, int32_t H, int32_t W, int32_t C, int32_t G,
+                              int32_t F, float eps, float* dxx, float* dgs, void* ws, size_t ws_bytes, t2i_stream_t stream) {
+  if (!v || !x || !gs || !dxx || !dgs || !mb_shape_ok(B, H, W, C, G, F) || !(eps > 0.f)) {
+    set_error("t2i_minibatch_stddev_bwd2: bad argument (B=%d H=%d W=%d C=%d G=%d F=%d eps=%g; 1 <= G <= 16 divides B, F >= 1 divides C, eps > 0)", B, H,
+              W, C, G, F, (double)eps);
+    return T2I_ERR_INVALID;
+  }
+  if (!ws || ws_bytes < t2i_minibatch_stddev_workspace_bytes(B, H, W, C, G, F)) {
+    set_error("t2i_minibatch_stddev_bwd2: workspace too small (%zu bytes, %zu needed)", ws ? ws_bytes : (size_t)0,
+              t2i_minibatch_stddev_workspace_bytes(B, H, W, C, G, F));
+    return T2I_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const bool v4 = ((C / F) & 3) == 0 && al16(v) && al16(x) && al16(dxx);
+  const MbGeom ge = mb_geom(H, W, C, F, v4);
+  const int nblk = mb_blocks(ge.nfu);
+  const float denom = (float)((long long)H * W * (C / F)) * (float)G;
+  float* part = reinterpret_cast<float*>(ws);
+  const dim3 grid((unsigned)nblk, (unsigned)F, (unsigned)(B / G));
+  if (v4)
+    T2I_MB_GMAX(mbstd_bwd2_kernel, float4, reinterpret_cast<const float4*>(v), reinterpret_cast<const float4*>(x), gs, ge, G, eps, denom,
+                reinterpret_cast<float4*>(dxx), part);
+  else
+    T2I_MB_GMAX(mbstd_bwd2_kernel, float, v, x, gs, ge, G, eps, denom, dxx, part);
+  hipLaunchKernelGGL(mbstd_join_kernel, dim3((unsigned)F, (unsigned)(B / G)), dim3(64), 0, st, part, nblk, G, denom, dgs);
+  return launched("t2i_minibatch_stddev_bwd2");
+}
+#undef T2I_MB_GMAX

@@ -1777,6 +1777,51 @@ def layer_norm_bwd2(v, gy, xhat, y, gamma, rstd, act=ACT_NONE, alpha=0.2, want_h
     return layer_norm_bwd2_apply(v, gy, xhat, y, gamma, rstd, sums, act, alpha, want_hgz)
 
 
+def _mbstd_args(x, G, F):
+    _chk(x, 'x', f32=True)
+    assert x.dim() == 4
+    B, H, W, C = x.shape
+    if not (1 <= G <= 16 and B % G == 0 and F >= 1 and C % F == 0):
+        raise ValueError('minibatch_stddev: group size %d (1..16) must divide the batch %d and %d statistic channels the %d channels' % (G, B, F, C))
+    return B, H, W, C
+
+
+def minibatch_stddev_fwd(x, G, F, eps=1e-8):
+    """x [B,H,W,C] -> stat [B,F]: the mean over chunk f's columns of the standard deviation across the G contiguous samples of a
+    group, the same in every row of the group (two launches: partials into the workspace, then their fixed-order sum)."""
+    B, H, W, C = _mbstd_args(x, G, F)
+    stat = torch.empty((B, F), dtype=torch.float32, device=x.device)
+    if _live(x) and x.numel() > 0:
+        wsp, wsn = _ws_args(x, int(lib.t2i_minibatch_stddev_workspace_bytes(B, H, W, C, G, F)))
+        check(lib.t2i_minibatch_stddev_fwd(_ptr(x), B, H, W, C, G, F, eps, _ptr(stat), wsp, wsn, _stream()), 't2i_minibatch_stddev_fwd')
+    return stat
+
+
+def minibatch_stddev_bwd(gs, x, G, F, eps=1e-8):
+    """dx of minibatch_stddev_fwd for the cotangent gs [B,F]; mu and sigma are recomputed from x.  One launch."""
+    B, H, W, C = _mbstd_args(x, G, F)
+    _chk(gs, 'gs', f32=True)
+    assert tuple(gs.shape) == (B, F)
+    dx = torch.empty_like(x)
+    if _live(x) and x.numel() > 0:
+        check(lib.t2i_minibatch_stddev_bwd(_ptr(gs), _ptr(x), B, H, W, C, G, F, eps, _ptr(dx), _stream()), 't2i_minibatch_stddev_bwd')
+    return dx
+
+
+def minibatch_stddev_bwd2(v, x, gs, G, F, eps=1e-8):
+    """The double backward: -> (dL/dx, dL/dgs [B,F]) of L = <v, minibatch_stddev_bwd(gs, x)>; two launches."""
+    B, H, W, C = _mbstd_args(x, G, F)
+    _chk(v, 'v', f32=True); _chk(gs, 'gs', f32=True)
+    assert v.shape == x.shape and tuple(gs.shape) == (B, F)
+    dxx = torch.empty_like(x)
+    dgs = torch.empty((B, F), dtype=torch.float32, device=x.device)
+    if _live(x) and x.numel() > 0:
+        wsp, wsn = _ws_args(x, int(lib.t2i_minibatch_stddev_workspace_bytes(B, H, W, C, G, F)))
+        check(lib.t2i_minibatch_stddev_bwd2(_ptr(v), _ptr(x), _ptr(gs), B, H, W, C, G, F, eps, _ptr(dxx), _ptr(dgs), wsp, wsn, _stream()),
+              't2i_minibatch_stddev_bwd2')
+    return dxx, dgs
+
+
 def resize_nearest(x, Ho, Wo):
     """x [B,H,W,C] -> [B,Ho,Wo,C], tf.image.resize_nearest_neighbor (align_corners=False)."""
     _chk(x, 'x', f32=True)

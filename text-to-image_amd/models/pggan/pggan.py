@@ -7,7 +7,9 @@ alpha = iter / steps next to the up-scaled previous `to_rgb` (generator) / the p
 The losses reuse the hot path's WGAN-GP machinery (gradient penalty through a double-differentiable critic); new
 here: per-sample layer norm (generator only), 2x2 average pool and nearest x2 upscale (a pair of adjoint kernels, closed
 under differentiation — the critic is differentiated twice), the fade-in mix; `critic_norm='layer' | 'pixel'` (not in the
-reference; default None = the reference's critic) normalises the critic's 3x3 / 4x4 convolutions per sample.  Reference specifics kept: penalty
+reference; default None = the reference's critic) normalises the critic's 3x3 / 4x4 convolutions per sample; `critic_mbstd=G` (not in the
+reference either; default None) puts the progressive-growing paper's minibatch standard deviation in front of the critic's last block
+(DESIGN.md section 4.29).  Reference specifics kept: penalty
 coefficient 200, no kt term, G = -D_fake + 5 KL, Adam(2e-6, beta1=0, beta2=0.99) hard-coded (pggan.py:104-110; the
 `learning_rate` placeholder is fed but unused), eps of x_hat drawn in-graph (pggan.py:68 overrides the placeholder),
 `to_rgb` = k2 s1 SAME 9-channel relu conv + 1x1, every kernel He-initialised by utils/ops.py's defaults.
@@ -25,16 +27,25 @@ from ... import autograd as A
 from ... import kernels as K
 from ... import optim
 from ... import scope as S
-from ...utils.ops import concat_tile, conv2d, fc, layer_norm, lerp, lrelu_act, pixel_norm, pool, relu, upscale
+from ...utils.ops import concat_tile, conv2d, fc, layer_norm, lerp, lrelu_act, minibatch_stddev_stat, pixel_norm, pool, relu, upscale
 
 
 class PGGAN(object):
     def __init__(self, batch_size, steps, check_dir_write, check_dir_read, dataset, sample_path, log_dir, stage, trans,
                  build_model=True, device=None, seed=0, store=None, fmap_base=1024, fmap_max=512, z_dim=128, embed_dim=1024,
-                 compr_embed_dim=128, dp=None, critic_norm=None):
+                 compr_embed_dim=128, dp=None, critic_norm=None, critic_mbstd=None):
         if critic_norm not in (None, 'layer', 'pixel'):
             raise ValueError("critic_norm must be None, 'layer' or 'pixel', got %r" % (critic_norm,))
         self.critic_norm = critic_norm
+        if critic_mbstd is not None and (isinstance(critic_mbstd, bool) or not isinstance(critic_mbstd, int) or critic_mbstd < 1):
+            raise ValueError('critic_mbstd must be None or an integer >= 1 (the group size of the minibatch standard deviation), got %r'
+                             % (critic_mbstd,))
+        if critic_mbstd is not None and (isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1):
+            raise ValueError('critic_mbstd needs an integer batch_size >= 1 to pick its group size from, got %r' % (batch_size,))
+        # the group: the largest divisor of the batch not above the argument (and the kernels' 16), so that groups of contiguous rows
+        # never straddle the B-row parts of the critic's 3B pass; per rank under data parallelism (batch_size is the local batch)
+        self.critic_mbstd = critic_mbstd
+        self.mbstd_group = None if critic_mbstd is None else max(g for g in range(1, min(critic_mbstd, 16) + 1) if batch_size % g == 0)
         self.batch_size, self.steps = batch_size, steps
         self.check_dir_write, self.check_dir_read = check_dir_write, check_dir_read
         self.dataset, self.sample_path, self.log_dir = dataset, sample_path, log_dir
@@ -113,7 +124,9 @@ class PGGAN(object):
             self._ca = self._noise(feed, 'ca_noise_d', cond[:, :self.compr_embed_dim])
             G, _, _ = self.generator(z, cond, stages=st, t=t, reuse=True)
             x_hat = K.interp(eps.reshape(B, 1, 1, 1).contiguous(), G, x)
-        # the critic has no batch coupling: D(G), D(x), D(x_mismatch) as one pass over 3B samples
+        # D(G), D(x), D(x_mismatch) as one pass over 3B samples: without critic_mbstd the critic has no batch coupling; with it the
+        # coupling is inside groups of contiguous rows whose size divides B, so no group straddles two of the three parts, and the
+        # statistic of the 3B rows is bit for bit that of three B-row passes
         logits = self.discriminator(torch.cat([G, x, xm], 0), torch.cat([cond, cond, cond], 0), reuse=True, stages=st, t=t).view(3, B)
         Dg_logit, Dx_logit, Dxmi_logit = logits[0], logits[1], logits[2]
         x_hat.requires_grad_(True)
@@ -249,6 +262,8 @@ class PGGAN(object):
                     x = lerp(x_iden, x, alpha_trans)              # alpha * x + (1 - alpha) * x_iden
             with S.variable_scope(self.get_conv_scope_name(0), reuse=reuse):
                 cond_compress = fc(cond, units=self.compr_embed_dim, act=act)
+                if self.mbstd_group is not None:        # [features | tiled compressed cond | tiled stat], the stat channels last
+                    cond_compress = torch.cat([cond_compress, minibatch_stddev_stat(x, self.mbstd_group, self.mbstd_features(x.shape[-1]))], 1)
                 concat = self.concat_cond4(x, cond_compress)
                 x_b1 = self._d_conv(concat, self.get_dnf(0), (3, 3), 'SAME', act)
                 x_b1 = self._d_conv(x_b1, self.get_dnf(0), (4, 4), 'VALID', act)
@@ -294,6 +309,12 @@ class PGGAN(object):
             if t:
                 x = lerp(x_iden, x, alpha_trans)                  # (1 - alpha) * x_iden + alpha * x
             return x, mean_lr, log_sigma_lr
+
+    @staticmethod
+    def mbstd_features(channels):
+        """Statistic channels of the minibatch standard deviation: 4 where the 4x4 map has a multiple of 16 channels (the next
+        convolution's input channels stay a multiple of four: the 16-byte conv kernels), else 1."""
+        return 4 if channels % 16 == 0 else 1
 
     def concat_cond4(self, x, cond):
         return concat_tile(x, cond)

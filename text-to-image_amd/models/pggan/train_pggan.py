@@ -93,6 +93,9 @@ def main(argv=None):
     ap.add_argument('--math', choices=['f32', 'bf16'], default='f32')
     ap.add_argument('--critic-norm', choices=['layer', 'pixel'], default=None,
                     help="normalise the critic's 3x3 / 4x4 convolutions per sample (default: the reference's un-normalised critic)")
+    ap.add_argument('--critic-mbstd', type=int, default=None, metavar='G',
+                    help="minibatch standard deviation in front of the critic's last block, over groups of (the largest divisor of the "
+                         "batch not above) G samples (default: none, the reference's critic)")
     ap.add_argument('--eager', action='store_true', help='--bench: keep eager launches instead of hipGraph replay')
     ap.add_argument('--bench', action='store_true', help='time `--iters` iterations of each entry instead of training with side effects')
     args = ap.parse_args(argv)
@@ -128,7 +131,8 @@ def main(argv=None):
         size = 4 * 2 ** (STAGE[i] - 1)
         pggan = PGGAN(batch_size=batch_size, steps=max_iters, check_dir_write=wdir, check_dir_read=rdir,
                       dataset=dataset_for(size, dev) if cfg is None else real_dataset(cfg, STAGE[i], dev), sample_path=sample_path,
-                      log_dir=logs_dir, stage=STAGE[i], trans=t, device=dev, critic_norm=args.critic_norm)
+                      log_dir=logs_dir, stage=STAGE[i], trans=t, device=dev, critic_norm=args.critic_norm,
+                      critic_mbstd=args.critic_mbstd)
         if args.bench:
             gen = torch.Generator(device=dev).manual_seed(0)
             feed = pggan.make_feed(gen)

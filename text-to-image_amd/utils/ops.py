@@ -15,7 +15,8 @@ Every public name of the reference's utils/ops.py exists here with its signature
     extents), ``gn`` and ``batch_renorm`` take fp32 tensors only: a bf16 tensor (bf16 storage) is refused with ValueError and a
     stacked pass (``stacked.Stacked``) with NotImplementedError, both before any launch and naming the operator;
   * ``batch_renorm`` and ``gn`` restate TF 1.4 as read from its sources; like the rest of the oracle they are not pinned against TF.
-``layer_norm`` and ``pixel_norm`` are differentiable twice (the per-sample normalisations of a critic under the gradient penalty),
+``layer_norm``, ``pixel_norm`` and ``minibatch_stddev`` (not in the reference: the PGGAN paper's critic layer) are differentiable twice
+(what a critic under the gradient penalty needs),
 like ``pool``, ``resize_nearest_neighbor``, ``gn``, ``lerp``, ``add`` and the convolutions; ``batch_norm`` / ``batch_renorm`` are first order.
 """
 import math
@@ -354,6 +355,39 @@ def pixel_norm(x, eps=1e-8, act=None):
         raise ValueError('pixel_norm normalises over the last axis of physically NHWC data; got a non-contiguous tensor (shape %s, strides %s) '
                          '- convert a logical NCHW view with to_nhwc first' % (tuple(x.shape), x.stride()))
     return A.PixelNormFn.apply(x, float(eps), kind, alpha)
+
+
+def minibatch_stddev_stat(x, group_size=4, num_features=1, eps=1e-8):
+    """The minibatch standard deviation of the progressive-growing paper's critic, as a statistic: x [B,H,W,C] (contiguous NHWC,
+    fp32) -> [B, num_features].  Sample n belongs to group n // group_size — CONTIGUOUS rows (the paper's code strides the groups; for
+    i.i.d. rows that is a permutation of this, and contiguous groups stay inside the B-row parts of a concatenated batch) —, channel c to
+    chunk c // (C / num_features).  Per column (h, w, c): the biased standard deviation sqrt(var + eps) across the group's samples;
+    row n, chunk f = its mean over the chunk's columns, the same in every row of a group.  group_size is taken as given: 1..16 and a
+    divisor of B (the caller picks a divisor); num_features divides C.  Differentiable twice; results for a
+    batch are bit for bit those of its groups taken separately."""
+    op = 'minibatch_stddev'
+    _fp32_plain(x, op)
+    if int(group_size) != group_size or int(num_features) != num_features:
+        raise ValueError('%s: group_size and num_features must be integers, got %r and %r' % (op, group_size, num_features))
+    G, F = int(group_size), int(num_features)
+    B, C = x.shape[0], x.shape[3]
+    if G < 1 or G > 16:
+        raise ValueError('%s: group_size must be in 1..16 (a thread keeps the group in registers), got %d' % (op, G))
+    if B % G != 0:
+        raise ValueError('%s: group_size %d does not divide the batch of %d' % (op, G, B))
+    if F < 1 or C % F != 0:
+        raise ValueError('%s: num_features %d does not divide the %d channels' % (op, F, C))
+    if not float(eps) > 0.0:
+        raise ValueError('%s: eps must be positive (the backward divides by sqrt(var + eps)), got %r' % (op, eps))
+    if not x.is_contiguous():
+        raise ValueError('%s works on physically NHWC data; got a non-contiguous tensor (shape %s, strides %s) - convert a logical NCHW '
+                         'view with to_nhwc first' % (op, tuple(x.shape), x.stride()))
+    return A.MinibatchStddevFn.apply(x, G, F, float(eps))
+
+
+def minibatch_stddev(x, group_size=4, num_features=1, eps=1e-8):
+    """x [B,H,W,C] -> [B,H,W,C + num_features]: minibatch_stddev_stat tiled over the map and appended as the last channels (concat_tile)."""
+    return concat_tile(x, minibatch_stddev_stat(x, group_size, num_features, eps))
 
 
 def pool(x, s=2, p_type='AVG', df=NHWC):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """The memory-bound kernels of csrc/t2i_ops.hip (pixel_norm, nearest resize and its adjoint, pool AVG / MAX with their backward maps,
-gn, the double backward of pixel_norm and layer_norm) at PGGAN-sized tensors: one JSON line per kernel with the time per call, the bytes the algorithm moves (reads + writes, from the
+gn, the double backward of pixel_norm and layer_norm, the minibatch standard deviation) at PGGAN-sized tensors: one JSON line per kernel with the time per call, the bytes the algorithm moves (reads + writes, from the
 shapes), bytes per second, and the ratio of that rate to a device-to-device copy that moves the SAME number of bytes (half read, half
 written), timed in the same process.  Per measurement: 10 warm-up launches, then REPS rounds of 100 back-to-back launches between
 device events, kernel and copy rounds alternating; the median round is reported.  Read the ratio, not the absolute rate, as the share
@@ -104,6 +104,16 @@ def main():
           lambda: K.layer_norm_bwd2_apply(v, g, xhat, yl, gamma, rstd, sums, K.ACT_LRELU, 0.2))
         m('layer_norm_bwd2_apply lrelu + hgz for dgamma (4r + 3w)', shape, 28 * n,
           lambda: K.layer_norm_bwd2_apply(v, g, xhat, yl, gamma, rstd, sums, K.ACT_LRELU, 0.2, want_hgz=True))
+
+    # minibatch standard deviation: the critic's own 4x4 map, and a streaming size in the cache regime of the lines above
+    for shape in ((64, 4, 4, 512), (64, 16, 16, 512)):
+        x = torch.randn(shape, device='cuda')
+        v = torch.randn(shape, device='cuda')
+        gs = torch.randn(shape[0], 4, device='cuda')
+        n = x.numel()
+        m('minibatch_stddev_fwd G=4 F=4 (r)', shape, 4 * n, lambda: K.minibatch_stddev_fwd(x, 4, 4))
+        m('minibatch_stddev_bwd G=4 F=4 (r + w)', shape, 8 * n, lambda: K.minibatch_stddev_bwd(gs, x, 4, 4))
+        m('minibatch_stddev_bwd2 G=4 F=4 (2r + w)', shape, 12 * n, lambda: K.minibatch_stddev_bwd2(v, x, gs, 4, 4))
 
 
 if __name__ == '__main__':
