@@ -342,6 +342,19 @@ int t2i_ca_kl_bwd(const float* mean, const float* log_sigma, const float* eps, c
  * m may be NULL when beta1 == 0 (v7): m_t = g_t * grad_scale whatever m_{t-1} was, so it is neither read nor written. */
 int t2i_adam_tf(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, const float* lr_t_dev, float beta1,
                 float beta2, float eps, float grad_scale, t2i_stream_t stream);
+/* t2i_adam_tf plus tf.train.ExponentialMovingAverage of the updated weights, in the same launch (v13, added without a version
+ * change: no existing argument list moved).  w, m, v after the call are bit for bit what t2i_adam_tf writes from the same inputs;
+ * then, per element, in fp32 and without fma contraction,
+ *   omd = 1 - decay;  ema = ema - omd * (ema - w_new)
+ * so the shadow equals a step-by-step fp32 restatement on the host bit for bit.  decay is read from *ema_decay_dev when that
+ * pointer is non-NULL (as lr_t_dev: a captured launch replays with a changed decay), else it is ema_decay, which must lie in
+ * [0, 1].  ema: n floats, 16-byte aligned, overlapping none of w, g, m, v.  Everything t2i_adam_tf refuses is refused here, and
+ * every refusal returns T2I_ERR_INVALID before any launch.  Enqueues one kernel on `stream`, allocates and synchronises nothing,
+ * graph-capturable; treats the filter cache as t2i_adam_tf does for the arena it updates (the tuning key cache_refresh included).
+ * The shadow is not filter memory to the cache: whoever copies it into an arena is a writer of filter memory like any other. */
+int t2i_adam_tf_ema(float* w, const float* g, float* m, float* v, float* ema, int64_t n, float lr_t, const float* lr_t_dev,
+                    float beta1, float beta2, float eps, float grad_scale, float ema_decay, const float* ema_decay_dev,
+                    t2i_stream_t stream);
 
 /* kt <- kt - lr * 2 (kt*wd2 - wd) * wd2, the SGD step on balance_loss = (kt*wdist2 - wdist)^2 (reference
  * models/wgancls/model.py:85,100: GradientDescentOptimizer(0.001) minimising balance_loss over kt).  wdist_sums = device

@@ -1598,6 +1598,71 @@ hipError_t adam_tf_launch(float* w, const float* g, float* m, float* v, int64_t 
   return hipGetLastError();
 }
 
+// tf.train.ExponentialMovingAverage of the weights, formed in the pass that updates them: ema -= (1 - decay) * (ema - w_t).
+// One more read and one more write per element (28 instead of 20 bytes at beta1 == 0; a pass of its own would read w_t again: 12
+// bytes and a launch).  The shadow statement is compiled without fma contraction — it then equals a step-by-step fp32 restatement
+// on the host bit for bit; the Adam arithmetic above it is adam_tf_kernel's, statement for statement, under the file's default
+// contraction, so w, m, v are bit for bit what that kernel writes.
+__device__ __forceinline__ float ema_step(float s, float w, float omd) {
+#pragma clang fp contract(off)
+  const float d = s - w;
+  const float p = omd * d;
+  return s - p;
+}
+
+__global__ __launch_bounds__(256) void adam_tf_ema_kernel(float* __restrict__ w, const float* __restrict__ g,
+                                                          float* __restrict__ m, float* __restrict__ v,
+                                                          float* __restrict__ ema, size_t n, float lr_val,
+                                                          const float* __restrict__ lr_dev, float b1, float b2, float eps,
+                                                          float gscale, float decay_val, const float* __restrict__ decay_dev) {
+  const float lr_t = lr_dev ? *lr_dev : lr_val;
+  const float omd = 1.0f - (decay_dev ? *decay_dev : decay_val);   // device scalar: a captured graph replays with a new decay
+  const size_t n4 = n >> 2;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (size_t i = t; i < n4; i += stride) {
+    float4 W = reinterpret_cast<float4*>(w)[i];
+    const float4 G0 = reinterpret_cast<const float4*>(g)[i];
+    float4 M = b1 != 0.f ? reinterpret_cast<float4*>(m)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 V = reinterpret_cast<float4*>(v)[i];
+    float4 E = reinterpret_cast<float4*>(ema)[i];
+    float gx = G0.x * gscale, gy = G0.y * gscale, gz = G0.z * gscale, gw = G0.w * gscale;
+    M.x = b1 * M.x + (1.f - b1) * gx; M.y = b1 * M.y + (1.f - b1) * gy;
+    M.z = b1 * M.z + (1.f - b1) * gz; M.w = b1 * M.w + (1.f - b1) * gw;
+    V.x = b2 * V.x + (1.f - b2) * gx * gx; V.y = b2 * V.y + (1.f - b2) * gy * gy;
+    V.z = b2 * V.z + (1.f - b2) * gz * gz; V.w = b2 * V.w + (1.f - b2) * gw * gw;
+    W.x -= lr_t * M.x / (sqrtf(V.x) + eps); W.y -= lr_t * M.y / (sqrtf(V.y) + eps);
+    W.z -= lr_t * M.z / (sqrtf(V.z) + eps); W.w -= lr_t * M.w / (sqrtf(V.w) + eps);
+    E.x = ema_step(E.x, W.x, omd); E.y = ema_step(E.y, W.y, omd);
+    E.z = ema_step(E.z, W.z, omd); E.w = ema_step(E.w, W.w, omd);
+    reinterpret_cast<float4*>(w)[i] = W;
+    if (m) reinterpret_cast<float4*>(m)[i] = M;
+    reinterpret_cast<float4*>(v)[i] = V;
+    reinterpret_cast<float4*>(ema)[i] = E;
+  }
+  for (size_t i = (n4 << 2) + t; i < n; i += stride) {
+    const float gg = g[i] * gscale;
+    const float mm = b1 * (b1 != 0.f ? m[i] : 0.f) + (1.f - b1) * gg;
+    const float vv = b2 * v[i] + (1.f - b2) * gg * gg;
+    if (m) m[i] = mm;
+    v[i] = vv;
+    float ww = w[i];
+    ww -= lr_t * mm / (sqrtf(vv) + eps);
+    w[i] = ww;
+    ema[i] = ema_step(ema[i], ww, omd);
+  }
+}
+
+hipError_t adam_tf_ema_launch(float* w, const float* g, float* m, float* v, float* ema, int64_t n, float lr_t, const float* lr_dev,
+                              float b1, float b2, float eps, float gscale, float decay, const float* decay_dev, hipStream_t stream) {
+  const int adam_cap = tuning().adam_blocks;
+  size_t nb = ((((size_t)n + 3) >> 2) + 255) / 256;
+  if (nb > (size_t)adam_cap) nb = adam_cap;
+  hipLaunchKernelGGL(adam_tf_ema_kernel, dim3((int)nb), dim3(256), 0, stream, w, g, m, v, ema, (size_t)n,
+                     lr_t, lr_dev, b1, b2, eps, gscale, decay, decay_dev);
+  return hipGetLastError();
+}
+
 // kt <- kt - lr * d(balance_loss)/d(kt) with balance_loss = (kt*wdist2 - wdist)^2 (reference models/wgancls/model.py:85,100:
 // GradientDescentOptimizer(0.001) on kt).  wdist / wdist2 arrive as SUMS over the data-parallel ranks of the per-rank batch
 // means (scale = 1/ranks turns them into the global-batch means: the balance loss is quadratic in them, so averaging

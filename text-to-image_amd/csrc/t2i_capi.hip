@@ -96,6 +96,8 @@ hipError_t lerp_dev_launch(const float*, const float*, const float*, int, size_t
 hipError_t col_reduce_partials_launch(const float*, const float*, int, int, float*, float*, int, hipStream_t);
 hipError_t adam_tf_launch(float*, const float*, float*, float*, int64_t, float, const float*, float, float, float, float,
                           hipStream_t);
+hipError_t adam_tf_ema_launch(float*, const float*, float*, float*, float*, int64_t, float, const float*, float, float, float, float,
+                              float, const float*, hipStream_t);
 hipError_t kt_sgd_launch(float*, const float*, float, float, hipStream_t);
 hipError_t zero_ranges_launch(float*, const long long*, int, hipStream_t);
 hipError_t trunc_normal_launch(float*, size_t, unsigned long long, unsigned long long, float, float, float, float, hipStream_t);
@@ -1814,6 +1816,33 @@ int t2i_adam_tf(float* w, const float* g, float* m, float* v, int64_t n, float l
   const int rc = check(adam_tf_launch(w, g, m, v, n, lr_t, lr_t_dev, beta1, beta2, eps, grad_scale, (hipStream_t)stream), "t2i_adam_tf");
   if (rc != T2I_OK || !tuning().cache_refresh) return rc;
   return filter_cache_refresh(w, (size_t)n * 4, (hipStream_t)stream);   // ... and regenerated behind the update, all in one launch
+}
+
+int t2i_adam_tf_ema(float* w, const float* g, float* m, float* v, float* ema, int64_t n, float lr_t, const float* lr_t_dev,
+                    float beta1, float beta2, float eps, float grad_scale, float ema_decay, const float* ema_decay_dev,
+                    t2i_stream_t stream) {
+  if (!w || !g || !v || n <= 0) { set_error("t2i_adam_tf_ema: bad argument"); return T2I_ERR_INVALID; }
+  if (!ema) { set_error("t2i_adam_tf_ema: ema is NULL (t2i_adam_tf is the update without a shadow)"); return T2I_ERR_INVALID; }
+  if (!m && beta1 != 0.f) { set_error("t2i_adam_tf_ema: m may be NULL only with beta1 == 0 (the first moment is then grad * grad_scale)"); return T2I_ERR_INVALID; }
+  if (!(aligned16(w) && aligned16(g) && (!m || aligned16(m)) && aligned16(v) && aligned16(ema))) {
+    set_error("t2i_adam_tf_ema: arena and shadow must be 16-byte aligned");
+    return T2I_ERR_INVALID;
+  }
+  const uintptr_t e0 = reinterpret_cast<uintptr_t>(ema), bytes = (uintptr_t)n * 4;
+  const void* others[4] = {w, g, m, v};
+  for (const void* o : others) {
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(o);
+    if (o && e0 < o0 + bytes && o0 < e0 + bytes) { set_error("t2i_adam_tf_ema: ema overlaps w, g, m or v"); return T2I_ERR_INVALID; }
+  }
+  if (!ema_decay_dev && !(ema_decay >= 0.f && ema_decay <= 1.f)) {
+    set_error("t2i_adam_tf_ema: ema_decay %g is outside [0, 1]", (double)ema_decay);
+    return T2I_ERR_INVALID;
+  }
+  filter_cache_invalidate(w, (size_t)n * 4);          // as t2i_adam_tf: transformed filters of this arena are stale from here on
+  const int rc = check(adam_tf_ema_launch(w, g, m, v, ema, n, lr_t, lr_t_dev, beta1, beta2, eps, grad_scale, ema_decay, ema_decay_dev,
+                                          (hipStream_t)stream), "t2i_adam_tf_ema");
+  if (rc != T2I_OK || !tuning().cache_refresh) return rc;
+  return filter_cache_refresh(w, (size_t)n * 4, (hipStream_t)stream);
 }
 
 long long t2i_stat(const char* key) {

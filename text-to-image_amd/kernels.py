@@ -1087,6 +1087,20 @@ def adam_tf(w, g, m, v, lr_t, beta1, beta2, eps=1e-8, grad_scale=1.0, lr_t_dev=N
               't2i_adam_tf')
 
 
+def adam_tf_ema(w, g, m, v, ema, lr_t, beta1, beta2, eps=1e-8, grad_scale=1.0, ema_decay=0.999, lr_t_dev=None, ema_decay_dev=None):
+    """adam_tf plus the exponential moving average of the updated weights in the same launch: ema -= (1 - decay) * (ema - w_new).
+    ema_decay_dev: optional device scalar that overrides ema_decay (graph replay)."""
+    for t in (w, g, v) + ((m,) if m is not None else ()):
+        _chk(t)
+    _chk(ema, 'ema', f32=True)
+    assert w.numel() == g.numel() == v.numel() == ema.numel() and (m is None or m.numel() == w.numel())
+    assert m is not None or beta1 == 0.0, 'the first moment can be skipped only with beta1 == 0'
+    if _live(w):
+        check(lib.t2i_adam_tf_ema(_ptr(w), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), w.numel(), lr_t, _ptr(lr_t_dev), beta1, beta2, eps,
+                                  grad_scale, ema_decay, _ptr(ema_decay_dev), _stream()),
+              't2i_adam_tf_ema')
+
+
 def device_info(device=0):
     cu, clk = ctypes.c_int32(0), ctypes.c_int32(0)
     arch = ctypes.create_string_buffer(64)

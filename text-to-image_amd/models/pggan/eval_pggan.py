@@ -46,8 +46,10 @@ def stage_model(cfg, stage, batch_size, dataset, device, **widths):
     return m
 
 
-def restore_generator(m):
-    restore_scopes(m.store, [('g_net', m.check_dir_read)], error=lambda scope: RuntimeError('Could not load stage %d' % m.stage), verbose=False)
+def restore_generator(m, ema=False):
+    """ema=True: the moving average of the weights that `train_pggan.py --g-ema` keeps in the checkpoint, as the weights."""
+    restore_scopes(m.store, [('g_net', m.check_dir_read)], error=lambda scope: RuntimeError('Could not load stage %d' % m.stage), verbose=False,
+                   ema=ema)
 
 
 def generate(m, z, cond, cond_noise=True):
@@ -63,6 +65,7 @@ class PGGANEval(GeneratorEval):
     keep_preds = True
     size_error = 'EVAL.SIZE %d is smaller than the batch %d'
     announce = {}
+    ema = False                            # True: score the moving average of the generator's weights
 
     def batch_size(self):
         return self.model.batch_size
@@ -71,7 +74,7 @@ class PGGANEval(GeneratorEval):
         return self.bs                     # eval_pggan.py: incep_batch_size = batch_size
 
     def restore(self):
-        restore_generator(self.model)
+        restore_generator(self.model, ema=self.ema)
 
     def generate_batch(self, z, cond, is_training):
         return generate(self.model, z, cond)          # no batch norm: no mode
@@ -94,6 +97,7 @@ def main(argv=None, **widths):
     ap.add_argument('--stage', type=int, default=7, help='the stage whose generator is scored [7]')
     ap.add_argument('--batch', type=int, default=64, help='images generated (and scored) per batch [64]')
     ap.add_argument('--incep-batch', type=int, default=None, help='Inception batch (default: --batch)')
+    ap.add_argument('--ema', action='store_true', help="score the moving average of the generator's weights (a checkpoint of train_pggan.py --g-ema)")
     args = ap.parse_args(argv)
     if not 1 <= args.stage <= 8:
         ap.error('--stage must be in 1..8')
@@ -108,6 +112,7 @@ def main(argv=None, **widths):
     dataset = load_stage_dataset(cfg, args.stage, dev)
     m = stage_model(cfg, args.stage, args.batch, dataset, dev, **widths)
     ev = PGGANEval(None, m, dataset, cfg, incep_batch_size=args.incep_batch)
+    ev.ema = args.ema
     out = ev.evaluate_inception() if args.eval == 'is' else ev.evaluate_fid()
     out.pop('preds', None)
     return out

@@ -9,7 +9,8 @@ here: per-sample layer norm (generator only), 2x2 average pool and nearest x2 up
 under differentiation — the critic is differentiated twice), the fade-in mix; `critic_norm='layer' | 'pixel'` (not in the
 reference; default None = the reference's critic) normalises the critic's 3x3 / 4x4 convolutions per sample; `critic_mbstd=G` (not in the
 reference either; default None) puts the progressive-growing paper's minibatch standard deviation in front of the critic's last block
-(DESIGN.md section 4.29).  Reference specifics kept: penalty
+(DESIGN.md section 4.29); `g_ema=D` (the paper's `Gs`; default None) keeps an exponential moving average of the generator's weights, formed in
+the generator's Adam launch, that checkpoints carry and `ema_weights()` / `--ema` sample from.  Reference specifics kept: penalty
 coefficient 200, no kt term, G = -D_fake + 5 KL, Adam(2e-6, beta1=0, beta2=0.99) hard-coded (pggan.py:104-110; the
 `learning_rate` placeholder is fed but unused), eps of x_hat drawn in-graph (pggan.py:68 overrides the placeholder),
 `to_rgb` = k2 s1 SAME 9-channel relu conv + 1x1, every kernel He-initialised by utils/ops.py's defaults.
@@ -18,6 +19,7 @@ reference's) so that the golden step can be tiny.
 alpha: the reference assigns `alpha_tra = iter / steps` under a control dependency of D_optim only (pggan.py:76-77,112);
 whether the critic step's own forward sees the new or the previous value is a TF scheduling race.  Here alpha is set
 from `iter` BEFORE the critic step and kept for the generator step and the sampler — the assign-first order."""
+import contextlib
 import sys
 import time
 
@@ -33,7 +35,10 @@ from ...utils.ops import concat_tile, conv2d, fc, layer_norm, lerp, lrelu_act, m
 class PGGAN(object):
     def __init__(self, batch_size, steps, check_dir_write, check_dir_read, dataset, sample_path, log_dir, stage, trans,
                  build_model=True, device=None, seed=0, store=None, fmap_base=1024, fmap_max=512, z_dim=128, embed_dim=1024,
-                 compr_embed_dim=128, dp=None, critic_norm=None, critic_mbstd=None):
+                 compr_embed_dim=128, dp=None, critic_norm=None, critic_mbstd=None, g_ema=None):
+        if g_ema is not None and (isinstance(g_ema, bool) or not isinstance(g_ema, (int, float)) or not 0.0 < g_ema < 1.0):
+            raise ValueError("g_ema must be None or a decay in (0, 1) (the moving average of the generator's weights), got %r" % (g_ema,))
+        self.g_ema = None if g_ema is None else float(g_ema)
         if critic_norm not in (None, 'layer', 'pixel'):
             raise ValueError("critic_norm must be None, 'layer' or 'pixel', got %r" % (critic_norm,))
         self.critic_norm = critic_norm
@@ -104,7 +109,7 @@ class PGGAN(object):
         """pggan.py:84-130 (the optimizers; the loss expressions are in d_losses / g_losses)."""
         self.gp_coeff, self.kl_coeff = 200.0, 5.0
         self.D_optimizer = optim.AdamTF(self.d_arena, 0.0, 0.99)
-        self.G_optimizer = optim.AdamTF(self.g_arena, 0.0, 0.99)
+        self.G_optimizer = optim.AdamTF(self.g_arena, 0.0, 0.99, ema_decay=self.g_ema)      # (None: no shadow, the plain launch)
         self.adam_lr = 0.000002
 
     def _noise(self, feed, key, like):
@@ -237,6 +242,30 @@ class PGGAN(object):
         d = self._d_body(feed)
         self.G_optimizer.prepare(self.adam_lr)
         return {'d': d, 'g': self._g_body(feed)}
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the generator's variables hold the moving average and the shadow holds the weights; on exit they are
+        exchanged back, bit for bit.  Both exchanges write filter memory behind the optimizer's back, so the arena's cached filter
+        images are dropped both times.  Not inside a capture (the exchange is host-ordered work around the sampler, not a step)."""
+        opt = getattr(self, 'G_optimizer', None)
+        if opt is None or opt.ema is None:
+            raise RuntimeError('this model keeps no moving average of the generator (g_ema=None)')
+        if self.device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('ema_weights() cannot run inside a graph capture')
+        flat, ema = self.g_arena.flat, opt.ema
+
+        def exchange():
+            with torch.no_grad():
+                tmp = flat.clone()
+                flat.copy_(ema)
+                ema.copy_(tmp)
+            K.filter_cache_invalidate(flat)
+        exchange()
+        try:
+            yield self
+        finally:
+            exchange()
 
     def sampler(self, z_sample, cond_sample):
         with torch.no_grad():
@@ -404,9 +433,10 @@ class PGGAN(object):
         from ...utils.saver import Saver, load, save
         from ...utils.utils import get_balanced_factorization, save_captions, save_images
         log = log or (lambda s: (sys.stdout.write(s + '\n'), sys.stdout.flush()))
-        saver = Saver(self.store, var_list=self.get_variables_up_to_stage(self.stage), max_to_keep=2)
+        shadows = [self.G_optimizer] if self.g_ema is not None else None      # both savers: a transition restores the previous stage's shadows too
+        saver = Saver(self.store, var_list=self.get_variables_up_to_stage(self.stage), max_to_keep=2, shadows=shadows)
         if side_effects and self.stage != 1:
-            src = Saver(self.store, var_list=self.get_variables_up_to_stage(self.stage - 1)) if self.trans else saver
+            src = Saver(self.store, var_list=self.get_variables_up_to_stage(self.stage - 1), shadows=shadows) if self.trans else saver
             could_load, step = load(src, None, self.check_dir_read)
             if not could_load:
                 raise RuntimeError('Could not load previous stage during transition' if self.trans else 'Could not load current stage')
@@ -434,6 +464,10 @@ class PGGAN(object):
             if side_effects and (idx % 2000 == 0 or (final_sample and idx == end - 1)):
                 samples = torch.clamp(self.sampler(sample_z, sample_cond), -1.0, 1.0)
                 save_images(samples, get_balanced_factorization(samples.shape[0]), '{}train_{:02d}_{:04d}.png'.format(self.sample_path, 0, idx))
+                if self.g_ema is not None:            # the same z and captions from the averaged generator
+                    with self.ema_weights():
+                        samples = torch.clamp(self.sampler(sample_z, sample_cond), -1.0, 1.0)
+                    save_images(samples, get_balanced_factorization(samples.shape[0]), '{}train_ema_{:02d}_{:04d}.png'.format(self.sample_path, 0, idx))
             if side_effects and (idx % 2000 == 0 or idx == end - 1):      # end - 1 == steps - 1 unless max_steps truncates
                 save(saver, None, self.check_dir_write, idx)
         return out

@@ -96,6 +96,10 @@ def main(argv=None):
     ap.add_argument('--critic-mbstd', type=int, default=None, metavar='G',
                     help="minibatch standard deviation in front of the critic's last block, over groups of (the largest divisor of the "
                          "batch not above) G samples (default: none, the reference's critic)")
+    ap.add_argument('--g-ema', type=float, default=None, metavar='D',
+                    help="keep an exponential moving average of the generator's weights with decay D in (0, 1) (the paper: 0.999); checkpoints "
+                         "carry it, a second sample grid train_ema_* is drawn from it, and eval / visualize read it with --ema "
+                         "(default: none)")
     ap.add_argument('--eager', action='store_true', help='--bench: keep eager launches instead of hipGraph replay')
     ap.add_argument('--bench', action='store_true', help='time `--iters` iterations of each entry instead of training with side effects')
     args = ap.parse_args(argv)
@@ -103,6 +107,8 @@ def main(argv=None):
         ap.error('--first %d / --last %d: need 0 <= first <= last <= %d' % (args.first, args.last, len(STAGE) - 1))
     if args.iters is not None and args.iters < 1:
         ap.error('--iters must be positive')
+    if args.g_ema is not None and not 0.0 < args.g_ema < 1.0:          # (NaN fails both comparisons)
+        ap.error('--g-ema %r: the decay must lie in (0, 1)' % args.g_ema)
     cfg = None
     if args.cfg is not None:
         from t2i_amd.utils.config import config_from_yaml
@@ -132,7 +138,7 @@ def main(argv=None):
         pggan = PGGAN(batch_size=batch_size, steps=max_iters, check_dir_write=wdir, check_dir_read=rdir,
                       dataset=dataset_for(size, dev) if cfg is None else real_dataset(cfg, STAGE[i], dev), sample_path=sample_path,
                       log_dir=logs_dir, stage=STAGE[i], trans=t, device=dev, critic_norm=args.critic_norm,
-                      critic_mbstd=args.critic_mbstd)
+                      critic_mbstd=args.critic_mbstd, **({} if args.g_ema is None else {'g_ema': args.g_ema}))
         if args.bench:
             gen = torch.Generator(device=dev).manual_seed(0)
             feed = pggan.make_feed(gen)

@@ -47,7 +47,7 @@ def stage_sample(samples, size=128):
     return out
 
 
-def visualize_last_stage(cfg, dataset, device, batch_size=64, stages=STAGES, **widths):
+def visualize_last_stage(cfg, dataset, device, batch_size=64, stages=STAGES, ema=False, **widths):
     """-> dict(sheets: the uint8 sheets written, samples: the clipped stage outputs, resized: stage_sample's result)."""
     z_dim = widths.get('z_dim', 128)
     z_sample = np.random.standard_normal((batch_size, z_dim))
@@ -60,7 +60,7 @@ def visualize_last_stage(cfg, dataset, device, batch_size=64, stages=STAGES, **w
     for stage in stages:
         print('Generating stage %d' % stage, flush=True)
         m = stage_model(cfg, stage, batch_size, dataset, device, **widths)
-        restore_generator(m)
+        restore_generator(m, ema=ema)
         all_samples.append(generate(m, z, cond).cpu().numpy())
         del m
     resized = stage_sample(all_samples, 128)
@@ -75,6 +75,7 @@ def main(argv=None, **widths):
     from t2i_amd.utils.config import config_from_yaml
     ap = argparse.ArgumentParser()
     ap.add_argument('--cfg', required=True, help='models/pggan/cfg/flowers.yml or birds.yml')
+    ap.add_argument('--ema', action='store_true', help="every stage from the moving average of its generator's weights (checkpoints of train_pggan.py --g-ema)")
     args = ap.parse_args(argv)
     cfg = config_from_yaml(args.cfg)
     for stage in STAGES:
@@ -83,7 +84,7 @@ def main(argv=None, **widths):
             raise RuntimeError('Could not load stage %d (no checkpoint in %s)' % (stage, d))
     dev = torch.device('cuda')
     dataset = load_stage_dataset(cfg, 5, dev)         # TextDataset(datadir, 64) as the reference: only its test captions are used
-    return visualize_last_stage(cfg, dataset, dev, **widths)
+    return visualize_last_stage(cfg, dataset, dev, ema=args.ema, **widths)
 
 
 if __name__ == '__main__':

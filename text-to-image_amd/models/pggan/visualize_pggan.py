@@ -60,8 +60,9 @@ def generator_fn(m, cond_noise):
 
 
 class PGGANVisualizer(object):
-    def __init__(self, sess, model, dataset, config):
+    def __init__(self, sess, model, dataset, config, ema=False):
         self.sess = sess                   # unused: there is no TF session
+        self.ema = ema                     # True: draw from the moving average of the generator's weights
         self.model = model
         self.dataset = dataset
         self.config = config
@@ -81,7 +82,7 @@ class PGGANVisualizer(object):
         ('gifs': list of uint8 [64, h, w, 3])."""
         m, test = self.model, self.dataset.test
         specials = self.special_positions()
-        restore_generator(m)
+        restore_generator(m, ema=self.ema)
         gen, gen_no_noise = generator_fn(m, True), generator_fn(m, False)
         B, z_dim = m.batch_size, m.z_dim
         cap = WGanClsVisualizer._first_caption
@@ -121,6 +122,7 @@ def main(argv=None, **widths):
     ap.add_argument('--cfg', required=True, help='models/pggan/cfg/flowers.yml or birds.yml')
     ap.add_argument('--interp', type=int, default=40, help='rounds of interpolation / caption sheets [40]')
     ap.add_argument('--stage', type=int, default=7, help='the stage whose generator draws the sheets [7]')
+    ap.add_argument('--ema', action='store_true', help="draw from the moving average of the generator's weights (a checkpoint of train_pggan.py --g-ema)")
     args = ap.parse_args(argv)
     if args.interp < 0 or not 1 <= args.stage <= 8:
         ap.error('--interp must be >= 0 and --stage in 1..8')
@@ -132,7 +134,7 @@ def main(argv=None, **widths):
     dev = torch.device('cuda')
     dataset = load_stage_dataset(cfg, args.stage, dev)
     m = stage_model(cfg, args.stage, 64, dataset, dev, **widths)
-    return PGGANVisualizer(None, m, dataset, cfg).visualize(args.interp)
+    return PGGANVisualizer(None, m, dataset, cfg, ema=args.ema).visualize(args.interp)
 
 
 if __name__ == '__main__':

@@ -121,10 +121,24 @@ class Arena(object):
 
 class AdamTF(object):
     """lr_t = lr*sqrt(1-b2^t)/(1-b1^t); m,v updates; w -= lr_t*m/(sqrt(v)+eps) — epsilon OUTSIDE the bias correction
-    (SURVEY.md §8a M5).  With beta1=0, t=1 this is ~lr*sign(g)."""
+    (SURVEY.md §8a M5).  With beta1=0, t=1 this is ~lr*sign(g).
+    ema_decay (default None: no shadow, the plain update): a float in (0, 1) keeps `ema`, tf.train.ExponentialMovingAverage of the
+    weights — a flat fp32 buffer of the arena's layout that starts as a copy of the weights (TF initialises a shadow to its
+    variable's value) and is advanced by every step, in the update's own launch: ema -= (1 - decay) * (ema - w_new)
+    (DESIGN.md section 4.30)."""
 
-    def __init__(self, arena, beta1=0.9, beta2=0.999, eps=1e-8):
+    ema = None
+
+    def __init__(self, arena, beta1=0.9, beta2=0.999, eps=1e-8, ema_decay=None):
+        if ema_decay is not None:
+            if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 < ema_decay < 1.0:
+                raise ValueError('ema_decay must be None or a number in (0, 1), got %r' % (ema_decay,))
+            ema_decay = float(ema_decay)
         self.arena, self.beta1, self.beta2, self.eps = arena, beta1, beta2, eps
+        self.ema_decay = ema_decay
+        if ema_decay is not None:
+            self.ema = arena.flat.detach().clone()
+            self.ema_decay_dev = torch.full((4,), ema_decay, dtype=torch.float32, device=arena.flat.device)   # [0] = the decay
         self._m = torch.zeros_like(arena.flat)
         self.v = torch.zeros_like(arena.flat)
         # beta1 == 0 (both wgancls optimizers, PGGAN): m_t = g_t * grad_scale whatever m_{t-1} was, so the step neither reads nor
@@ -173,6 +187,28 @@ class AdamTF(object):
         self.lr_t_dev.fill_(lr_t)
         return lr_t
 
+    def set_ema_decay(self, decay):
+        """Publish a new decay to the device scalar the fused launch reads (a host call outside any captured graph, like prepare)."""
+        if self.ema is None:
+            raise RuntimeError('this optimizer keeps no moving average (ema_decay=None)')
+        if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 <= decay <= 1.0:
+            raise ValueError('the decay must be a number in [0, 1], got %r' % (decay,))
+        self.ema_decay = float(decay)
+        self.ema_decay_dev.fill_(self.ema_decay)
+
+    def sync_ema(self, names=None):
+        """ema <- weights for the named slots of the arena (None: every slot): a variable restored or re-initialised behind the
+        optimizer's back starts its average from its new value."""
+        if self.ema is None:
+            raise RuntimeError('this optimizer keeps no moving average (ema_decay=None)')
+        with torch.no_grad():
+            if names is None:
+                self.ema.copy_(self.arena.flat)
+                return
+            for n in names:
+                o, k = self.arena.offsets[n]
+                self.ema[o:o + k].copy_(self.arena.flat[o:o + k])
+
     def apply(self, grad_scale=1.0, refresh=None):
         """Device half: one kernel over the arena, step size read from the device scalar (graph-capturable).
         refresh: regenerate the cached filter images of this arena behind the update, in one launch
@@ -180,8 +216,12 @@ class AdamTF(object):
         with a refresh of everything — pass True where the same capture goes on to use these filters (the critic's update in
         a one-graph iteration)."""
         self.arena.finish_step()
-        K.adam_tf(self.arena.flat, self.arena.grad, None if self.skip_m else self._m, self.v, 0.0, self.beta1, self.beta2, self.eps, grad_scale,
-                  lr_t_dev=self.lr_t_dev)
+        if self.ema is None:
+            K.adam_tf(self.arena.flat, self.arena.grad, None if self.skip_m else self._m, self.v, 0.0, self.beta1, self.beta2, self.eps, grad_scale,
+                      lr_t_dev=self.lr_t_dev)
+        else:
+            K.adam_tf_ema(self.arena.flat, self.arena.grad, None if self.skip_m else self._m, self.v, self.ema, 0.0, self.beta1, self.beta2,
+                          self.eps, grad_scale, self.ema_decay, lr_t_dev=self.lr_t_dev, ema_decay_dev=self.ema_decay_dev)
         if self.skip_m:
             self._last_scale = float(grad_scale)
             self._m_stale = True             # (an eager zero_grad between prepare() and here has formed the PREVIOUS step's moment)

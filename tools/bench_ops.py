@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """The memory-bound kernels of csrc/t2i_ops.hip (pixel_norm, nearest resize and its adjoint, pool AVG / MAX with their backward maps,
-gn, the double backward of pixel_norm and layer_norm, the minibatch standard deviation) at PGGAN-sized tensors: one JSON line per kernel with the time per call, the bytes the algorithm moves (reads + writes, from the
+gn, the double backward of pixel_norm and layer_norm, the minibatch standard deviation) at PGGAN-sized tensors, and the Adam launch with and
+without the weight EMA (`--only adam_ema`) at the sizes of two generator arenas: one JSON line per kernel with the time per call, the bytes the algorithm moves (reads + writes, from the
 shapes), bytes per second, and the ratio of that rate to a device-to-device copy that moves the SAME number of bytes (half read, half
 written), timed in the same process.  Per measurement: 10 warm-up launches, then REPS rounds of 100 back-to-back launches between
 device events, kernel and copy rounds alternating; the median round is reported.  Read the ratio, not the absolute rate, as the share
@@ -114,6 +115,30 @@ def main():
         m('minibatch_stddev_fwd G=4 F=4 (r)', shape, 4 * n, lambda: K.minibatch_stddev_fwd(x, 4, 4))
         m('minibatch_stddev_bwd G=4 F=4 (r + w)', shape, 8 * n, lambda: K.minibatch_stddev_bwd(gs, x, 4, 4))
         m('minibatch_stddev_bwd2 G=4 F=4 (2r + w)', shape, 12 * n, lambda: K.minibatch_stddev_bwd2(v, x, gs, 4, 4))
+
+    # Adam with the exponential moving average of the weights, beta1 = 0 and m = NULL as the PGGAN and wgancls
+    # optimizers run it, at the sizes of the stage-7 PGGAN generator arena and of the wgancls generator arena: the plain launch
+    # (w, g, v read; w, v written), the fused launch (+ the shadow read and written), and the plain launch followed by the same
+    # shadow update as tensor-library launches (sub, mul, sub in place: 3 reads + 1 write of an arena more than the fused form's 8 bytes)
+    for n, arena in ((23598252, 'pggan stage 7 g_arena'), (22643292, 'wgancls g_arena')):
+        w, g, v = torch.randn(n, device='cuda') * 0.05, torch.randn(n, device='cuda'), torch.rand(n, device='cuda') * 1e-2
+        s, tmp = w.clone(), torch.empty(n, device='cuda')
+        lr, dec = torch.full((4,), 2e-6, device='cuda'), torch.full((4,), 0.999, device='cuda')
+
+        def plain():
+            K.adam_tf(w, g, None, v, 0.0, 0.0, 0.99, 1e-8, 1.0, lr_t_dev=lr)
+
+        def fused():
+            K.adam_tf_ema(w, g, None, v, s, 0.0, 0.0, 0.99, 1e-8, 1.0, 0.999, lr_t_dev=lr, ema_decay_dev=dec)
+
+        def two_step():
+            plain()
+            torch.sub(s, w, out=tmp)
+            tmp.mul_(1.0 - 0.999)
+            s.sub_(tmp)
+        m('adam_ema: t2i_adam_tf beta1=0 m=NULL, %s (3r + 2w)' % arena, (n,), 20 * n, plain)
+        m('adam_ema: t2i_adam_tf_ema beta1=0 m=NULL, %s (4r + 3w)' % arena, (n,), 28 * n, fused)
+        m('adam_ema: t2i_adam_tf then sub, mul, sub_ by the tensor library, %s (8r + 5w)' % arena, (n,), 52 * n, two_step)
 
 
 if __name__ == '__main__':
