@@ -355,6 +355,24 @@ int t2i_adam_tf(float* w, const float* g, float* m, float* v, int64_t n, float l
 int t2i_adam_tf_ema(float* w, const float* g, float* m, float* v, float* ema, int64_t n, float lr_t, const float* lr_t_dev,
                     float beta1, float beta2, float eps, float grad_scale, float ema_decay, const float* ema_decay_dev,
                     t2i_stream_t stream);
+/* The same update with two multipliers per arena slot (v13, added without a version change): the arena is a sequence of n_slots
+ * slots, slot s ending (exclusive, in elements) at slot_end_dev[s]; per slot, two fp32 products are formed once,
+ *   gs = grad_scale * slot_mult_dev[2 s]       lr_s = lr_t * slot_mult_dev[2 s + 1]
+ * and the slot's elements are updated by t2i_adam_tf's statements with gs in place of grad_scale and lr_s in place of lr_t.  With
+ * every multiplier 1.0f the result is bit for bit t2i_adam_tf's (t2i_adam_tf_ema's with a shadow); with a general table it is bit
+ * for bit one such launch per slot that is handed those two products.  Training w-hat ~ N(0, 1) with Adam and using c * w-hat (the
+ * equalized learning rate) is Adam on w = c * w-hat with (grad_mult, lr_mult) = (c, c); a per-layer learning rate is (1, k).
+ * ema: NULL for no shadow, else t2i_adam_tf_ema's shadow with ema_decay / ema_decay_dev (both ignored when ema is NULL).
+ * n: a positive multiple of 4.  slot_end_dev: device int64[n_slots], 8-byte aligned, ascending, each a multiple of 4 (a float4
+ * lies in one slot), the last equal to n.  slot_mult_dev: device float[2 n_slots].  1 <= n_slots <= T2I_ADAM_MAX_SLOTS (the
+ * table is staged in LDS, 16 bytes per slot).  The tables only select multipliers: whatever they hold, no address is formed
+ * from them and the kernel stays inside the arenas; elements past the last slot end use the last slot's multipliers.  Neither
+ * table may overlap an arena.  Everything t2i_adam_tf_ema refuses is refused here in the same form (T2I_ERR_INVALID before any
+ * launch, no buffer touched); graph-capturable; the filter cache is treated as by t2i_adam_tf. */
+#define T2I_ADAM_MAX_SLOTS 2048
+int t2i_adam_tf_slots(float* w, const float* g, float* m, float* v, float* ema, int64_t n, const int64_t* slot_end_dev,
+                      const float* slot_mult_dev, int32_t n_slots, float lr_t, const float* lr_t_dev, float beta1, float beta2,
+                      float eps, float grad_scale, float ema_decay, const float* ema_decay_dev, t2i_stream_t stream);
 
 /* kt <- kt - lr * 2 (kt*wd2 - wd) * wd2, the SGD step on balance_loss = (kt*wdist2 - wdist)^2 (reference
  * models/wgancls/model.py:85,100: GradientDescentOptimizer(0.001) minimising balance_loss over kt).  wdist_sums = device

@@ -1663,6 +1663,94 @@ hipError_t adam_tf_ema_launch(float* w, const float* g, float* m, float* v, floa
   return hipGetLastError();
 }
 
+// The same update with two multipliers per arena slot (the equalized learning rate folded into Adam): slot s
+// uses gs = gscale * grad_mult_s in place of gscale and lr_s = lr_t * lr_mult_s in place of lr_t; both products are formed once per
+// slot while the table is staged in LDS, so the loop below is adam_tf_kernel's statement for statement and, given the same two fp32
+// products, writes the same bits.  Slots are 16-byte aligned: a float4 lies in one slot.  A thread's indices only grow, so its cursor
+// into the table only moves forward (binary search over the slots behind the cursor, only when the index has left the current slot).
+// The table selects multipliers and nothing else: the cursor stays in [0, n_slots - 1] whatever the table holds, and no address is
+// formed from a table value.
+template <bool EMA>
+__global__ __launch_bounds__(256) void adam_tf_slots_kernel(float* __restrict__ w, const float* __restrict__ g,
+                                                            float* __restrict__ m, float* __restrict__ v,
+                                                            float* __restrict__ ema, size_t n,
+                                                            const long long* __restrict__ slot_end,
+                                                            const float* __restrict__ slot_mult, int n_slots, float lr_val,
+                                                            const float* __restrict__ lr_dev, float b1, float b2, float eps,
+                                                            float gscale, float decay_val, const float* __restrict__ decay_dev) {
+  extern __shared__ __align__(16) unsigned char slots_lds[];
+  long long* s_end = reinterpret_cast<long long*>(slots_lds);                 // [n_slots]
+  float2* s_mul = reinterpret_cast<float2*>(s_end + n_slots);                // [n_slots]: (gs, lr_s)
+  const float lr_t = lr_dev ? *lr_dev : lr_val;
+  float omd = 0.f;
+  if (EMA) omd = 1.0f - (decay_dev ? *decay_dev : decay_val);
+  for (int s = threadIdx.x; s < n_slots; s += blockDim.x) {
+    s_end[s] = slot_end[s];
+    s_mul[s] = make_float2(gscale * slot_mult[2 * s], lr_t * slot_mult[2 * s + 1]);
+  }
+  __syncthreads();
+  const size_t n4 = n >> 2;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int last = n_slots - 1;
+  int cur = -1;
+  long long cur_end = 0;                 // the first index looks its slot up
+  float gs = 0.f, lr_s = 0.f;
+  for (size_t i = t; i < n4; i += stride) {
+    const long long e = (long long)(i << 2);
+    if (e >= cur_end && cur < last) {
+      int lo = cur + 1, hi = last;       // the first slot behind the cursor whose end lies above e; `last` if none does
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (e < s_end[mid]) hi = mid; else lo = mid + 1;
+      }
+      cur = lo;
+      cur_end = s_end[cur];
+      const float2 mu = s_mul[cur];
+      gs = mu.x; lr_s = mu.y;
+    }
+    float4 W = reinterpret_cast<float4*>(w)[i];
+    const float4 G0 = reinterpret_cast<const float4*>(g)[i];
+    float4 M = b1 != 0.f ? reinterpret_cast<float4*>(m)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 V = reinterpret_cast<float4*>(v)[i];
+    float4 E = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (EMA) E = reinterpret_cast<float4*>(ema)[i];
+    float gx = G0.x * gs, gy = G0.y * gs, gz = G0.z * gs, gw = G0.w * gs;
+    M.x = b1 * M.x + (1.f - b1) * gx; M.y = b1 * M.y + (1.f - b1) * gy;
+    M.z = b1 * M.z + (1.f - b1) * gz; M.w = b1 * M.w + (1.f - b1) * gw;
+    V.x = b2 * V.x + (1.f - b2) * gx * gx; V.y = b2 * V.y + (1.f - b2) * gy * gy;
+    V.z = b2 * V.z + (1.f - b2) * gz * gz; V.w = b2 * V.w + (1.f - b2) * gw * gw;
+    W.x -= lr_s * M.x / (sqrtf(V.x) + eps); W.y -= lr_s * M.y / (sqrtf(V.y) + eps);
+    W.z -= lr_s * M.z / (sqrtf(V.z) + eps); W.w -= lr_s * M.w / (sqrtf(V.w) + eps);
+    if (EMA) {
+      E.x = ema_step(E.x, W.x, omd); E.y = ema_step(E.y, W.y, omd);
+      E.z = ema_step(E.z, W.z, omd); E.w = ema_step(E.w, W.w, omd);
+    }
+    reinterpret_cast<float4*>(w)[i] = W;
+    if (m) reinterpret_cast<float4*>(m)[i] = M;
+    reinterpret_cast<float4*>(v)[i] = V;
+    if (EMA) reinterpret_cast<float4*>(ema)[i] = E;
+  }
+}
+
+// n is a multiple of 4 and 1 <= n_slots <= T2I_ADAM_MAX_SLOTS (the caller checked): 16 bytes of LDS per slot, 32 KiB at the cap
+hipError_t adam_tf_slots_launch(float* w, const float* g, float* m, float* v, float* ema, int64_t n, const int64_t* slot_end,
+                                const float* slot_mult, int n_slots, float lr_t, const float* lr_dev, float b1, float b2, float eps,
+                                float gscale, float decay, const float* decay_dev, hipStream_t stream) {
+  const int adam_cap = tuning().adam_blocks;
+  size_t nb = ((((size_t)n + 3) >> 2) + 255) / 256;
+  if (nb > (size_t)adam_cap) nb = adam_cap;
+  const size_t lds = (size_t)n_slots * (sizeof(long long) + sizeof(float2));
+  const long long* ends = reinterpret_cast<const long long*>(slot_end);
+  if (ema)
+    hipLaunchKernelGGL(adam_tf_slots_kernel<true>, dim3((int)nb), dim3(256), lds, stream, w, g, m, v, ema, (size_t)n, ends, slot_mult,
+                       n_slots, lr_t, lr_dev, b1, b2, eps, gscale, decay, decay_dev);
+  else
+    hipLaunchKernelGGL(adam_tf_slots_kernel<false>, dim3((int)nb), dim3(256), lds, stream, w, g, m, v, ema, (size_t)n, ends, slot_mult,
+                       n_slots, lr_t, lr_dev, b1, b2, eps, gscale, decay, decay_dev);
+  return hipGetLastError();
+}
+
 // kt <- kt - lr * d(balance_loss)/d(kt) with balance_loss = (kt*wdist2 - wdist)^2 (reference models/wgancls/model.py:85,100:
 // GradientDescentOptimizer(0.001) on kt).  wdist / wdist2 arrive as SUMS over the data-parallel ranks of the per-rank batch
 // means (scale = 1/ranks turns them into the global-batch means: the balance loss is quadratic in them, so averaging

@@ -98,6 +98,8 @@ hipError_t adam_tf_launch(float*, const float*, float*, float*, int64_t, float, 
                           hipStream_t);
 hipError_t adam_tf_ema_launch(float*, const float*, float*, float*, float*, int64_t, float, const float*, float, float, float, float,
                               float, const float*, hipStream_t);
+hipError_t adam_tf_slots_launch(float*, const float*, float*, float*, float*, int64_t, const int64_t*, const float*, int, float,
+                                const float*, float, float, float, float, float, const float*, hipStream_t);
 hipError_t kt_sgd_launch(float*, const float*, float, float, hipStream_t);
 hipError_t zero_ranges_launch(float*, const long long*, int, hipStream_t);
 hipError_t trunc_normal_launch(float*, size_t, unsigned long long, unsigned long long, float, float, float, float, hipStream_t);
@@ -1841,6 +1843,45 @@ int t2i_adam_tf_ema(float* w, const float* g, float* m, float* v, float* ema, in
   filter_cache_invalidate(w, (size_t)n * 4);          // as t2i_adam_tf: transformed filters of this arena are stale from here on
   const int rc = check(adam_tf_ema_launch(w, g, m, v, ema, n, lr_t, lr_t_dev, beta1, beta2, eps, grad_scale, ema_decay, ema_decay_dev,
                                           (hipStream_t)stream), "t2i_adam_tf_ema");
+  if (rc != T2I_OK || !tuning().cache_refresh) return rc;
+  return filter_cache_refresh(w, (size_t)n * 4, (hipStream_t)stream);
+}
+
+int t2i_adam_tf_slots(float* w, const float* g, float* m, float* v, float* ema, int64_t n, const int64_t* slot_end_dev,
+                      const float* slot_mult_dev, int32_t n_slots, float lr_t, const float* lr_t_dev, float beta1, float beta2,
+                      float eps, float grad_scale, float ema_decay, const float* ema_decay_dev, t2i_stream_t stream) {
+  if (!w || !g || !v || !slot_end_dev || !slot_mult_dev) { set_error("t2i_adam_tf_slots: bad argument (w, g, v or a slot table is NULL)"); return T2I_ERR_INVALID; }
+  if (n <= 0 || (n & 3)) { set_error("t2i_adam_tf_slots: n = %lld must be a positive multiple of 4", (long long)n); return T2I_ERR_INVALID; }
+  if (n_slots < 1 || n_slots > T2I_ADAM_MAX_SLOTS) {
+    set_error("t2i_adam_tf_slots: n_slots = %d is outside [1, %d]", (int)n_slots, (int)T2I_ADAM_MAX_SLOTS);
+    return T2I_ERR_INVALID;
+  }
+  if (!m && beta1 != 0.f) { set_error("t2i_adam_tf_slots: m may be NULL only with beta1 == 0 (the first moment is then grad * grad_scale * grad_mult)"); return T2I_ERR_INVALID; }
+  if (!(aligned16(w) && aligned16(g) && (!m || aligned16(m)) && aligned16(v) && (!ema || aligned16(ema)))) {
+    set_error("t2i_adam_tf_slots: arena and shadow must be 16-byte aligned");
+    return T2I_ERR_INVALID;
+  }
+  if (reinterpret_cast<uintptr_t>(slot_end_dev) & 7) { set_error("t2i_adam_tf_slots: slot_end_dev must be 8-byte aligned"); return T2I_ERR_INVALID; }
+  const uintptr_t bytes = (uintptr_t)n * 4;
+  const void* arenas[5] = {w, g, m, v, ema};
+  auto overlaps = [](const void* a, uintptr_t na, const void* b, uintptr_t nb) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a && b && a0 < b0 + nb && b0 < a0 + na;
+  };
+  for (int i = 0; i < 4; ++i)
+    if (overlaps(ema, bytes, arenas[i], bytes)) { set_error("t2i_adam_tf_slots: ema overlaps w, g, m or v"); return T2I_ERR_INVALID; }
+  for (const void* a : arenas)
+    if (overlaps(slot_end_dev, (uintptr_t)n_slots * 8, a, bytes) || overlaps(slot_mult_dev, (uintptr_t)n_slots * 8, a, bytes)) {
+      set_error("t2i_adam_tf_slots: a slot table overlaps an arena");
+      return T2I_ERR_INVALID;
+    }
+  if (ema && !ema_decay_dev && !(ema_decay >= 0.f && ema_decay <= 1.f)) {
+    set_error("t2i_adam_tf_slots: ema_decay %g is outside [0, 1]", (double)ema_decay);
+    return T2I_ERR_INVALID;
+  }
+  filter_cache_invalidate(w, (size_t)n * 4);          // as t2i_adam_tf: transformed filters of this arena are stale from here on
+  const int rc = check(adam_tf_slots_launch(w, g, m, v, ema, n, slot_end_dev, slot_mult_dev, (int)n_slots, lr_t, lr_t_dev, beta1, beta2,
+                                            eps, grad_scale, ema_decay, ema_decay_dev, (hipStream_t)stream), "t2i_adam_tf_slots");
   if (rc != T2I_OK || !tuning().cache_refresh) return rc;
   return filter_cache_refresh(w, (size_t)n * 4, (hipStream_t)stream);
 }

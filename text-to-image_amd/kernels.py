@@ -1101,6 +1101,33 @@ def adam_tf_ema(w, g, m, v, ema, lr_t, beta1, beta2, eps=1e-8, grad_scale=1.0, e
               't2i_adam_tf_ema')
 
 
+ADAM_MAX_SLOTS = 2048      # T2I_ADAM_MAX_SLOTS (include/t2i_hip.h)
+
+
+def adam_tf_slots(w, g, m, v, slot_end, slot_mult, lr_t, beta1, beta2, eps=1e-8, grad_scale=1.0, ema=None, ema_decay=0.999, lr_t_dev=None,
+                  ema_decay_dev=None):
+    """adam_tf (ema=None) / adam_tf_ema with two multipliers per arena slot: slot s, ending at element slot_end[s] (device int64
+    [n_slots], ascending multiples of 4, the last == w.numel()), steps with grad_scale * slot_mult[s, 0] and lr_t * slot_mult[s, 1]
+    (device float32 [n_slots, 2]).  All ones: the bits of adam_tf / adam_tf_ema."""
+    for t in (w, g, v) + ((m,) if m is not None else ()):
+        _chk(t)
+    if ema is not None:
+        _chk(ema, 'ema', f32=True)
+    _chk(slot_mult, 'slot_mult', f32=True)
+    if slot_end.dtype != torch.int64:
+        raise TypeError('slot_end must be int64, got %s' % slot_end.dtype)
+    if not slot_end.is_contiguous():
+        raise ValueError('slot_end must be contiguous (shape %s, strides %s)' % (tuple(slot_end.shape), slot_end.stride()))
+    assert w.numel() == g.numel() == v.numel() and (m is None or m.numel() == w.numel()) and (ema is None or ema.numel() == w.numel())
+    assert m is not None or beta1 == 0.0, 'the first moment can be skipped only with beta1 == 0'
+    assert slot_end.dim() == 1 and slot_mult.numel() == 2 * slot_end.numel() and slot_end.device == w.device == slot_mult.device
+    if _live(w):
+        check(lib.t2i_adam_tf_slots(_ptr(w), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), w.numel(), _ptr(slot_end), _ptr(slot_mult),
+                                    int(slot_end.numel()), lr_t, _ptr(lr_t_dev), beta1, beta2, eps, grad_scale, ema_decay,
+                                    _ptr(ema_decay_dev), _stream()),
+              't2i_adam_tf_slots')
+
+
 def device_info(device=0):
     cu, clk = ctypes.c_int32(0), ctypes.c_int32(0)
     arch = ctypes.create_string_buffer(64)

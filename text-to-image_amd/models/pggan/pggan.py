@@ -10,7 +10,12 @@ under differentiation — the critic is differentiated twice), the fade-in mix; 
 reference; default None = the reference's critic) normalises the critic's 3x3 / 4x4 convolutions per sample; `critic_mbstd=G` (not in the
 reference either; default None) puts the progressive-growing paper's minibatch standard deviation in front of the critic's last block
 (DESIGN.md section 4.29); `g_ema=D` (the paper's `Gs`; default None) keeps an exponential moving average of the generator's weights, formed in
-the generator's Adam launch, that checkpoints carry and `ema_weights()` / `--ema` sample from.  Reference specifics kept: penalty
+the generator's Adam launch, that checkpoints carry and `ema_weights()` / `--ema` sample from (DESIGN.md section 4.30);
+`equalized_lr=True` (the paper's equalized learning rate; default False) draws every conv2d / fc kernel from N(0, c^2), c = sqrt(2 / fan_in),
+not truncated, and gives both optimizers the per-slot multipliers (c, c) for it: Adam on w-hat ~ N(0, 1) used as c * w-hat, restated on
+w = c * w-hat itself, so the convolutions, the checkpoints and the readers see plain weights.  The gain is sqrt(2)
+for every layer: the paper's gain 1 on the last linear layers (to_rgb's 1x1, the critic's last dense) is deliberately left out.  Biases and
+the layer-norm gamma / beta keep the multiplier 1.  `adam_lr=L` sets Adam's step size (default None: the reference's 2e-6).  Reference specifics kept: penalty
 coefficient 200, no kt term, G = -D_fake + 5 KL, Adam(2e-6, beta1=0, beta2=0.99) hard-coded (pggan.py:104-110; the
 `learning_rate` placeholder is fed but unused), eps of x_hat drawn in-graph (pggan.py:68 overrides the placeholder),
 `to_rgb` = k2 s1 SAME 9-channel relu conv + 1x1, every kernel He-initialised by utils/ops.py's defaults.
@@ -20,6 +25,7 @@ alpha: the reference assigns `alpha_tra = iter / steps` under a control dependen
 whether the critic step's own forward sees the new or the previous value is a TF scheduling race.  Here alpha is set
 from `iter` BEFORE the critic step and kept for the generator step and the sampler — the assign-first order."""
 import contextlib
+import math
 import sys
 import time
 
@@ -35,7 +41,13 @@ from ...utils.ops import concat_tile, conv2d, fc, layer_norm, lerp, lrelu_act, m
 class PGGAN(object):
     def __init__(self, batch_size, steps, check_dir_write, check_dir_read, dataset, sample_path, log_dir, stage, trans,
                  build_model=True, device=None, seed=0, store=None, fmap_base=1024, fmap_max=512, z_dim=128, embed_dim=1024,
-                 compr_embed_dim=128, dp=None, critic_norm=None, critic_mbstd=None, g_ema=None):
+                 compr_embed_dim=128, dp=None, critic_norm=None, critic_mbstd=None, g_ema=None, equalized_lr=False, adam_lr=None):
+        if adam_lr is not None and (isinstance(adam_lr, bool) or not isinstance(adam_lr, (int, float)) or not (math.isfinite(adam_lr) and adam_lr > 0.0)):
+            raise ValueError("adam_lr must be None (the reference's 2e-6) or a finite step size > 0, got %r" % (adam_lr,))
+        self.adam_lr = 0.000002 if adam_lr is None else float(adam_lr)
+        if not isinstance(equalized_lr, bool):
+            raise ValueError('equalized_lr must be True or False, got %r' % (equalized_lr,))
+        self.equalized_lr = equalized_lr
         if g_ema is not None and (isinstance(g_ema, bool) or not isinstance(g_ema, (int, float)) or not 0.0 < g_ema < 1.0):
             raise ValueError("g_ema must be None or a decay in (0, 1) (the moving average of the generator's weights), got %r" % (g_ema,))
         self.g_ema = None if g_ema is None else float(g_ema)
@@ -108,9 +120,32 @@ class PGGAN(object):
     def define_losses(self):
         """pggan.py:84-130 (the optimizers; the loss expressions are in d_losses / g_losses)."""
         self.gp_coeff, self.kl_coeff = 200.0, 5.0
-        self.D_optimizer = optim.AdamTF(self.d_arena, 0.0, 0.99)
-        self.G_optimizer = optim.AdamTF(self.g_arena, 0.0, 0.99, ema_decay=self.g_ema)      # (None: no shadow, the plain launch)
-        self.adam_lr = 0.000002
+        self.D_optimizer = optim.AdamTF(self.d_arena, 0.0, 0.99, slot_scales=self.kernel_scales(self.d_vars))
+        self.G_optimizer = optim.AdamTF(self.g_arena, 0.0, 0.99, ema_decay=self.g_ema,       # (None: no shadow, the plain launch)
+                                        slot_scales=self.kernel_scales(self.g_vars))
+
+    def kernel_scales(self, variables):
+        """equalized_lr: name -> c = sqrt(2 / fan_in) for every conv2d (`weights` [kh, kw, Cin, f]) and fc (`kernel` [in, units])
+        kernel among `variables`, the fan_in utils/ops.py initialises them with; None without the flag (the plain Adam launches)."""
+        if not self.equalized_lr:
+            return None
+        scales = {}
+        for n, v in variables.items():
+            if n.endswith('/weights') and v.dim() == 4:
+                scales[n] = math.sqrt(2.0 / (v.shape[0] * v.shape[1] * v.shape[2]))
+            elif n.endswith('/kernel') and v.dim() == 2:
+                scales[n] = math.sqrt(2.0 / v.shape[0])
+        return scales
+
+    def _init(self, fan_in):
+        """The kernel initialiser handed to conv2d / fc: None (their He default) or, with equalized_lr, N(0, 2 / fan_in)."""
+        return S.normal_init(math.sqrt(2.0 / fan_in)) if self.equalized_lr else None
+
+    def _conv2d(self, x, f, ks, **kw):
+        return conv2d(x, f=f, ks=ks, init=self._init(ks[0] * ks[1] * x.shape[-1]), **kw)
+
+    def _fc(self, x, units, **kw):
+        return fc(x, units=units, init=self._init(x.shape[-1]), **kw)
 
     def _noise(self, feed, key, like):
         n = feed.get(key)
@@ -290,13 +325,13 @@ class PGGAN(object):
                 if i == stages - 1 and t:
                     x = lerp(x_iden, x, alpha_trans)              # alpha * x + (1 - alpha) * x_iden
             with S.variable_scope(self.get_conv_scope_name(0), reuse=reuse):
-                cond_compress = fc(cond, units=self.compr_embed_dim, act=act)
+                cond_compress = self._fc(cond, units=self.compr_embed_dim, act=act)
                 if self.mbstd_group is not None:        # [features | tiled compressed cond | tiled stat], the stat channels last
                     cond_compress = torch.cat([cond_compress, minibatch_stddev_stat(x, self.mbstd_group, self.mbstd_features(x.shape[-1]))], 1)
                 concat = self.concat_cond4(x, cond_compress)
                 x_b1 = self._d_conv(concat, self.get_dnf(0), (3, 3), 'SAME', act)
                 x_b1 = self._d_conv(x_b1, self.get_dnf(0), (4, 4), 'VALID', act)
-                output_b1 = fc(x_b1.reshape(x_b1.shape[0], -1), units=1)      # dense on the [B,1,1,C] map
+                output_b1 = self._fc(x_b1.reshape(x_b1.shape[0], -1), units=1)      # dense on the [B,1,1,C] map
             return output_b1.reshape(-1)
 
     def _d_conv(self, x, f, ks, padding, act):
@@ -304,8 +339,8 @@ class PGGAN(object):
         without activation, then the per-sample normalisation with the lrelu fused — the normalised critic of the WGAN-GP and PGGAN
         papers (batch norm would couple the samples under the per-sample penalty); both are differentiable twice."""
         if self.critic_norm is None:
-            return conv2d(x, f=f, ks=ks, s=(1, 1), padding=padding, act=act)
-        x = conv2d(x, f=f, ks=ks, s=(1, 1), padding=padding, act=None)
+            return self._conv2d(x, f=f, ks=ks, s=(1, 1), padding=padding, act=act)
+        x = self._conv2d(x, f=f, ks=ks, s=(1, 1), padding=padding, act=None)
         return layer_norm(x, act=act) if self.critic_norm == 'layer' else pixel_norm(x, act=act)
 
     def generator(self, z_var, cond_inp, stages, t, reuse=False, cond_noise=True):
@@ -316,12 +351,12 @@ class PGGAN(object):
                 mean_lr, log_sigma_lr = self.generate_conditionals(cond_inp)
                 cond = self.sample_normal_conditional(mean_lr, log_sigma_lr, cond_noise)
                 x = torch.cat([z_var, cond], 1)
-                x = fc(x, units=4 * 4 * self.get_nf(0))
+                x = self._fc(x, units=4 * 4 * self.get_nf(0))
                 x = layer_norm(x)
                 x = x.reshape(-1, 4, 4, self.get_nf(0))
-                x = conv2d(x, f=self.get_nf(0), ks=(3, 3), s=(1, 1))
+                x = self._conv2d(x, f=self.get_nf(0), ks=(3, 3), s=(1, 1))
                 x = layer_norm(x, act=relu)
-                x = conv2d(x, f=self.get_nf(0), ks=(3, 3), s=(1, 1))
+                x = self._conv2d(x, f=self.get_nf(0), ks=(3, 3), s=(1, 1))
                 x = layer_norm(x, act=relu)
             x_iden = None
             for i in range(1, stages):
@@ -330,9 +365,9 @@ class PGGAN(object):
                     x_iden = upscale(x_iden, 2)
                 with S.variable_scope(self.get_conv_scope_name(i), reuse=reuse):
                     x = upscale(x, 2)
-                    x = conv2d(x, f=self.get_nf(i), ks=(3, 3), s=(1, 1))
+                    x = self._conv2d(x, f=self.get_nf(i), ks=(3, 3), s=(1, 1))
                     x = layer_norm(x, act=relu)
-                    x = conv2d(x, f=self.get_nf(i), ks=(3, 3), s=(1, 1))
+                    x = self._conv2d(x, f=self.get_nf(i), ks=(3, 3), s=(1, 1))
                     x = layer_norm(x, act=relu)
             x = self.to_rgb(x, stages - 1)
             if t:
@@ -362,17 +397,17 @@ class PGGAN(object):
 
     def from_rgb(self, x, stage):
         with S.variable_scope(self.get_rgb_name(stage), reuse=S.default_store().reuse()):
-            return conv2d(x, f=self.get_dnf(stage), ks=(1, 1), s=(1, 1), act=lrelu_act())
+            return self._conv2d(x, f=self.get_dnf(stage), ks=(1, 1), s=(1, 1), act=lrelu_act())
 
     def to_rgb(self, x, stage):
         with S.variable_scope(self.get_rgb_name(stage), reuse=S.default_store().reuse()):
-            x = conv2d(x, f=9, ks=(2, 2), s=(1, 1), act=relu)
-            return conv2d(x, f=3, ks=(1, 1), s=(1, 1))
+            x = self._conv2d(x, f=9, ks=(2, 2), s=(1, 1), act=relu)
+            return self._conv2d(x, f=3, ks=(1, 1), s=(1, 1))
 
     def generate_conditionals(self, embeddings, units=None):
         units = units or self.compr_embed_dim
         with K.f32_outputs():          # conditioning statistics stay fp32 in every storage mode
-            return fc(embeddings, units, act=lrelu_act()), fc(embeddings, units, act=lrelu_act())
+            return self._fc(embeddings, units, act=lrelu_act()), self._fc(embeddings, units, act=lrelu_act())
 
     def sample_normal_conditional(self, mean, log_sigma, cond_noise=True):
         if not cond_noise:

@@ -5,6 +5,7 @@ gradients, first and second moments in three more buffers of the same shape.  A 
 over ~29 M (critic) / ~23 M (generator) floats instead of one launch per tensor, and data-parallel gradient exchange
 works on contiguous slices of the gradient arena (dp.py)."""
 import math
+import numbers
 from collections import OrderedDict
 
 import torch
@@ -125,17 +126,24 @@ class AdamTF(object):
     ema_decay (default None: no shadow, the plain update): a float in (0, 1) keeps `ema`, tf.train.ExponentialMovingAverage of the
     weights — a flat fp32 buffer of the arena's layout that starts as a copy of the weights (TF initialises a shadow to its
     variable's value) and is advanced by every step, in the update's own launch: ema -= (1 - decay) * (ema - w_new)
-    (DESIGN.md section 4.30)."""
+    (DESIGN.md section 4.30).
+    slot_scales (default None: the plain launches, nothing allocated): a mapping variable name -> c or -> (grad_mult, lr_mult); the
+    variable then steps with its gradient times grad_mult and its step size times lr_mult, in one launch over the arena
+    (t2i_adam_tf_slots).  Variables not named keep (1, 1).  c for both is the equalized learning rate: Adam on
+    w-hat ~ N(0, 1) used as w = c * w-hat, restated on w itself; (1, k) is a per-layer learning-rate multiplier."""
 
     ema = None
+    slot_end = slot_mult = slot_scales = None
 
-    def __init__(self, arena, beta1=0.9, beta2=0.999, eps=1e-8, ema_decay=None):
+    def __init__(self, arena, beta1=0.9, beta2=0.999, eps=1e-8, ema_decay=None, slot_scales=None):
         if ema_decay is not None:
             if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 < ema_decay < 1.0:
                 raise ValueError('ema_decay must be None or a number in (0, 1), got %r' % (ema_decay,))
             ema_decay = float(ema_decay)
         self.arena, self.beta1, self.beta2, self.eps = arena, beta1, beta2, eps
         self.ema_decay = ema_decay
+        if slot_scales is not None:
+            self._build_slot_tables(slot_scales)
         if ema_decay is not None:
             self.ema = arena.flat.detach().clone()
             self.ema_decay_dev = torch.full((4,), ema_decay, dtype=torch.float32, device=arena.flat.device)   # [0] = the decay
@@ -152,6 +160,30 @@ class AdamTF(object):
             import weakref
             arena.before_zero = tuple(arena.before_zero) + (weakref.ref(self),)
 
+    def _build_slot_tables(self, slot_scales):
+        """The two device tables of t2i_adam_tf_slots, once: slot_end[s] = the padded end of the arena's s-th variable (the next
+        variable's offset; the arena's size for the last), slot_mult[s] = (grad_mult, lr_mult)."""
+        arena = self.arena
+        mults = OrderedDict((n, (1.0, 1.0)) for n in arena.names)
+        for name, c in dict(slot_scales).items():
+            if name not in mults:
+                raise KeyError('slot_scales names %r, which is not a variable of this arena' % (name,))
+            pair = tuple(c) if isinstance(c, (tuple, list)) else (c, c)
+            if len(pair) != 2:
+                raise ValueError('slot_scales[%r] must be a number or (grad_mult, lr_mult), got %r' % (name, c))
+            for x in pair:
+                if isinstance(x, bool) or not isinstance(x, numbers.Real) or not (math.isfinite(x) and x > 0.0):
+                    raise ValueError('slot_scales[%r]: a multiplier must be a finite number > 0, got %r' % (name, x))
+            mults[name] = (float(pair[0]), float(pair[1]))
+        if len(mults) > K.ADAM_MAX_SLOTS:
+            raise ValueError('slot_scales: the arena has %d variables, one launch takes at most %d slots' % (len(mults), K.ADAM_MAX_SLOTS))
+        ends = [o + (k + 3) // 4 * 4 for o, k in arena.offsets.values()]
+        assert ends[-1] == arena.numel
+        dev = arena.flat.device
+        self.slot_end = torch.tensor(ends, dtype=torch.int64, device=dev)
+        self.slot_mult = torch.tensor([list(p) for p in mults.values()], dtype=torch.float32, device=dev)
+        self.slot_scales = mults
+
     @property
     def m(self):
         """First moment.  With the beta1 == 0 fast path it is (re)built from the gradient arena on access (see __init__): the arena
@@ -159,7 +191,15 @@ class AdamTF(object):
         them (_materialize_m), so a checkpoint taken after a stray zero_grad / backward still holds the last step's moment."""
         if self.skip_m and self._m_stale:
             with torch.no_grad():
-                torch.mul(self.arena.grad, self._last_scale, out=self._m)
+                if self.slot_end is None:
+                    torch.mul(self.arena.grad, self._last_scale, out=self._m)
+                else:          # per slot what the launch would have written: g * fl32(grad_scale * grad_mult_s)
+                    import numpy as np
+                    start = 0
+                    for end, (gm, _) in zip(self.slot_end.tolist(), self.slot_scales.values()):
+                        gs = float(np.float32(self._last_scale) * np.float32(gm))
+                        torch.mul(self.arena.grad[start:end], gs, out=self._m[start:end])
+                        start = end
             self._m_stale = False
         return self._m
 
@@ -216,7 +256,11 @@ class AdamTF(object):
         with a refresh of everything — pass True where the same capture goes on to use these filters (the critic's update in
         a one-graph iteration)."""
         self.arena.finish_step()
-        if self.ema is None:
+        if self.slot_end is not None:
+            K.adam_tf_slots(self.arena.flat, self.arena.grad, None if self.skip_m else self._m, self.v, self.slot_end, self.slot_mult, 0.0,
+                            self.beta1, self.beta2, self.eps, grad_scale, ema=self.ema, ema_decay=0.0 if self.ema is None else self.ema_decay,
+                            lr_t_dev=self.lr_t_dev, ema_decay_dev=None if self.ema is None else self.ema_decay_dev)
+        elif self.ema is None:
             K.adam_tf(self.arena.flat, self.arena.grad, None if self.skip_m else self._m, self.v, 0.0, self.beta1, self.beta2, self.eps, grad_scale,
                       lr_t_dev=self.lr_t_dev)
         else:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """The memory-bound kernels of csrc/t2i_ops.hip (pixel_norm, nearest resize and its adjoint, pool AVG / MAX with their backward maps,
 gn, the double backward of pixel_norm and layer_norm, the minibatch standard deviation) at PGGAN-sized tensors, and the Adam launch with and
-without the weight EMA (`--only adam_ema`) at the sizes of two generator arenas: one JSON line per kernel with the time per call, the bytes the algorithm moves (reads + writes, from the
+without the weight EMA (`--only adam_ema`) and with per-slot multipliers (`--only adam_slots`) at the sizes of two generator arenas: one JSON line per kernel with the time per call, the bytes the algorithm moves (reads + writes, from the
 shapes), bytes per second, and the ratio of that rate to a device-to-device copy that moves the SAME number of bytes (half read, half
 written), timed in the same process.  Per measurement: 10 warm-up launches, then REPS rounds of 100 back-to-back launches between
 device events, kernel and copy rounds alternating; the median round is reported.  Read the ratio, not the absolute rate, as the share
@@ -139,6 +139,35 @@ def main():
         m('adam_ema: t2i_adam_tf beta1=0 m=NULL, %s (3r + 2w)' % arena, (n,), 20 * n, plain)
         m('adam_ema: t2i_adam_tf_ema beta1=0 m=NULL, %s (4r + 3w)' % arena, (n,), 28 * n, fused)
         m('adam_ema: t2i_adam_tf then sub, mul, sub_ by the tensor library, %s (8r + 5w)' % arena, (n,), 52 * n, two_step)
+
+    # Adam with per-slot multipliers at the same two arena sizes, against the launch it stands in for, in the same
+    # process: the new launch moves the same bytes, so its time against that launch is the comparison.  The table is the slot layout and the
+    # equalized-learning-rate multipliers of the stage-7 (transition) PGGAN generator arena; for the wgancls size the same slot ends are
+    # cut off at the arena's size.
+    if a.only in 'adam_slots':
+        from t2i_amd.models.pggan.pggan import PGGAN
+        pg = PGGAN(8, 100, None, None, None, None, None, 7, True, device='cpu', equalized_lr=True)
+        ends_pg, mult_pg = pg.G_optimizer.slot_end.tolist(), pg.G_optimizer.slot_mult.tolist()
+        del pg
+        for n, arena in ((23598252, 'pggan stage 7 g_arena'), (22643292, 'wgancls g_arena')):
+            keep = [i for i, e in enumerate(ends_pg) if e < n]
+            ends = [ends_pg[i] for i in keep] + [n]
+            mult = [mult_pg[i] for i in keep] + [mult_pg[len(keep)] if len(keep) < len(mult_pg) else [1.0, 1.0]]
+            slot_end = torch.tensor(ends, dtype=torch.int64, device='cuda')
+            slot_mult = torch.tensor(mult, dtype=torch.float32, device='cuda')
+            w, g, v = torch.randn(n, device='cuda') * 0.05, torch.randn(n, device='cuda'), torch.rand(n, device='cuda') * 1e-2
+            s = w.clone()
+            lr, dec = torch.full((4,), 2e-6, device='cuda'), torch.full((4,), 0.999, device='cuda')
+            tag = '%s, %d slots' % (arena, len(ends))
+            m('adam_slots: t2i_adam_tf beta1=0 m=NULL, %s (3r + 2w)' % arena, (n,), 20 * n,
+              lambda: K.adam_tf(w, g, None, v, 0.0, 0.0, 0.99, 1e-8, 1.0, lr_t_dev=lr))
+            m('adam_slots: t2i_adam_tf_slots beta1=0 m=NULL, %s (3r + 2w)' % tag, (n,), 20 * n,
+              lambda: K.adam_tf_slots(w, g, None, v, slot_end, slot_mult, 0.0, 0.0, 0.99, 1e-8, 1.0, lr_t_dev=lr))
+            m('adam_slots: t2i_adam_tf_ema beta1=0 m=NULL, %s (4r + 3w)' % arena, (n,), 28 * n,
+              lambda: K.adam_tf_ema(w, g, None, v, s, 0.0, 0.0, 0.99, 1e-8, 1.0, 0.999, lr_t_dev=lr, ema_decay_dev=dec))
+            m('adam_slots: t2i_adam_tf_slots + shadow beta1=0 m=NULL, %s (4r + 3w)' % tag, (n,), 28 * n,
+              lambda: K.adam_tf_slots(w, g, None, v, slot_end, slot_mult, 0.0, 0.0, 0.99, 1e-8, 1.0, ema=s, ema_decay=0.999, lr_t_dev=lr,
+                                      ema_decay_dev=dec))
 
 
 if __name__ == '__main__':
