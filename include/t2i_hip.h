@@ -715,6 +715,54 @@ int t2i_gn_fwd(const float* x, int64_t n, float log_m, uint64_t seed, uint64_t o
 /* y = a * b, n elements: the backward (and every further derivative) of gn. */
 int t2i_mul(const float* a, const float* b, int64_t n, float* y, t2i_stream_t stream);
 
+/* ---- sliced Wasserstein distance of Laplacian-pyramid patch descriptors (Karras et al., progressive growing of GANs; the reference
+ * has no such metric).  Added within ABI v13: no existing argument list changed.  fp32 tensors, C in 1..4, every tensor below 2^31
+ * elements.  No atomics: every sum in a fixed order, results bitwise identical from call to call; every entry only enqueues kernels
+ * on `stream` (capturable).  Bad arguments (a NULL or misaligned pointer, a non-positive size, overlapping input / output /
+ * workspace ranges, and what each entry names) return T2I_ERR_INVALID, a workspace that is NULL, misaligned (16 bytes) or smaller
+ * than its query T2I_ERR_WORKSPACE, before anything is launched. ------------------------------------------------------------- */
+/* x [N, H, W, C] -> out: the `levels` levels back to back, level i = [N, H >> i, W >> i, C] at element offset
+ * N * C * sum_{j < i} (H >> j)(W >> j).  With k = [1, 4, 6, 4, 1] / 16, F = outer(k, k), g_0 = x:
+ * g_{i+1} = convolve(g_i, F, 'mirror')[::2, ::2] (scipy.ndimage's mirror: reflection about the centre of the edge pixel),
+ * lap_i = g_i - convolve(zero_insert_x2(g_{i+1}), 4 F, 'mirror') for i < levels - 1 and lap_{levels-1} = g_{levels-1}.  The
+ * filters run separably in fp32 (rows then columns of an LDS tile; the up-sampling in its polyphase form), the Gaussian chain
+ * g_1 .. g_{levels-2} lives in the workspace.  H and W must be multiples of 2^(levels-1) with H >> (levels-1) and W >> (levels-1)
+ * at least 7; N <= 65535.  levels == 1 copies x. */
+size_t t2i_laplacian_pyramid_workspace_bytes(int64_t N, int32_t H, int32_t W, int32_t C, int32_t levels);
+int t2i_laplacian_pyramid(const float* x, int64_t N, int32_t H, int32_t W, int32_t C, int32_t levels, float* out, void* ws,
+                          size_t ws_bytes, t2i_stream_t stream);
+/* Rows row0 + n P + p of the descriptor store out [rows_total, 49 C]: the 7 x 7 x C neighbourhood of level [N, h, w, C] around
+ * (y, x) = pos[n, p] (int32 [N, P, 2]), flattened in the order (c, dy, dx).  A pure gather, bit-exact.  Centres belong in
+ * [3, side - 3); the kernel clamps them into that range, so no address is formed from an unchecked value.  row0 + N P <=
+ * rows_total. */
+int t2i_swd_descriptors(const float* level, int64_t N, int32_t h, int32_t w, int32_t C, const int32_t* pos, int32_t P, float* out,
+                        int64_t row0, int64_t rows_total, t2i_stream_t stream);
+/* mean64[c], std64[c] (fp64 [C]) of channel c of A [rows, 49 C]: over all rows and the channel's 49 columns, the mean and the
+ * population standard deviation (ddof 0).  Two passes in fp64, the mean and then the centred squares, each leaving at most 1024
+ * per-workgroup partials that one workgroup folds in a fixed order (four launches). */
+size_t t2i_swd_channel_stats_workspace_bytes(int64_t rows, int32_t C);
+int t2i_swd_channel_stats(const float* A, int64_t rows, int32_t C, double* mean64, double* std64, void* ws, size_t ws_bytes,
+                          t2i_stream_t stream);
+/* out[s][r] = sum_j ((A[r][j] - mean64[c(j)]) / std64[c(j)]) dirs[j][s], c(j) = j / 49, for A [rows, 49 C], dirs fp32 [49 C, S],
+ * out fp32 [S, rows_pad]: the operand is standardised in fp64 as it is loaded and rounded once to fp32 (the standardised matrix
+ * never exists in memory), then one fp32 fma chain over j in order.  The output is transposed, so a slice is one contiguous run;
+ * entries rows <= r < rows_pad are +inf.  rows_pad: a power of two >= rows.  std64 must be non-zero (the caller checks). */
+int t2i_swd_project(const float* A, int64_t rows, int32_t C, const double* mean64, const double* std64, const float* dirs, int32_t S,
+                    float* out, int64_t rows_pad, t2i_stream_t stream);
+/* Ascending bitonic sort of every segment of data [segments, len], in place; len a power of two, segments <= 65535 (a grid
+ * dimension), data 16-byte aligned.  Chunks of T2I_SORT_CHUNK floats are sorted entirely in LDS by one launch; for each larger
+ * merge size, global compare-exchange passes (16-byte accesses, up to three strides per pass) take the strides >= the chunk and
+ * one LDS launch finishes all strides below it.  Inputs hold no NaN by contract (there is no NaN policy); +inf is legal and sorts
+ * last.  t2i_segmented_sort_chunk() returns T2I_SORT_CHUNK. */
+#define T2I_SORT_CHUNK 4096
+int32_t t2i_segmented_sort_chunk(void);
+int t2i_segmented_sort_f32(float* data, int32_t segments, int64_t len, t2i_stream_t stream);
+/* out64[0] = (sum over segments and the first `rows` entries of each of |a - b|) / (segments * rows), a and b fp32
+ * [segments, len], in fp64 and in a fixed order (two launches).  Entries rows <= r < len (the padding) are never read. */
+size_t t2i_sorted_l1_mean_workspace_bytes(int32_t segments, int64_t rows);
+int t2i_sorted_l1_mean(const float* a, const float* b, int32_t segments, int64_t len, int64_t rows, double* out64, void* ws,
+                       size_t ws_bytes, t2i_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,16 @@ SIGNATURES = {
     't2i_pool_same_take': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p]),
     't2i_gn_fwd': (ctypes.c_int, [_p, _i64, _f, ctypes.c_uint64, ctypes.c_uint64, _p, _p, _p]),
     't2i_mul': (ctypes.c_int, [_p, _p, _i64, _p, _p]),
+    't2i_laplacian_pyramid_workspace_bytes': (_sz, [_i64, _i32, _i32, _i32, _i32]),
+    't2i_laplacian_pyramid': (ctypes.c_int, [_p, _i64, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),
+    't2i_swd_descriptors': (ctypes.c_int, [_p, _i64, _i32, _i32, _i32, _p, _i32, _p, _i64, _i64, _p]),
+    't2i_swd_channel_stats_workspace_bytes': (_sz, [_i64, _i32]),
+    't2i_swd_channel_stats': (ctypes.c_int, [_p, _i64, _i32, _p, _p, _p, _sz, _p]),
+    't2i_swd_project': (ctypes.c_int, [_p, _i64, _i32, _p, _p, _p, _i32, _p, _i64, _p]),
+    't2i_segmented_sort_chunk': (_i32, []),
+    't2i_segmented_sort_f32': (ctypes.c_int, [_p, _i32, _i64, _p]),
+    't2i_sorted_l1_mean_workspace_bytes': (_sz, [_i32, _i64]),
+    't2i_sorted_l1_mean': (ctypes.c_int, [_p, _p, _i32, _i64, _i64, _p, _p, _sz, _p]),
 }
 
 if not os.path.exists(LIB_PATH):

@@ -70,6 +70,18 @@ hipError_t gram_accumulate_launch(const float*, int, int, const float*, double*,
 hipError_t cosine_distance_launch(const float*, int64_t, const float*, int64_t, int64_t, int, double*, hipStream_t);
 size_t bytescale_nearest_ws(int64_t N, int64_t per);
 hipError_t bytescale_nearest_launch(const float*, int64_t, int, int, int, int, uint8_t*, void*, hipStream_t);
+// implemented in t2i_swd.hip
+size_t pyramid_level_elems(int64_t N, int H, int W, int C, int i);
+size_t laplacian_pyramid_ws(int64_t N, int H, int W, int C, int levels);
+hipError_t laplacian_pyramid_launch(const float*, int64_t, int, int, int, int, float*, void*, hipStream_t);
+hipError_t swd_descriptors_launch(const float*, int64_t, int, int, int, const int32_t*, int, float*, int64_t, hipStream_t);
+size_t swd_channel_stats_ws(int64_t rows, int C);
+hipError_t swd_channel_stats_launch(const float*, int64_t, int, double*, double*, void*, hipStream_t);
+hipError_t swd_project_launch(const float*, int64_t, int, const double*, const double*, const float*, int, float*, int64_t, hipStream_t);
+int segmented_sort_chunk();
+hipError_t segmented_sort_launch(float*, int, int64_t, hipStream_t);
+size_t sorted_l1_mean_ws(int segments, int64_t rows);
+hipError_t sorted_l1_mean_launch(const float*, const float*, int, int64_t, int64_t, double*, void*, hipStream_t);
 // implemented in t2i_preprocess.hip
 int pillow_table_taps(int filter, int in_size, int out_size);
 hipError_t pillow_tables_launch(int, const int32_t*, int64_t, int, int32_t*, int32_t*, int, hipStream_t);
@@ -1984,6 +1996,162 @@ size_t t2i_conv2d_input_transform_bytes(const t2i_conv_desc* d) {
   if (!d || validate_desc(d)) return 0;
   if (!((d->Cin % 4) == 0 && (d->Cout % 4) == 0)) return 0;
   return xform_bytes(*d);
+}
+
+// ---- sliced Wasserstein distance (t2i_swd.hip) -----------------------------------------------------------------------------------
+static inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+static inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+static inline bool swd_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a && b && na && nb && a0 < b0 + nb && b0 < a0 + na;
+}
+static const int64_t kSwdLim = ((int64_t)1 << 31) - 1;          // elements of one tensor: the kernels' row and tile indices are int32
+
+// N * H * W * C within kSwdLim, formed factor by factor; N is a grid extent
+static bool pyramid_shape_ok(int64_t N, int32_t H, int32_t W, int32_t C, int32_t levels) {
+  if (N <= 0 || N > 65535 || H <= 0 || W <= 0 || C < 1 || C > 4 || levels < 1 || levels > 24) return false;
+  const int32_t m = (1 << (levels - 1)) - 1;
+  if ((H & m) || (W & m) || (H >> (levels - 1)) < 7 || (W >> (levels - 1)) < 7) return false;
+  return (int64_t)H * W <= kSwdLim / C && N <= kSwdLim / ((int64_t)H * W * C);
+}
+
+static size_t pyramid_out_elems(int64_t N, int32_t H, int32_t W, int32_t C, int32_t levels) {
+  size_t e = 0;
+  for (int i = 0; i < levels; ++i) e += pyramid_level_elems(N, H, W, C, i);
+  return e;
+}
+
+size_t t2i_laplacian_pyramid_workspace_bytes(int64_t N, int32_t H, int32_t W, int32_t C, int32_t levels) {
+  return pyramid_shape_ok(N, H, W, C, levels) ? laplacian_pyramid_ws(N, H, W, C, levels) : 0;
+}
+
+int t2i_laplacian_pyramid(const float* x, int64_t N, int32_t H, int32_t W, int32_t C, int32_t levels, float* out, void* ws,
+                          size_t ws_bytes, t2i_stream_t stream) {
+  if (!x || !out || !aligned4(x) || !aligned4(out) || !pyramid_shape_ok(N, H, W, C, levels)) {
+    set_error("t2i_laplacian_pyramid: bad argument (N=%lld H=%d W=%d C=%d levels=%d, x %s, out %s; N in 1..65535, C in 1..4, H and W "
+              "multiples of 2^(levels-1) with a coarsest side of at least 7, at most 2^31-1 elements, 4-byte aligned tensors)",
+              (long long)N, H, W, C, levels, x ? "given" : "NULL", out ? "given" : "NULL");
+    return T2I_ERR_INVALID;
+  }
+  const uint64_t in_bytes = (uint64_t)pyramid_level_elems(N, H, W, C, 0) * 4, out_bytes = (uint64_t)pyramid_out_elems(N, H, W, C, levels) * 4;
+  const size_t need = laplacian_pyramid_ws(N, H, W, C, levels);
+  if (swd_overlap(x, in_bytes, out, out_bytes) || (need && (swd_overlap(ws, need, x, in_bytes) || swd_overlap(ws, need, out, out_bytes)))) {
+    set_error("t2i_laplacian_pyramid: bad argument (x, out and the workspace must not overlap)");
+    return T2I_ERR_INVALID;
+  }
+  if (need && (!ws || ws_bytes < need || !aligned16(ws))) {
+    set_error("t2i_laplacian_pyramid: workspace too small or misaligned (%zu bytes, need %zu)", ws_bytes, need);
+    return T2I_ERR_WORKSPACE;
+  }
+  return check(laplacian_pyramid_launch(x, N, H, W, C, levels, out, ws, (hipStream_t)stream), "t2i_laplacian_pyramid");
+}
+
+int t2i_swd_descriptors(const float* level, int64_t N, int32_t h, int32_t w, int32_t C, const int32_t* pos, int32_t P, float* out,
+                        int64_t row0, int64_t rows_total, t2i_stream_t stream) {
+  bool ok = level && pos && out && aligned4(level) && aligned4(pos) && aligned4(out) && N > 0 && h >= 7 && w >= 7 && C >= 1 && C <= 4 &&
+            P > 0 && row0 >= 0 && rows_total > 0 && rows_total <= kSwdLim / (49 * 4) && N <= kSwdLim / P && row0 <= rows_total &&
+            N * P <= rows_total - row0 && (int64_t)h * w <= kSwdLim / C && N <= kSwdLim / ((int64_t)h * w * C);
+  if (ok) {
+    const uint64_t D4 = (uint64_t)49 * C * 4;
+    ok = !swd_overlap(level, (uint64_t)N * h * w * C * 4, out + (size_t)row0 * 49 * C, (uint64_t)N * P * D4) &&
+         !swd_overlap(pos, (uint64_t)N * P * 8, out + (size_t)row0 * 49 * C, (uint64_t)N * P * D4);
+  }
+  if (!ok) {
+    set_error("t2i_swd_descriptors: bad argument (N=%lld h=%d w=%d C=%d P=%d row0=%lld rows_total=%lld, level %s, pos %s, out %s; "
+              "sides of at least 7, C in 1..4, row0 + N * P <= rows_total, rows_total * 49 * C < 2^31, no overlap of the written rows "
+              "with level or pos, 4-byte aligned tensors)", (long long)N, h, w, C, P, (long long)row0, (long long)rows_total,
+              level ? "given" : "NULL", pos ? "given" : "NULL", out ? "given" : "NULL");
+    return T2I_ERR_INVALID;
+  }
+  return check(swd_descriptors_launch(level, N, h, w, C, pos, P, out, row0, (hipStream_t)stream), "t2i_swd_descriptors");
+}
+
+static bool swd_rows_ok(int64_t rows, int32_t C) { return rows > 0 && C >= 1 && C <= 4 && rows <= kSwdLim / (49 * C); }
+
+size_t t2i_swd_channel_stats_workspace_bytes(int64_t rows, int32_t C) { return swd_rows_ok(rows, C) ? swd_channel_stats_ws(rows, C) : 0; }
+
+int t2i_swd_channel_stats(const float* A, int64_t rows, int32_t C, double* mean64, double* std64, void* ws, size_t ws_bytes,
+                          t2i_stream_t stream) {
+  bool ok = A && mean64 && std64 && aligned4(A) && aligned8(mean64) && aligned8(std64) && swd_rows_ok(rows, C);
+  if (ok) {
+    const uint64_t a_bytes = (uint64_t)rows * 49 * C * 4;
+    ok = !swd_overlap(A, a_bytes, mean64, 8 * C) && !swd_overlap(A, a_bytes, std64, 8 * C) && !swd_overlap(mean64, 8 * C, std64, 8 * C) &&
+         !swd_overlap(ws, swd_channel_stats_ws(rows, C), A, a_bytes) && !swd_overlap(ws, swd_channel_stats_ws(rows, C), mean64, 8 * C) &&
+         !swd_overlap(ws, swd_channel_stats_ws(rows, C), std64, 8 * C);
+  }
+  if (!ok) {
+    set_error("t2i_swd_channel_stats: bad argument (rows=%lld C=%d, A %s, mean64 %s, std64 %s; C in 1..4, rows * 49 * C < 2^31, no "
+              "overlap, A 4-byte and the fp64 outputs 8-byte aligned)", (long long)rows, C, A ? "given" : "NULL",
+              mean64 ? "given" : "NULL", std64 ? "given" : "NULL");
+    return T2I_ERR_INVALID;
+  }
+  const size_t need = swd_channel_stats_ws(rows, C);
+  if (!ws || ws_bytes < need || !aligned16(ws)) {
+    set_error("t2i_swd_channel_stats: workspace too small or misaligned (%zu bytes, need %zu)", ws_bytes, need);
+    return T2I_ERR_WORKSPACE;
+  }
+  return check(swd_channel_stats_launch(A, rows, C, mean64, std64, ws, (hipStream_t)stream), "t2i_swd_channel_stats");
+}
+
+int t2i_swd_project(const float* A, int64_t rows, int32_t C, const double* mean64, const double* std64, const float* dirs, int32_t S,
+                    float* out, int64_t rows_pad, t2i_stream_t stream) {
+  bool ok = A && mean64 && std64 && dirs && out && aligned4(A) && aligned8(mean64) && aligned8(std64) && aligned4(dirs) && aligned4(out) &&
+            swd_rows_ok(rows, C) && S > 0 && S <= 65535 * 128 && rows_pad >= rows && (rows_pad & (rows_pad - 1)) == 0 &&
+            rows_pad <= kSwdLim / S;
+  if (ok) {
+    const uint64_t a_bytes = (uint64_t)rows * 49 * C * 4, o_bytes = (uint64_t)rows_pad * S * 4;
+    ok = !swd_overlap(out, o_bytes, A, a_bytes) && !swd_overlap(out, o_bytes, dirs, (uint64_t)49 * C * S * 4) &&
+         !swd_overlap(out, o_bytes, mean64, 8 * C) && !swd_overlap(out, o_bytes, std64, 8 * C);
+  }
+  if (!ok) {
+    set_error("t2i_swd_project: bad argument (rows=%lld C=%d S=%d rows_pad=%lld, A %s, mean64 %s, std64 %s, dirs %s, out %s; C in 1..4, "
+              "rows_pad a power of two >= rows, S * rows_pad < 2^31, out apart from every input, aligned tensors)", (long long)rows, C, S,
+              (long long)rows_pad, A ? "given" : "NULL", mean64 ? "given" : "NULL", std64 ? "given" : "NULL", dirs ? "given" : "NULL",
+              out ? "given" : "NULL");
+    return T2I_ERR_INVALID;
+  }
+  return check(swd_project_launch(A, rows, C, mean64, std64, dirs, S, out, rows_pad, (hipStream_t)stream), "t2i_swd_project");
+}
+
+int32_t t2i_segmented_sort_chunk(void) { return segmented_sort_chunk(); }
+
+int t2i_segmented_sort_f32(float* data, int32_t segments, int64_t len, t2i_stream_t stream) {
+  if (!data || !aligned16(data) || segments <= 0 || segments > 65535 || len <= 0 || (len & (len - 1)) != 0 || len > kSwdLim / segments) {
+    set_error("t2i_segmented_sort_f32: bad argument (segments=%d len=%lld, data %s; segments in 1..65535, len a power of two, "
+              "segments * len < 2^31, data 16-byte aligned)", segments, (long long)len, data ? "given" : "NULL");
+    return T2I_ERR_INVALID;
+  }
+  return check(segmented_sort_launch(data, segments, len, (hipStream_t)stream), "t2i_segmented_sort_f32");
+}
+
+static bool l1_shape_ok(int32_t segments, int64_t len, int64_t rows) {
+  return segments > 0 && segments <= 65535 && len > 0 && rows > 0 && rows <= len && len <= kSwdLim / segments;
+}
+
+size_t t2i_sorted_l1_mean_workspace_bytes(int32_t segments, int64_t rows) {
+  return l1_shape_ok(segments, rows, rows) ? sorted_l1_mean_ws(segments, rows) : 0;
+}
+
+int t2i_sorted_l1_mean(const float* a, const float* b, int32_t segments, int64_t len, int64_t rows, double* out64, void* ws,
+                       size_t ws_bytes, t2i_stream_t stream) {
+  bool ok = a && b && out64 && aligned4(a) && aligned4(b) && aligned8(out64) && l1_shape_ok(segments, len, rows);
+  if (ok) {
+    const uint64_t bytes = (uint64_t)segments * len * 4;
+    ok = !swd_overlap(out64, 8, a, bytes) && !swd_overlap(out64, 8, b, bytes) && !swd_overlap(ws, sorted_l1_mean_ws(segments, rows), a, bytes) &&
+         !swd_overlap(ws, sorted_l1_mean_ws(segments, rows), b, bytes) && !swd_overlap(ws, sorted_l1_mean_ws(segments, rows), out64, 8);
+  }
+  if (!ok) {
+    set_error("t2i_sorted_l1_mean: bad argument (segments=%d len=%lld rows=%lld, a %s, b %s, out64 %s; segments in 1..65535, "
+              "1 <= rows <= len, segments * len < 2^31, out64 and the workspace apart from a and b, aligned tensors)", segments,
+              (long long)len, (long long)rows, a ? "given" : "NULL", b ? "given" : "NULL", out64 ? "given" : "NULL");
+    return T2I_ERR_INVALID;
+  }
+  const size_t need = sorted_l1_mean_ws(segments, rows);
+  if (!ws || ws_bytes < need || !aligned16(ws)) {
+    set_error("t2i_sorted_l1_mean: workspace too small or misaligned (%zu bytes, need %zu)", ws_bytes, need);
+    return T2I_ERR_WORKSPACE;
+  }
+  return check(sorted_l1_mean_launch(a, b, segments, len, rows, out64, ws, (hipStream_t)stream), "t2i_sorted_l1_mean");
 }
 
 }  // extern "C"

@@ -13,6 +13,8 @@ either
 The real images' statistics are read from EVAL.ACT_STAT_PATH, or computed from the images under EVAL.R_IMG_PATH and saved there
 first; on a failure of the distance the reference prints the error and reports 500, which is kept.  evaluate_imd is an addition the
 reference does not have (evaluation/imd.py): each real test image of the batch against the image generated from its embedding.
+evaluate_swd is another (evaluation/swd.py): the sliced Wasserstein distance of the same pairs' Laplacian-pyramid patches, per
+resolution level; it needs no Inception net and no EVAL.ACT_STAT_PATH.
 
 A model's evaluator states what differs (DESIGN.md has the table): restore(), dims(), generate_batch(), and the attributes below."""
 import os
@@ -23,7 +25,7 @@ import torch
 from .. import kernels as K
 from ..models.inception.model import IMAGE_SIZE, load_inception_inference
 from ..utils.saver import restore_g_net
-from . import fid, imd, inception_score
+from . import fid, imd, inception_score, swd
 
 
 class GeneratorEval(object):
@@ -200,6 +202,24 @@ class GeneratorEval(object):
         mean, std = float(np.mean(d)), float(np.std(d))
         print('IMD | mean: %.4f std: %.4f' % (mean, std))
         out = dict(mean=mean, std=std, distances=d)
+        if keep_samples:
+            out.update(real=np.concatenate([r for r, _ in self._kept]), gen=np.concatenate([g for _, g in self._kept]))
+        return out
+
+    def evaluate_swd(self, keep_samples=False):
+        """-> dict(levels: SWD x 10^3 per pyramid level, finest first; mean; sides) of the real test images against the images
+        generated from their embeddings, and, with keep_samples, the host pairs (real, gen).  One SlicedWasserstein.add per batch;
+        its draws come from its own generator, so the batches are those of evaluate_imd."""
+        self.restore()
+        sw = None
+        for real, gen in self._batches(False, keep_samples, with_real=True):
+            if sw is None:
+                sw = swd.SlicedWasserstein(tuple(gen.shape[1:]), self._n_batches() * self.bs, self.model.device)
+            sw.add(real.reshape(gen.shape), gen)
+        out = sw.finalize()
+        for side, v in zip(out['sides'], out['levels']):
+            print('SWD x 1e3 | %4d x %-4d: %.4f' % (side, side, v))
+        print('SWD x 1e3 | mean: %.4f' % out['mean'])
         if keep_samples:
             out.update(real=np.concatenate([r for r, _ in self._kept]), gen=np.concatenate([g for _, g in self._kept]))
         return out

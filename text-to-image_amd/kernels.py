@@ -1942,3 +1942,128 @@ def mul(a, b):
     if _live(a) and a.numel() > 0:
         check(lib.t2i_mul(_ptr(a), _ptr(b), a.numel(), _ptr(y), _stream()), 't2i_mul')
     return y
+
+
+# ---- sliced Wasserstein distance (csrc/t2i_swd.hip; evaluation/swd.py is the caller) -----------------------------------------
+def _f32_nd(t, name, dim):
+    if t.dtype != torch.float32 or t.dim() != dim or not t.is_contiguous():
+        raise ValueError('%s must be a contiguous float32 tensor of %d dimensions, got %s %s' % (name, dim, t.dtype, tuple(t.shape)))
+    return t
+
+
+def pyramid_offsets(N, H, W, C, levels):
+    """Element offsets of the levels in laplacian_pyramid's packed output, and its total element count."""
+    offs, total = [], 0
+    for i in range(levels):
+        offs.append(total)
+        total += N * (H >> i) * (W >> i) * C
+    return offs, total
+
+
+def laplacian_pyramid(x, levels):
+    """x float32 [N,H,W,C] -> the list of `levels` Laplacian levels [N, H >> i, W >> i, C] (views of one packed buffer):
+    t2i_laplacian_pyramid, the 5 x 5 binomial with scipy.ndimage's 'mirror' edges."""
+    _f32_nd(x, 'laplacian_pyramid: x', 4)
+    N, H, W, C = (int(s) for s in x.shape)
+    levels = int(levels)
+    if levels < 1 or min(N, H, W) <= 0 or not 1 <= C <= 4 or H % (1 << (levels - 1)) or W % (1 << (levels - 1)) or \
+            min(H, W) >> (levels - 1) < 7:
+        raise ValueError('laplacian_pyramid: %d levels of %s need C in 1..4 and sides that are multiples of 2^(levels-1) with a '
+                         'coarsest side of at least 7' % (levels, tuple(x.shape)))
+    offs, total = pyramid_offsets(N, H, W, C, levels)
+    out = torch.empty(total, dtype=torch.float32, device=x.device)
+    if _live(x):
+        wsp, wsn = _ws_args(x, int(lib.t2i_laplacian_pyramid_workspace_bytes(N, H, W, C, levels)))
+        check(lib.t2i_laplacian_pyramid(_ptr(x), N, H, W, C, levels, _ptr(out), wsp, wsn, _stream()), 't2i_laplacian_pyramid')
+    return [out[o:o + N * (H >> i) * (W >> i) * C].view(N, H >> i, W >> i, C) for i, o in enumerate(offs)]
+
+
+def swd_descriptors(level, pos, out, row0):
+    """Rows row0 + n P + p of out [rows_total, 49 C] = the 7 x 7 x C neighbourhood of level [N,h,w,C] around (y, x) = pos[n, p],
+    flattened (c, dy, dx).  pos: an integer array or tensor [N,P,2] on the HOST, every centre in [3, side - 3) (checked here; the
+    kernel also clamps)."""
+    _f32_nd(level, 'swd_descriptors: level', 4); _f32_nd(out, 'swd_descriptors: out', 2)
+    N, h, w, C = (int(s) for s in level.shape)
+    pos = torch.as_tensor(pos)
+    if pos.is_cuda or pos.dim() != 3 or pos.shape[0] != N or pos.shape[2] != 2 or pos.shape[1] == 0 or pos.is_floating_point():
+        raise ValueError('swd_descriptors: pos must be a host integer [N=%d, P, 2] table, got %s %s' % (N, pos.dtype, tuple(pos.shape)))
+    P = int(pos.shape[1])
+    if min(h, w) < 7 or int(pos[..., 0].min()) < 3 or int(pos[..., 0].max()) >= h - 3 or int(pos[..., 1].min()) < 3 or \
+            int(pos[..., 1].max()) >= w - 3:
+        raise ValueError('swd_descriptors: a centre lies outside [3, side - 3) of a %d x %d level' % (h, w))
+    row0 = int(row0)
+    if out.shape[1] != 49 * C or row0 < 0 or row0 + N * P > out.shape[0] or out.device != level.device:
+        raise ValueError('swd_descriptors: rows %d..%d of a %s store on %s cannot take %d x %d descriptors of %d floats from %s' % (
+            row0, row0 + N * P, tuple(out.shape), out.device, N, P, 49 * C, level.device))
+    if _live(level):
+        p = pos.to(torch.int32).contiguous().to(level.device)
+        check(lib.t2i_swd_descriptors(_ptr(level), N, h, w, C, _ptr(p), P, _ptr(out), row0, out.shape[0], _stream()), 't2i_swd_descriptors')
+    return out
+
+
+def swd_channel_stats(A, C):
+    """A float32 [rows, 49 C] -> (mean, std): float64 [C] each, per channel over all rows and its 49 columns, std with ddof 0."""
+    _f32_nd(A, 'swd_channel_stats: A', 2)
+    rows, C = int(A.shape[0]), int(C)
+    if rows <= 0 or not 1 <= C <= 4 or A.shape[1] != 49 * C:
+        raise ValueError('swd_channel_stats: A %s is not a non-empty [rows, 49 * %d] store with C in 1..4' % (tuple(A.shape), C))
+    mean = torch.empty(C, dtype=torch.float64, device=A.device)
+    std = torch.empty(C, dtype=torch.float64, device=A.device)
+    if _live(A):
+        wsp, wsn = _ws_args(A, int(lib.t2i_swd_channel_stats_workspace_bytes(rows, C)))
+        check(lib.t2i_swd_channel_stats(_ptr(A), rows, C, _ptr(mean), _ptr(std), wsp, wsn, _stream()), 't2i_swd_channel_stats')
+    return mean, std
+
+
+def next_pow2(n):
+    return 1 << max(int(n) - 1, 0).bit_length()
+
+
+def swd_project(A, mean, std, dirs, out=None):
+    """out [S, rows_pad] (rows_pad = next_pow2(rows), or that of `out`) with out[s][r] = sum_j ((A[r][j] - mean_c) / std_c)
+    dirs[j][s] and +inf for r >= rows.  A float32 [rows, 49 C], mean / std float64 [C], dirs float32 [49 C, S]."""
+    _f32_nd(A, 'swd_project: A', 2); _f32_nd(dirs, 'swd_project: dirs', 2)
+    rows, D = (int(s) for s in A.shape)
+    C, S = D // 49, int(dirs.shape[1])
+    if rows <= 0 or S <= 0 or D != 49 * C or not 1 <= C <= 4 or dirs.shape[0] != D:
+        raise ValueError('swd_project: A %s and dirs %s are not [rows, 49 C] and [49 C, S] with C in 1..4' % (tuple(A.shape), tuple(dirs.shape)))
+    for t, name in ((mean, 'mean'), (std, 'std')):
+        if t.dtype != torch.float64 or tuple(t.shape) != (C,) or not t.is_contiguous() or t.device != A.device:
+            raise ValueError('swd_project: %s must be a contiguous float64 [%d] on %s' % (name, C, A.device))
+    if out is None:
+        out = torch.empty((S, next_pow2(rows)), dtype=torch.float32, device=A.device)
+    _f32_nd(out, 'swd_project: out', 2)
+    rows_pad = int(out.shape[1])
+    if out.shape[0] != S or rows_pad < rows or rows_pad & (rows_pad - 1) or out.device != A.device or dirs.device != A.device:
+        raise ValueError('swd_project: out %s must be [%d, a power of two >= %d] on %s' % (tuple(out.shape), S, rows, A.device))
+    if _live(A):
+        check(lib.t2i_swd_project(_ptr(A), rows, C, _ptr(mean), _ptr(std), _ptr(dirs), S, _ptr(out), rows_pad, _stream()), 't2i_swd_project')
+    return out
+
+
+SORT_CHUNK = int(lib.t2i_segmented_sort_chunk())      # elements one workgroup sorts in LDS (include/t2i_hip.h T2I_SORT_CHUNK)
+
+
+def segmented_sort(data):
+    """Sorts every row of data float32 [segments, len] ascending, in place (len a power of two; no NaN by contract, +inf last)."""
+    _f32_nd(data, 'segmented_sort: data', 2)
+    segments, n = (int(s) for s in data.shape)
+    if segments <= 0 or n <= 0 or n & (n - 1):
+        raise ValueError('segmented_sort: %s is not [segments, a power of two]' % (tuple(data.shape),))
+    if _live(data):
+        check(lib.t2i_segmented_sort_f32(_ptr(data), segments, n, _stream()), 't2i_segmented_sort_f32')
+    return data
+
+
+def sorted_l1_mean(a, b, rows):
+    """mean |a - b| over the first `rows` entries of every row of a, b float32 [segments, len] -> float64 [1] on the device."""
+    _f32_nd(a, 'sorted_l1_mean: a', 2); _f32_nd(b, 'sorted_l1_mean: b', 2)
+    segments, n = (int(s) for s in a.shape)
+    rows = int(rows)
+    if tuple(a.shape) != tuple(b.shape) or segments <= 0 or not 1 <= rows <= n or a.device != b.device:
+        raise ValueError('sorted_l1_mean: a %s, b %s, rows %d' % (tuple(a.shape), tuple(b.shape), rows))
+    out = torch.empty(1, dtype=torch.float64, device=a.device)
+    if _live(a):
+        wsp, wsn = _ws_args(a, int(lib.t2i_sorted_l1_mean_workspace_bytes(segments, rows)))
+        check(lib.t2i_sorted_l1_mean(_ptr(a), _ptr(b), segments, n, rows, _ptr(out), wsp, wsn, _stream()), 't2i_sorted_l1_mean')
+    return out

@@ -3,7 +3,7 @@ raised before a directory is created or anything touches the GPU), the output di
 import argparse
 import os
 
-EVAL_MODES = ('is', 'fid', 'imd')
+EVAL_MODES = ('is', 'fid', 'imd', 'swd')
 
 
 def make_parser(default_cfg):
@@ -11,8 +11,9 @@ def make_parser(default_cfg):
     ap.add_argument('--cfg', default=default_cfg, help='Relative path to the config of the model')
     mode = ap.add_mutually_exclusive_group()
     mode.add_argument('--train', action='store_true', help='train even if the yml says TRAIN.FLAG: False')
-    mode.add_argument('--eval', choices=EVAL_MODES, default=None, help='Inception score, FID or Inception match distance of the '
-                      'latest checkpoint (needs the pickled dataset and an Inception checkpoint in EVAL.INCEP_CHECKPOINT_DIR)')
+    mode.add_argument('--eval', choices=EVAL_MODES, default=None, help='Inception score, FID, Inception match distance or sliced Wasserstein '
+                      'distance of the latest checkpoint (needs the pickled dataset and, except for swd, an Inception checkpoint in '
+                      'EVAL.INCEP_CHECKPOINT_DIR)')
     mode.add_argument('--visualize', action='store_true', help='run the caption visualiser on the latest checkpoint (needs the '
                       'pickled dataset)')
     ap.add_argument('--incep-batch', type=int, default=None, help='--eval: Inception batch size (default EVAL.INCEP_BATCH_SIZE)')
@@ -56,4 +57,4 @@ def make_dirs(cfg):
 
 
 def run_eval(ev, mode):
-    return {'is': ev.evaluate_inception, 'fid': ev.evaluate_fid, 'imd': ev.evaluate_imd}[mode]()
+    return {'is': ev.evaluate_inception, 'fid': ev.evaluate_fid, 'imd': ev.evaluate_imd, 'swd': ev.evaluate_swd}[mode]()
