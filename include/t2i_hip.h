@@ -763,6 +763,29 @@ size_t t2i_sorted_l1_mean_workspace_bytes(int32_t segments, int64_t rows);
 int t2i_sorted_l1_mean(const float* a, const float* b, int32_t segments, int64_t len, int64_t rows, double* out64, void* ws,
                        size_t ws_bytes, t2i_stream_t stream);
 
+/* ---- multi-scale structural similarity (Karras et al., ms_ssim.py = the TensorFlow-compression msssim; the reference has no such
+ * metric).  Added within ABI v13: no existing argument list changed. -------------------------------------------------------------- */
+/* One scale for N pairs a[n], b[n] of fp32 [H, W, C] images (levels 0..255 held as floats, C in 1..4, N H W C < 2^31):
+ * with g = window_host[0..S) (S <= T2I_SSIM_MAX_WINDOW doubles ON THE HOST, copied into the kernel's arguments: the entry only
+ * enqueues work and can be captured), mu1, mu2, E[a^2], E[b^2], E[ab] the VALID correlations with outer(g, g) per channel
+ * ((H - S + 1) x (W - S + 1) x C maps, every moment accumulated in fp64), s11 = E[a^2] - mu1^2, s22 = E[b^2] - mu2^2,
+ * s12 = E[ab] - mu1 mu2, v1 = 2 s12 + c2, v2 = s11 + s22 + c2:
+ *   cs[n] = mean(v1 / v2),   ssim[n] = mean((2 mu1 mu2 + c1) v1 / ((mu1^2 + mu2^2 + c1) v2))      (device fp64 [N] each)
+ * over the whole map, channels included.  Sums run in a fixed order (one fp64 partial pair per workgroup in the workspace, folded
+ * per pair by a second launch; no atomics): results repeat bit for bit.  With a_half and b_half (both or neither) the same launch
+ * writes the next scale [N, ceil(H/2), ceil(W/2), C]: out[i, j] = ((x[2i, 2j] + x[2i, j']) + (x[i', 2j] + x[i', j'])) * 0.25 in
+ * fp32, i' = min(2i + 1, H - 1), j' = min(2j + 1, W - 1) (scipy.ndimage.convolve(x, ones(2, 2) / 4, 'reflect')[::2, ::2]).
+ * Every refusal, a short workspace included, returns T2I_ERR_INVALID before anything is launched: a NULL a, b, ssim, cs,
+ * window_host or workspace; N <= 0, H < 1, W < 1; C outside 1..4; S < 1, S > T2I_SSIM_MAX_WINDOW or S > min(H, W);
+ * N H W C >= 2^31; exactly one of a_half / b_half NULL; an output or the workspace overlapping an input or another output (a and
+ * b may be the same tensor); a workspace smaller than the query; a non-finite window entry, c1 or c2, or c2 <= 0; a misaligned
+ * pointer (4 bytes for fp32, 8 for fp64 and the workspace). */
+#define T2I_SSIM_MAX_WINDOW 11
+size_t t2i_ssim_scale_workspace_bytes(int64_t N, int32_t H, int32_t W, int32_t C);
+int t2i_ssim_scale(const float* a, const float* b, int64_t N, int32_t H, int32_t W, int32_t C, const double* window_host, int32_t S,
+                   double c1, double c2, double* ssim, double* cs, float* a_half, float* b_half, void* workspace,
+                   size_t workspace_bytes, t2i_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -160,6 +160,8 @@ SIGNATURES = {
     't2i_segmented_sort_f32': (ctypes.c_int, [_p, _i32, _i64, _p]),
     't2i_sorted_l1_mean_workspace_bytes': (_sz, [_i32, _i64]),
     't2i_sorted_l1_mean': (ctypes.c_int, [_p, _p, _i32, _i64, _i64, _p, _p, _sz, _p]),
+    't2i_ssim_scale_workspace_bytes': (_sz, [_i64, _i32, _i32, _i32]),
+    't2i_ssim_scale': (ctypes.c_int, [_p, _p, _i64, _i32, _i32, _i32, _p, _i32, ctypes.c_double, ctypes.c_double, _p, _p, _p, _p, _p, _sz, _p]),
 }
 
 if not os.path.exists(LIB_PATH):

@@ -82,6 +82,10 @@ int segmented_sort_chunk();
 hipError_t segmented_sort_launch(float*, int, int64_t, hipStream_t);
 size_t sorted_l1_mean_ws(int segments, int64_t rows);
 hipError_t sorted_l1_mean_launch(const float*, const float*, int, int64_t, int64_t, double*, void*, hipStream_t);
+// implemented in t2i_msssim.hip
+size_t ssim_scale_ws(int64_t N, int H, int W, int C, int S);
+hipError_t ssim_scale_launch(const float*, const float*, int64_t, int, int, int, const double*, int, double, double, double*, double*, float*,
+                             float*, void*, hipStream_t);
 // implemented in t2i_preprocess.hip
 int pillow_table_taps(int filter, int in_size, int out_size);
 hipError_t pillow_tables_launch(int, const int32_t*, int64_t, int, int32_t*, int32_t*, int, hipStream_t);
@@ -2152,6 +2156,51 @@ int t2i_sorted_l1_mean(const float* a, const float* b, int32_t segments, int64_t
     return T2I_ERR_WORKSPACE;
   }
   return check(sorted_l1_mean_launch(a, b, segments, len, rows, out64, ws, (hipStream_t)stream), "t2i_sorted_l1_mean");
+}
+
+
+// ---- multi-scale structural similarity (t2i_msssim.hip) ---------------------------------------------------------------------------
+// N * H * W * C within kSwdLim, formed factor by factor; 1 <= S <= min(T2I_SSIM_MAX_WINDOW, H, W)
+static bool ssim_shape_ok(int64_t N, int32_t H, int32_t W, int32_t C, int32_t S) {
+  if (N <= 0 || H < 1 || W < 1 || C < 1 || C > 4 || S < 1 || S > T2I_SSIM_MAX_WINDOW || S > H || S > W) return false;
+  return (int64_t)H * W <= kSwdLim / C && N <= kSwdLim / ((int64_t)H * W * C);
+}
+
+size_t t2i_ssim_scale_workspace_bytes(int64_t N, int32_t H, int32_t W, int32_t C) {
+  return ssim_shape_ok(N, H, W, C, 1) ? ssim_scale_ws(N, H, W, C, 1) : 0;          // S = 1: the most tiles any window leaves
+}
+
+int t2i_ssim_scale(const float* a, const float* b, int64_t N, int32_t H, int32_t W, int32_t C, const double* window_host, int32_t S,
+                   double c1, double c2, double* ssim, double* cs, float* a_half, float* b_half, void* workspace, size_t workspace_bytes,
+                   t2i_stream_t stream) {
+  bool ok = a && b && ssim && cs && window_host && workspace && aligned4(a) && aligned4(b) && aligned8(ssim) && aligned8(cs) &&
+            aligned8(workspace) && aligned4(a_half) && aligned4(b_half) && !a_half == !b_half && ssim_shape_ok(N, H, W, C, S) &&
+            std::isfinite(c1) && std::isfinite(c2) && c2 > 0.0;
+  for (int k = 0; ok && k < S; ++k) ok = std::isfinite(window_host[k]);
+  size_t need = 0;
+  if (ok) {
+    need = t2i_ssim_scale_workspace_bytes(N, H, W, C);
+    const uint64_t in_bytes = (uint64_t)N * H * W * C * 4, half_bytes = (uint64_t)N * ((H + 1) / 2) * ((W + 1) / 2) * C * 4;
+    const void* in[2] = {a, b};
+    const void* out[5] = {ssim, cs, a_half, b_half, workspace};
+    const uint64_t out_bytes[5] = {(uint64_t)N * 8, (uint64_t)N * 8, half_bytes, half_bytes, need};
+    for (int i = 0; i < 5; ++i) {
+      for (int j = 0; j < 2; ++j) ok = ok && !swd_overlap(out[i], out_bytes[i], in[j], in_bytes);        // (NULL never overlaps)
+      for (int j = 0; j < i; ++j) ok = ok && !swd_overlap(out[i], out_bytes[i], out[j], out_bytes[j]);
+    }
+    ok = ok && workspace_bytes >= need;
+  }
+  if (!ok) {
+    set_error("t2i_ssim_scale: bad argument (N=%lld H=%d W=%d C=%d S=%d c1=%g c2=%g, a %s, b %s, ssim %s, cs %s, window %s, a_half %s, "
+              "b_half %s, workspace %s of %zu bytes, need %zu; C in 1..4, 1 <= S <= min(%d, H, W), N H W C < 2^31, a finite window, c1 and "
+              "c2 > 0, a_half and b_half both or neither, aligned tensors, the outputs and the workspace apart from the inputs and "
+              "from each other)", (long long)N, H, W, C, S, c1, c2, a ? "given" : "NULL", b ? "given" : "NULL", ssim ? "given" : "NULL",
+              cs ? "given" : "NULL", window_host ? "given" : "NULL", a_half ? "given" : "NULL", b_half ? "given" : "NULL",
+              workspace ? "given" : "NULL", workspace_bytes, need, T2I_SSIM_MAX_WINDOW);
+    return T2I_ERR_INVALID;
+  }
+  return check(ssim_scale_launch(a, b, N, H, W, C, window_host, S, c1, c2, ssim, cs, a_half, b_half, workspace, (hipStream_t)stream),
+               "t2i_ssim_scale");
 }
 
 }  // extern "C"

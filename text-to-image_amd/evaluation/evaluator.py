@@ -14,7 +14,9 @@ The real images' statistics are read from EVAL.ACT_STAT_PATH, or computed from t
 first; on a failure of the distance the reference prints the error and reports 500, which is kept.  evaluate_imd is an addition the
 reference does not have (evaluation/imd.py): each real test image of the batch against the image generated from its embedding.
 evaluate_swd is another (evaluation/swd.py): the sliced Wasserstein distance of the same pairs' Laplacian-pyramid patches, per
-resolution level; it needs no Inception net and no EVAL.ACT_STAT_PATH.
+resolution level; it needs no Inception net and no EVAL.ACT_STAT_PATH.  evaluate_msssim (evaluation/msssim.py) is the one
+evaluation that compares generated images with each other: the multi-scale structural similarity of pairs of them, which is 1 for a
+generator that ignores z; it needs no Inception net either.
 
 A model's evaluator states what differs (DESIGN.md has the table): restore(), dims(), generate_batch(), and the attributes below."""
 import os
@@ -25,7 +27,7 @@ import torch
 from .. import kernels as K
 from ..models.inception.model import IMAGE_SIZE, load_inception_inference
 from ..utils.saver import restore_g_net
-from . import fid, imd, inception_score, swd
+from . import fid, imd, inception_score, msssim, swd
 
 
 class GeneratorEval(object):
@@ -97,6 +99,7 @@ class GeneratorEval(object):
         for i in range(n_batches):
             print('\rGenerating batch %d/%d' % (i + 1, n_batches), end='', flush=True)
             real, z, cond = self._draw_batch(with_real)
+            self._cond = cond                             # evaluate_msssim('caption') generates from it a second time
             with torch.no_grad():
                 img = self.generate_batch(z, cond, is_training).float().contiguous()
             if keep_samples:
@@ -222,4 +225,34 @@ class GeneratorEval(object):
         print('SWD x 1e3 | mean: %.4f' % out['mean'])
         if keep_samples:
             out.update(real=np.concatenate([r for r, _ in self._kept]), gen=np.concatenate([g for _, g in self._kept]))
+        return out
+
+    def evaluate_msssim(self, pairs='random', keep_samples=False):
+        """-> MultiScaleSSIM.finalize()'s dict (values, mean, std, cs_levels, clamped, sides) of pairs of GENERATED images (+ samples,
+        host, with keep_samples); the batches and their draws from np.random are those of the streamed evaluate_inception.
+        pairs='random' (the paper's protocol): image i of a batch against image i + bs // 2, different z and different captions,
+        bs // 2 pairs per batch.  pairs='caption': the batch is generated a second time from the SAME embeddings and a fresh z, image i
+        against its regeneration, bs pairs per batch: 1 means the generator ignores z.  The fresh z is normal(0, 1, (bs, z_dim)) cast
+        to float32 from the evaluation's own np.random.RandomState(0); the global stream is left alone."""
+        if pairs not in ('random', 'caption'):
+            raise ValueError("evaluate_msssim: pairs must be 'random' or 'caption', got %r" % (pairs,))
+        if pairs == 'random' and self.bs < 2:
+            raise ValueError('evaluate_msssim: random pairs need a batch of at least 2 images, got %d' % self.bs)
+        self.restore()
+        rs = np.random.RandomState(0)
+        ms, half = None, self.bs // 2
+        for _, img in self._batches(False, keep_samples):
+            if ms is None:
+                ms = msssim.MultiScaleSSIM(tuple(img.shape[1:]), self.model.device)
+            if pairs == 'random':
+                ms.add(img[:half], img[half:2 * half])
+            else:
+                z = torch.as_tensor(rs.normal(0, 1, size=(self.bs, self.dims()[0])).astype(np.float32)).to(self.model.device)
+                with torch.no_grad():
+                    again = self.generate_batch(z, self._cond, False).float().contiguous()
+                ms.add(img, again.reshape(img.shape))
+        out = ms.finalize()
+        print('MS-SSIM (%s) | mean: %.4f std: %.4f clamped: %d' % (pairs, out['mean'], out['std'], out['clamped']))
+        print('MS-SSIM (%s) | cs per scale: %s' % (pairs, ' '.join('%dx%d: %.4f' % (h, w, v) for (h, w), v in zip(out['sides'], out['cs_levels']))))
+        out.update(self._kept_samples(keep_samples))
         return out

@@ -10,6 +10,7 @@ import contextlib
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from ._lib import DT_BF16, DT_F32, XFORM_HAVE, XFORM_KEEP, ConvDesc, ConvOpts, ImageDesc, check, lib
@@ -2067,3 +2068,50 @@ def sorted_l1_mean(a, b, rows):
         wsp, wsn = _ws_args(a, int(lib.t2i_sorted_l1_mean_workspace_bytes(segments, rows)))
         check(lib.t2i_sorted_l1_mean(_ptr(a), _ptr(b), segments, n, rows, _ptr(out), wsp, wsn, _stream()), 't2i_sorted_l1_mean')
     return out
+
+
+# ---- multi-scale structural similarity (csrc/t2i_msssim.hip; evaluation/msssim.py is the caller) ------------------------------
+SSIM_MAX_WINDOW = 11                                    # include/t2i_hip.h T2I_SSIM_MAX_WINDOW
+
+
+def msssim_window(h, w, filter_size=11, sigma=1.5):
+    """The 1-D Gaussian window of a scale of size h x w: float64 [S], S = min(filter_size, h, w), sigma scaled by S / filter_size,
+    g[i] = exp(-x_i^2 / 2 sigma^2) normalised to sum 1 with x_i = i - S // 2 (+ 0.5 for even S).  outer(g, g) is the 2-D normalised
+    Gaussian of ms_ssim.py's _FSpecialGauss."""
+    h, w, filter_size = int(h), int(w), int(filter_size)
+    if min(h, w, filter_size) < 1 or not float(sigma) > 0:
+        raise ValueError('msssim_window: a %d x %d scale, filter_size %d and sigma %r' % (h, w, filter_size, sigma))
+    S = min(filter_size, h, w)
+    sig = S * float(sigma) / filter_size
+    x = np.arange(S, dtype=np.float64) - S // 2 + (0.5 if S % 2 == 0 else 0.0)
+    g = np.exp(-(x * x) / (2.0 * sig * sig))
+    return g / g.sum()
+
+
+def ssim_scale(a, b, window, c1, c2, downsample=True):
+    """One MS-SSIM scale of the pairs a[n], b[n] (device float32 [N,H,W,C], C in 1..4): -> (ssim, cs, a_half, b_half), ssim and cs
+    float64 [N] on the device, a_half / b_half the next scale [N, ceil(H/2), ceil(W/2), C] (None, None without downsample).
+    window: float64 [S] on the host (msssim_window), S <= min(11, H, W).  t2i_ssim_scale: every moment in fp64, fixed-order sums."""
+    _f32_nd(a, 'ssim_scale: a', 4); _f32_nd(b, 'ssim_scale: b', 4)
+    if tuple(a.shape) != tuple(b.shape) or a.device != b.device:
+        raise ValueError('ssim_scale: a %s on %s and b %s on %s must match' % (tuple(a.shape), a.device, tuple(b.shape), b.device))
+    N, H, W, C = (int(s) for s in a.shape)
+    win = np.ascontiguousarray(np.asarray(window, dtype=np.float64))
+    S = int(win.size)
+    if win.ndim != 1 or min(N, H, W) < 1 or not 1 <= C <= 4 or not 1 <= S <= min(SSIM_MAX_WINDOW, H, W) or N * H * W * C >= 1 << 31:
+        raise ValueError('ssim_scale: %s pairs with a window of %s: C in 1..4, 1 <= S <= min(%d, H, W), fewer than 2^31 elements' % (
+            tuple(a.shape), tuple(win.shape), SSIM_MAX_WINDOW))
+    c1, c2 = float(c1), float(c2)
+    if not (np.all(np.isfinite(win)) and np.isfinite(c1) and np.isfinite(c2) and c2 > 0):
+        raise ValueError('ssim_scale: the window, c1 = %r and c2 = %r must be finite and c2 positive' % (c1, c2))
+    ssim = torch.empty(N, dtype=torch.float64, device=a.device)
+    cs = torch.empty(N, dtype=torch.float64, device=a.device)
+    ah = bh = None
+    if downsample:
+        ah = torch.empty((N, (H + 1) // 2, (W + 1) // 2, C), dtype=torch.float32, device=a.device)
+        bh = torch.empty_like(ah)
+    if _live(a):
+        wsp, wsn = _ws_args(a, int(lib.t2i_ssim_scale_workspace_bytes(N, H, W, C)))
+        check(lib.t2i_ssim_scale(_ptr(a), _ptr(b), N, H, W, C, win.ctypes.data_as(ctypes.c_void_p), S, c1, c2, _ptr(ssim), _ptr(cs),
+                                 _ptr(ah), _ptr(bh), wsp, wsn, _stream()), 't2i_ssim_scale')
+    return ssim, cs, ah, bh

@@ -4,25 +4,49 @@ import argparse
 import os
 
 EVAL_MODES = ('is', 'fid', 'imd', 'swd')
+PAIR_MODES = ('msssim',)            # evaluations of pairs of generated images: evaluate_<mode>(pairs=...)
+PAIRINGS = ('random', 'caption')
+
+
+class Parser(argparse.ArgumentParser):
+    """parse_args also runs the checks that span two arguments, so that they end as argument errors (exit status 2)."""
+
+    def parse_args(self, *args, **kwargs):
+        parsed = super(Parser, self).parse_args(*args, **kwargs)
+        check_pairs(self, parsed)
+        return parsed
 
 
 def make_parser(default_cfg):
-    ap = argparse.ArgumentParser()
+    ap = Parser()
     ap.add_argument('--cfg', default=default_cfg, help='Relative path to the config of the model')
     mode = ap.add_mutually_exclusive_group()
     mode.add_argument('--train', action='store_true', help='train even if the yml says TRAIN.FLAG: False')
-    mode.add_argument('--eval', choices=EVAL_MODES, default=None, help='Inception score, FID, Inception match distance or sliced Wasserstein '
-                      'distance of the latest checkpoint (needs the pickled dataset and, except for swd, an Inception checkpoint in '
-                      'EVAL.INCEP_CHECKPOINT_DIR)')
+    mode.add_argument('--eval', choices=EVAL_MODES + PAIR_MODES, default=None, help='Inception score, FID, Inception match distance, '
+                      'sliced Wasserstein distance or multi-scale SSIM between generated pairs of the latest checkpoint (needs the pickled '
+                      'dataset and, except for swd and msssim, an Inception checkpoint in EVAL.INCEP_CHECKPOINT_DIR)')
     mode.add_argument('--visualize', action='store_true', help='run the caption visualiser on the latest checkpoint (needs the '
                       'pickled dataset)')
     ap.add_argument('--incep-batch', type=int, default=None, help='--eval: Inception batch size (default EVAL.INCEP_BATCH_SIZE)')
+    add_pairs_argument(ap)
     ap.add_argument('--interp', type=int, default=0, help='--visualize: rounds of interpolation / captioned sheets (default 0)')
     ap.add_argument('--synthetic', action='store_true', help='--train: synthetic on-device dataset instead of cfg.DATASET_DIR')
     ap.add_argument('--steps', type=int, default=None, help='--train: stop after this many updates')
     ap.add_argument('--batch', type=int, default=None, help='override TRAIN.BATCH_SIZE')
     ap.add_argument('--graphs', type=int, default=1, help='1: replay the iteration from hipGraphs once it has run eagerly (default)')
     return ap
+
+
+def add_pairs_argument(ap):
+    ap.add_argument('--msssim-pairs', choices=PAIRINGS, default=None, help='--eval msssim: random: image i of a batch against image '
+                    'i + batch // 2 (the paper\'s protocol); caption: every image against a second image of the same caption and a '
+                    'fresh z (default random)')
+
+
+def check_pairs(ap, args):
+    """--msssim-pairs without --eval msssim is an argument error."""
+    if args.msssim_pairs is not None and args.eval not in PAIR_MODES:
+        ap.error('--msssim-pairs needs --eval msssim')
 
 
 def check_mode(args, cfg, visualiser):
@@ -56,5 +80,10 @@ def make_dirs(cfg):
             os.makedirs(d)
 
 
-def run_eval(ev, mode):
-    return {'is': ev.evaluate_inception, 'fid': ev.evaluate_fid, 'imd': ev.evaluate_imd, 'swd': ev.evaluate_swd}[mode]()
+EVAL_METHODS = dict(zip(EVAL_MODES + PAIR_MODES, ('evaluate_inception', 'evaluate_fid', 'evaluate_imd', 'evaluate_swd', 'evaluate_msssim')))
+
+
+def run_eval(ev, mode, pairs=None):
+    """The requested mode's method only, looked up by name; a pair mode takes the pairing (default random)."""
+    fn = getattr(ev, EVAL_METHODS[mode])
+    return fn(pairs=pairs or PAIRINGS[0]) if mode in PAIR_MODES else fn()

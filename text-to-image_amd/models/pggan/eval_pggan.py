@@ -1,6 +1,7 @@
 """PGGANEval — reference models/pggan/eval_pggan.py: the Inception score of a stage's generator (stage 7, 256 x 256, by default).
 
-    python text-to-image_amd/models/pggan/eval_pggan.py --cfg models/pggan/cfg/flowers.yml --eval is|fid|swd [--stage 7] [--batch 64]
+    python text-to-image_amd/models/pggan/eval_pggan.py --cfg models/pggan/cfg/flowers.yml --eval is|fid|swd|msssim [--stage 7] [--batch 64]
+                                                        [--msssim-pairs random|caption]
 
 The generator's variables (`g_net`) are restored from CHECKPOINT_DIR/stage%d/; a failed load raises with the reference's
 message.  The dataset is `TextDataset(DATASET_DIR, MODEL.SIZES[stage - 1])` (256 at stage 7, as the reference reads).  Per batch
@@ -21,6 +22,10 @@ batch (default: `--batch`).
   test images and of the images generated from their embeddings, one value per level from the stage's resolution down to
   16 x 16 — the paper's own metric.  It needs no Inception net; stages 1 and 2 (4 x 4, 8 x 8) are too small for it.
 
+- evaluate_msssim: an addition (evaluation/msssim.py): the multi-scale SSIM between pairs of generated images, the paper's
+  diversity metric — `--msssim-pairs random` pairs image i of a batch with image i + batch // 2, `caption` pairs two images of one
+  caption and different z.  It needs no Inception net; its five scales need images of at least 16 x 16, so stage 3 or later.
+
 The PGGAN generator has no batch norm, so there is no training / inference mode to choose between the two."""
 import argparse
 import os
@@ -33,6 +38,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirna
 import t2i_amd  # noqa: E402,F401
 from t2i_amd import kernels as K  # noqa: E402
 from t2i_amd.evaluation.evaluator import GeneratorEval  # noqa: E402
+from t2i_amd.models import cli  # noqa: E402
 from t2i_amd.utils.saver import restore_scopes  # noqa: E402
 
 
@@ -97,7 +103,8 @@ def main(argv=None, **widths):
     from t2i_amd.utils.config import config_from_yaml
     ap = argparse.ArgumentParser()
     ap.add_argument('--cfg', required=True, help='models/pggan/cfg/flowers.yml or birds.yml')
-    ap.add_argument('--eval', choices=['is', 'fid', 'swd'], default='is')
+    ap.add_argument('--eval', choices=['is', 'fid', 'swd', 'msssim'], default='is')
+    cli.add_pairs_argument(ap)
     ap.add_argument('--stage', type=int, default=7, help='the stage whose generator is scored [7]')
     ap.add_argument('--batch', type=int, default=64, help='images generated (and scored) per batch [64]')
     ap.add_argument('--incep-batch', type=int, default=None, help='Inception batch (default: --batch)')
@@ -107,8 +114,11 @@ def main(argv=None, **widths):
         ap.error('--stage must be in 1..8')
     if args.batch < 1 or (args.incep_batch is not None and args.incep_batch < 1):
         ap.error('--batch and --incep-batch must be positive')
-    if args.eval == 'swd' and args.stage < 3:
-        ap.error('--eval swd needs images of at least 16 x 16: --stage 3 or later')
+    if args.eval in ('swd', 'msssim') and args.stage < 3:
+        ap.error('--eval %s needs images of at least 16 x 16: --stage 3 or later' % args.eval)
+    cli.check_pairs(ap, args)
+    if args.eval == 'msssim' and args.msssim_pairs != 'caption' and args.batch < 2:
+        ap.error('--eval msssim pairs image i of a batch with image i + batch // 2: --batch 2 or more (or --msssim-pairs caption)')
     cfg = config_from_yaml(args.cfg)
     if not os.path.isfile(os.path.join(cfg.CHECKPOINT_DIR, 'stage%d' % args.stage, 'checkpoint')):
         raise RuntimeError('Could not load stage %d (no checkpoint in %s)' % (args.stage, os.path.join(cfg.CHECKPOINT_DIR, 'stage%d' % args.stage)))
@@ -119,7 +129,7 @@ def main(argv=None, **widths):
     m = stage_model(cfg, args.stage, args.batch, dataset, dev, **widths)
     ev = PGGANEval(None, m, dataset, cfg, incep_batch_size=args.incep_batch)
     ev.ema = args.ema
-    out = {'is': ev.evaluate_inception, 'fid': ev.evaluate_fid, 'swd': ev.evaluate_swd}[args.eval]()
+    out = cli.run_eval(ev, args.eval, args.msssim_pairs)
     out.pop('preds', None)
     return out
 

@@ -1,6 +1,7 @@
 """Entry point of the wgancls model — reference models/wgancls/run.py:13-74.
 
-    python -m t2i_amd.models.wgancls.run --cfg <yaml> [--train | --visualize [--interp N] | --eval is|fid|swd [--incep-batch N]]
+    python -m t2i_amd.models.wgancls.run --cfg <yaml> [--train | --visualize [--interp N] | --eval is|fid|swd|msssim [--incep-batch N]
+                                         [--msssim-pairs random|caption]]
                                          [--synthetic] [--steps N] [--batch B] [--graphs 0|1]
 
 Behaviour of the reference's main(): read the config, create CHECKPOINT_DIR / SAMPLE_DIR / LOGS_DIR, load the pickled
@@ -12,7 +13,9 @@ shipped yml has TRAIN.FLAG: False); `--visualize` selects the caption visualiser
 says, with `--interp N` rounds of interpolation sheets (the reference runs none) — without it TRAIN.FLAG: False still
 raises, so that no run of the shipped yml starts something the caller did not ask for; `--eval is|fid` runs the
 Inception-score or FID evaluator (eval_wgan.py) whatever EVAL.FLAG says, with `--incep-batch N` overriding
-EVAL.INCEP_BATCH_SIZE, and `--eval swd` the sliced Wasserstein distance per pyramid level (evaluation/swd.py; no Inception net) —
+EVAL.INCEP_BATCH_SIZE, `--eval swd` the sliced Wasserstein distance per pyramid level (evaluation/swd.py; no Inception net) and
+`--eval msssim` the multi-scale SSIM between pairs of generated images (evaluation/msssim.py; `--msssim-pairs caption` pairs two
+images of one caption) —
 EVAL.FLAG: True without it still raises, for the same reason; `--synthetic` replaces the pickled dataset by the on-device synthetic one
 (t2i_amd.data) for machines without the data; `--steps` / `--batch` override TRAIN.MAX_STEPS / TRAIN.BATCH_SIZE."""
 import argparse
@@ -22,6 +25,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))))
 
 import t2i_amd  # noqa: E402,F401
+from t2i_amd.models import cli  # noqa: E402
 from t2i_amd.models.wgancls.model import WGanCls  # noqa: E402
 from t2i_amd.models.wgancls.trainer import WGanClsTrainer  # noqa: E402
 from t2i_amd.utils.config import config_from_yaml  # noqa: E402
@@ -51,16 +55,18 @@ def main(argv=None):
     mode.add_argument('--train', action='store_true', help='train even if the yml says TRAIN.FLAG: False')
     mode.add_argument('--visualize', action='store_true', help='run the caption visualiser on the latest checkpoint (needs the '
                       'pickled dataset)')
-    mode.add_argument('--eval', choices=('is', 'fid', 'swd'), default=None, help='run the Inception-score, FID or sliced-Wasserstein '
-                      'evaluator on the latest checkpoint (needs the pickled dataset and, except for swd, an Inception checkpoint in '
-                      'EVAL.INCEP_CHECKPOINT_DIR)')
+    mode.add_argument('--eval', choices=('is', 'fid', 'swd', 'msssim'), default=None, help='run the Inception-score, FID, '
+                      'sliced-Wasserstein or multi-scale-SSIM evaluator on the latest checkpoint (needs the pickled dataset and, except '
+                      'for swd and msssim, an Inception checkpoint in EVAL.INCEP_CHECKPOINT_DIR)')
     ap.add_argument('--incep-batch', type=int, default=None, help='--eval: Inception batch size (default EVAL.INCEP_BATCH_SIZE)')
+    cli.add_pairs_argument(ap)
     ap.add_argument('--interp', type=int, default=0, help='--visualize: rounds of interpolation / captioned sheets (default 0)')
     ap.add_argument('--synthetic', action='store_true', help='synthetic on-device dataset instead of cfg.DATASET_DIR')
     ap.add_argument('--steps', type=int, default=None, help='override TRAIN.MAX_STEPS')
     ap.add_argument('--batch', type=int, default=None, help='override TRAIN.BATCH_SIZE')
     ap.add_argument('--graphs', type=int, default=1, help='1: replay the iteration from hipGraphs once it has run eagerly (default)')
     args = ap.parse_args(argv)
+    cli.check_pairs(ap, args)
     print(args.cfg)
     cfg = config_from_yaml(args.cfg)
     if args.batch:
@@ -81,7 +87,7 @@ def main(argv=None):
         wgan = WGanCls(cfg, build_model=False)           # the evaluator creates and restores the generator's variables only
         dataset = load_dataset(cfg, wgan.device)
         ev = WGanClsEval(sess=None, model=wgan, dataset=dataset, cfg=cfg, incep_batch_size=args.incep_batch)
-        return {'is': ev.evaluate_inception, 'fid': ev.evaluate_fid, 'swd': ev.evaluate_swd}[args.eval]()
+        return cli.run_eval(ev, args.eval, args.msssim_pairs)
     if cfg.EVAL.FLAG:
         raise NotImplementedError('EVAL.FLAG: pass --eval is or --eval fid to run the Inception-score / FID evaluation '
                                   '(reference models/wgancls/eval_wgan.py)')
