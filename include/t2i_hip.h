@@ -786,6 +786,29 @@ int t2i_ssim_scale(const float* a, const float* b, int64_t N, int32_t H, int32_t
                    double c1, double c2, double* ssim, double* cs, float* a_half, float* b_half, void* workspace,
                    size_t workspace_bytes, t2i_stream_t stream);
 
+/* ---- k-nearest-neighbour distances and ball counts in fp64 (evaluation/prdc.py: improved precision and recall, Kynkaanniemi et al.
+ * 2019; density and coverage, Naeem et al. 2020; the reference has no such metric).  Added within ABI v13: no existing argument list
+ * changed. ------------------------------------------------------------------------------------------------------------------------ */
+/* Q [M, D] and R [N, D] are dense row-major fp32 on the device.  d2(m, n) = max(|Q_m|^2 + |R_n|^2 - 2 Q_m.R_n, 0), the three sums
+ * accumulated in fp64 from the inputs widened exactly, each pair over the whole D in one fixed order: results are bit-identical for
+ * every value of `segments` and from call to call (no atomics).  `segments` >= 1 splits the candidate range over workgroups (partial
+ * results in the workspace, folded in segment order by a second launch); 0 lets the library choose.
+ *   t2i_knn_dist2:   out[m, 0..k) = the k smallest d2(m, .) in ascending order (device fp64 [M, k]).  With exclude_self = 1 (M == N)
+ *                    candidate n == m is skipped by INDEX: a duplicate row of the query still counts as a neighbour.
+ *   t2i_ball_counts: count[m] = #{n : d2(m, n) <= r2[n]} (device int32 [M], r2 device fp64 [N]), dmin[m] = min_n d2(m, n) (fp64 [M]).
+ * A NaN distance is never selected or counted (d2 < worst, d2 <= r2); a slot with no candidate holds +inf.
+ * Every refusal returns T2I_ERR_INVALID before anything is launched: a NULL pointer; M, N or D < 1; k outside 1..T2I_KNN_MAX_K or
+ * k > N - exclude_self; exclude_self not 0 / 1, or 1 with M != N; segments < 0, > N or > 65536; M D or N D >= 2^31 * 64; M k beyond
+ * int64; a workspace smaller than the query; an output overlapping an input, another output or the workspace (Q and R may be the same
+ * tensor); a misaligned pointer (4 bytes for fp32 and int32, 8 for fp64 and the workspace).  The entries only enqueue work. */
+#define T2I_KNN_MAX_K 8
+size_t t2i_knn_dist2_workspace_bytes(int64_t M, int64_t N, int32_t D, int32_t k, int32_t segments);
+int t2i_knn_dist2(const float* Q, int64_t M, const float* R, int64_t N, int32_t D, int32_t k, int32_t exclude_self, int32_t segments,
+                  double* out, void* workspace, size_t workspace_bytes, t2i_stream_t stream);
+size_t t2i_ball_counts_workspace_bytes(int64_t M, int64_t N, int32_t D, int32_t segments);
+int t2i_ball_counts(const float* Q, int64_t M, const float* R, int64_t N, int32_t D, const double* r2, int32_t segments, int32_t* count,
+                    double* dmin, void* workspace, size_t workspace_bytes, t2i_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

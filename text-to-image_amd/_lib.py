@@ -162,6 +162,10 @@ SIGNATURES = {
     't2i_sorted_l1_mean': (ctypes.c_int, [_p, _p, _i32, _i64, _i64, _p, _p, _sz, _p]),
     't2i_ssim_scale_workspace_bytes': (_sz, [_i64, _i32, _i32, _i32]),
     't2i_ssim_scale': (ctypes.c_int, [_p, _p, _i64, _i32, _i32, _i32, _p, _i32, ctypes.c_double, ctypes.c_double, _p, _p, _p, _p, _p, _sz, _p]),
+    't2i_knn_dist2_workspace_bytes': (_sz, [_i64, _i64, _i32, _i32, _i32]),
+    't2i_knn_dist2': (ctypes.c_int, [_p, _i64, _p, _i64, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),
+    't2i_ball_counts_workspace_bytes': (_sz, [_i64, _i64, _i32, _i32]),
+    't2i_ball_counts': (ctypes.c_int, [_p, _i64, _p, _i64, _i32, _p, _i32, _p, _p, _p, _sz, _p]),
 }
 
 if not os.path.exists(LIB_PATH):

@@ -86,6 +86,12 @@ hipError_t sorted_l1_mean_launch(const float*, const float*, int, int64_t, int64
 size_t ssim_scale_ws(int64_t N, int H, int W, int C, int S);
 hipError_t ssim_scale_launch(const float*, const float*, int64_t, int, int, int, const double*, int, double, double, double*, double*, float*,
                              float*, void*, hipStream_t);
+// implemented in t2i_knn.hip
+int knn_auto_segments(int64_t M, int64_t N);
+size_t knn_dist2_ws(int64_t M, int64_t N, int segments);
+size_t ball_counts_ws(int64_t M, int64_t N, int segments);
+hipError_t knn_dist2_launch(const float*, int64_t, const float*, int64_t, int, int, int, int, double*, void*, hipStream_t);
+hipError_t ball_counts_launch(const float*, int64_t, const float*, int64_t, int, const double*, int, int32_t*, double*, void*, hipStream_t);
 // implemented in t2i_preprocess.hip
 int pillow_table_taps(int filter, int in_size, int out_size);
 hipError_t pillow_tables_launch(int, const int32_t*, int64_t, int, int32_t*, int32_t*, int, hipStream_t);
@@ -2201,6 +2207,83 @@ int t2i_ssim_scale(const float* a, const float* b, int64_t N, int32_t H, int32_t
   }
   return check(ssim_scale_launch(a, b, N, H, W, C, window_host, S, c1, c2, ssim, cs, a_half, b_half, workspace, (hipStream_t)stream),
                "t2i_ssim_scale");
+}
+
+// ---- k-nearest-neighbour distances and ball counts (t2i_knn.hip) -------------------------------------------------------------------
+static const int64_t kKnnLim = ((int64_t)1 << 31) * 64;     // elements of one feature set: the kernels index them with size_t
+static const int32_t kKnnMaxSegments = 65536;
+
+static bool knn_shape_ok(int64_t M, int64_t N, int32_t D, int32_t segments) {
+  return M >= 1 && N >= 1 && D >= 1 && M < (kKnnLim + D - 1) / D && N < (kKnnLim + D - 1) / D && segments >= 0 && segments <= N &&
+         segments <= kKnnMaxSegments;
+}
+
+static bool knn_k_ok(int64_t M, int64_t N, int32_t k, int32_t exclude_self) {
+  return k >= 1 && k <= T2I_KNN_MAX_K && (exclude_self == 0 || (exclude_self == 1 && M == N)) && k <= N - exclude_self &&
+         M <= INT64_MAX / (8 * (int64_t)k);
+}
+
+size_t t2i_knn_dist2_workspace_bytes(int64_t M, int64_t N, int32_t D, int32_t k, int32_t segments) {
+  if (!knn_shape_ok(M, N, D, segments) || k < 1 || k > T2I_KNN_MAX_K) return 0;
+  return knn_dist2_ws(M, N, segments ? segments : knn_auto_segments(M, N));
+}
+
+int t2i_knn_dist2(const float* Q, int64_t M, const float* R, int64_t N, int32_t D, int32_t k, int32_t exclude_self, int32_t segments,
+                  double* out, void* workspace, size_t workspace_bytes, t2i_stream_t stream) {
+  bool ok = Q && R && out && workspace && aligned4(Q) && aligned4(R) && aligned8(out) && aligned8(workspace) &&
+            knn_shape_ok(M, N, D, segments) && knn_k_ok(M, N, k, exclude_self);
+  size_t need = 0;
+  if (ok) {
+    need = t2i_knn_dist2_workspace_bytes(M, N, D, k, segments);
+    const uint64_t q_bytes = (uint64_t)M * D * 4, r_bytes = (uint64_t)N * D * 4, out_bytes = (uint64_t)M * k * 8;
+    ok = workspace_bytes >= need && !swd_overlap(out, out_bytes, Q, q_bytes) && !swd_overlap(out, out_bytes, R, r_bytes) &&
+         !swd_overlap(workspace, need, Q, q_bytes) && !swd_overlap(workspace, need, R, r_bytes) &&
+         !swd_overlap(workspace, need, out, out_bytes);
+  }
+  if (!ok) {
+    set_error("t2i_knn_dist2: bad argument (M=%lld N=%lld D=%d k=%d exclude_self=%d segments=%d, Q %s, R %s, out %s, workspace %s of %zu "
+              "bytes, need %zu; M, N, D >= 1, M D and N D < 2^37, k in 1..%d and <= N - exclude_self, exclude_self 0 or 1 and 1 only "
+              "with M == N, 0 <= segments <= min(N, %d), aligned tensors, out and the workspace apart from Q, R and each other)",
+              (long long)M, (long long)N, D, k, exclude_self, segments, Q ? "given" : "NULL", R ? "given" : "NULL", out ? "given" : "NULL",
+              workspace ? "given" : "NULL", workspace_bytes, need, T2I_KNN_MAX_K, kKnnMaxSegments);
+    return T2I_ERR_INVALID;
+  }
+  return check(knn_dist2_launch(Q, M, R, N, D, k, exclude_self, segments ? segments : knn_auto_segments(M, N), out, workspace,
+                                (hipStream_t)stream), "t2i_knn_dist2");
+}
+
+size_t t2i_ball_counts_workspace_bytes(int64_t M, int64_t N, int32_t D, int32_t segments) {
+  if (!knn_shape_ok(M, N, D, segments)) return 0;
+  return ball_counts_ws(M, N, segments ? segments : knn_auto_segments(M, N));
+}
+
+int t2i_ball_counts(const float* Q, int64_t M, const float* R, int64_t N, int32_t D, const double* r2, int32_t segments, int32_t* count,
+                    double* dmin, void* workspace, size_t workspace_bytes, t2i_stream_t stream) {
+  bool ok = Q && R && r2 && count && dmin && workspace && aligned4(Q) && aligned4(R) && aligned8(r2) && aligned4(count) && aligned8(dmin) &&
+            aligned8(workspace) && knn_shape_ok(M, N, D, segments);
+  size_t need = 0;
+  if (ok) {
+    need = t2i_ball_counts_workspace_bytes(M, N, D, segments);
+    const void* in[3] = {Q, R, r2};
+    const uint64_t in_bytes[3] = {(uint64_t)M * D * 4, (uint64_t)N * D * 4, (uint64_t)N * 8};
+    const void* outp[3] = {count, dmin, workspace};
+    const uint64_t out_bytes[3] = {(uint64_t)M * 4, (uint64_t)M * 8, need};
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) ok = ok && !swd_overlap(outp[i], out_bytes[i], in[j], in_bytes[j]);
+      for (int j = 0; j < i; ++j) ok = ok && !swd_overlap(outp[i], out_bytes[i], outp[j], out_bytes[j]);
+    }
+    ok = ok && workspace_bytes >= need;
+  }
+  if (!ok) {
+    set_error("t2i_ball_counts: bad argument (M=%lld N=%lld D=%d segments=%d, Q %s, R %s, r2 %s, count %s, dmin %s, workspace %s of %zu "
+              "bytes, need %zu; M, N, D >= 1, M D and N D < 2^37, 0 <= segments <= min(N, %d), aligned tensors, count, dmin and the "
+              "workspace apart from Q, R, r2 and each other)",
+              (long long)M, (long long)N, D, segments, Q ? "given" : "NULL", R ? "given" : "NULL", r2 ? "given" : "NULL",
+              count ? "given" : "NULL", dmin ? "given" : "NULL", workspace ? "given" : "NULL", workspace_bytes, need, kKnnMaxSegments);
+    return T2I_ERR_INVALID;
+  }
+  return check(ball_counts_launch(Q, M, R, N, D, r2, segments ? segments : knn_auto_segments(M, N), count, dmin, workspace,
+                                  (hipStream_t)stream), "t2i_ball_counts");
 }
 
 }  // extern "C"

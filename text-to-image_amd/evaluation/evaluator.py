@@ -16,7 +16,8 @@ reference does not have (evaluation/imd.py): each real test image of the batch a
 evaluate_swd is another (evaluation/swd.py): the sliced Wasserstein distance of the same pairs' Laplacian-pyramid patches, per
 resolution level; it needs no Inception net and no EVAL.ACT_STAT_PATH.  evaluate_msssim (evaluation/msssim.py) is the one
 evaluation that compares generated images with each other: the multi-scale structural similarity of pairs of them, which is 1 for a
-generator that ignores z; it needs no Inception net either.
+generator that ignores z; it needs no Inception net either.  evaluate_prdc (evaluation/prdc.py) asks where the generated SET lies:
+precision, recall, density and coverage from k-nearest-neighbour balls around the PreLogits features of evaluate_imd's batches.
 
 A model's evaluator states what differs (DESIGN.md has the table): restore(), dims(), generate_batch(), and the attributes below."""
 import os
@@ -27,7 +28,7 @@ import torch
 from .. import kernels as K
 from ..models.inception.model import IMAGE_SIZE, load_inception_inference
 from ..utils.saver import restore_g_net
-from . import fid, imd, inception_score, msssim, swd
+from . import fid, imd, inception_score, msssim, prdc, swd
 
 
 class GeneratorEval(object):
@@ -255,4 +256,35 @@ class GeneratorEval(object):
         print('MS-SSIM (%s) | mean: %.4f std: %.4f clamped: %d' % (pairs, out['mean'], out['std'], out['clamped']))
         print('MS-SSIM (%s) | cs per scale: %s' % (pairs, ' '.join('%dx%d: %.4f' % (h, w, v) for (h, w), v in zip(out['sides'], out['cs_levels']))))
         out.update(self._kept_samples(keep_samples))
+        return out
+
+    def evaluate_prdc(self, nearest_k=5, keep_samples=False, keep_features=False):
+        """-> ManifoldMetrics.finalize()'s dict (precision, recall, density, coverage, nearest_k, n_real, n_gen) (+ the host pairs
+        real, gen with keep_samples; + real_features, gen_features, host float32, with keep_features).  The batches and their draws
+        from np.random are those of evaluate_imd; per chunk of INCEP_BATCH_SIZE pairs one Inception forward scores both halves.
+        The test split starts a new permutation once it is exhausted, so real features are kept only for the first
+        num_examples // bs batches (one epoch, no image twice: a repeated image's nearest neighbours would be its own copies and
+        every radius would collapse); generated features are kept for all SIZE // bs batches."""
+        if int(nearest_k) != nearest_k or not 1 <= int(nearest_k) <= K.KNN_MAX_K:
+            raise ValueError('evaluate_prdc: nearest_k must be in 1..%d, got %r' % (K.KNN_MAX_K, nearest_k))
+        net = self._inception()
+        self.restore()
+        c = self.incep_batch_size
+        real_batches = self.dataset.test.num_examples // self.bs
+        mm = None
+        for i, (real, gen) in enumerate(self._batches(False, keep_samples, with_real=True)):
+            for s in range(0, self.bs, c):
+                pre_real, pre_gen = imd.pair_features(real[s:s + c], gen[s:s + c], net)
+                if mm is None:
+                    mm = prdc.ManifoldMetrics(pre_gen.shape[1], self.model.device, nearest_k)
+                if i < real_batches:
+                    mm.add_real(pre_real)
+                mm.add_gen(pre_gen)
+        out = mm.finalize()
+        print('PRDC (k = %d) | precision: %.4f recall: %.4f density: %.4f coverage: %.4f | %d real, %d generated' % (
+            out['nearest_k'], out['precision'], out['recall'], out['density'], out['coverage'], out['n_real'], out['n_gen']))
+        if keep_samples:
+            out.update(real=np.concatenate([r for r, _ in self._kept]), gen=np.concatenate([g for _, g in self._kept]))
+        if keep_features:
+            out.update(real_features=mm.real.rows().cpu().numpy(), gen_features=mm.gen.rows().cpu().numpy())
         return out

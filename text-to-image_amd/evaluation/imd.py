@@ -39,18 +39,23 @@ def get_cosine_dist(real_img_act, gen_img_act):
     return np.clip(dist, 0.0, 2.0)
 
 
-def pair_distances(real, gen, net):
+def pair_features(real, gen, net):
     """real, gen: device stores [c, H, W, 3] (uint8, or float32 in [-1, 1] denormalised in the resize kernel; the two may differ
-    in size) -> float64 [c] device distances of the pairs: one Inception forward over both halves, one cosine launch."""
+    in size) -> their PreLogits rows ([c, d], [c, d]) from one Inception forward over both halves."""
     c = real.shape[0]
     if gen.shape[0] != c:
-        raise ValueError('pair_distances: %d real and %d generated images' % (c, gen.shape[0]))
+        raise ValueError('pair_features: %d real and %d generated images' % (c, gen.shape[0]))
     x = torch.empty((2 * c, IMAGE_SIZE, IMAGE_SIZE, 3), dtype=torch.float32, device=real.device)
     K.resample_bilinear(real.contiguous(), IMAGE_SIZE, IMAGE_SIZE, out=x[:c])
     K.resample_bilinear(gen.contiguous(), IMAGE_SIZE, IMAGE_SIZE, out=x[c:])
     _, pre = net(x)
     pre = pre.reshape(2 * c, -1)
-    return K.cosine_distance(pre[:c], pre[c:])
+    return pre[:c], pre[c:]
+
+
+def pair_distances(real, gen, net):
+    """-> float64 [c] device distances of the pairs of pair_features: one Inception forward, one cosine launch."""
+    return K.cosine_distance(*pair_features(real, gen, net))
 
 
 def compute_imd(real_img, gen_img, net, batch_size, verbose=False):

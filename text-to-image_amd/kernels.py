@@ -2115,3 +2115,58 @@ def ssim_scale(a, b, window, c1, c2, downsample=True):
         check(lib.t2i_ssim_scale(_ptr(a), _ptr(b), N, H, W, C, win.ctypes.data_as(ctypes.c_void_p), S, c1, c2, _ptr(ssim), _ptr(cs),
                                  _ptr(ah), _ptr(bh), wsp, wsn, _stream()), 't2i_ssim_scale')
     return ssim, cs, ah, bh
+
+
+# ---- k-nearest-neighbour distances and ball counts in fp64 (csrc/t2i_knn.hip; evaluation/prdc.py is the caller) ----------------
+KNN_MAX_K = 8                                           # include/t2i_hip.h T2I_KNN_MAX_K
+KNN_MAX_SEGMENTS = 65536
+
+
+def _knn_sets(q, r, name, segments):
+    _f32_nd(q, '%s: q' % name, 2); _f32_nd(r, '%s: r' % name, 2)
+    if q.shape[1] != r.shape[1] or q.device != r.device:
+        raise ValueError('%s: q %s on %s and r %s on %s must share the feature dimension and the device' % (
+            name, tuple(q.shape), q.device, tuple(r.shape), r.device))
+    M, D = (int(s) for s in q.shape)
+    N = int(r.shape[0])
+    segments = int(segments)
+    if min(M, N, D) < 1 or max(M, N) * D >= 1 << 37 or not 0 <= segments <= min(N, KNN_MAX_SEGMENTS):
+        raise ValueError('%s: q %s, r %s, segments %d: M, N, D >= 1, fewer than 2^37 elements per set, 0 <= segments <= min(N, %d)' % (
+            name, tuple(q.shape), tuple(r.shape), segments, KNN_MAX_SEGMENTS))
+    return M, N, D, segments
+
+
+def knn_dist2(q, r, k, exclude_self=False, segments=0, out=None):
+    """The k smallest squared distances from every row of q [M, D] to the rows of r [N, D] (device float32): float64 [M, k],
+    ascending.  d2 = max(|q|^2 + |r|^2 - 2 q.r, 0) with the three sums in fp64 (t2i_knn_dist2).  exclude_self (M == N) skips candidate
+    n == m by index.  segments splits the candidates over workgroups (0: the library chooses); the result does not depend on it."""
+    M, N, D, segments = _knn_sets(q, r, 'knn_dist2', segments)
+    k, ex = int(k), int(bool(exclude_self))
+    if not 1 <= k <= KNN_MAX_K or k > N - ex or (ex and M != N):
+        raise ValueError('knn_dist2: k = %d of %d candidates (exclude_self %d, %d queries): k in 1..%d, k <= N - exclude_self, '
+                         'exclude_self only with M == N' % (k, N, ex, M, KNN_MAX_K))
+    if out is None:
+        out = torch.empty((M, k), dtype=torch.float64, device=q.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (M, k) or not out.is_contiguous() or out.device != q.device:
+        raise ValueError('knn_dist2: out must be a contiguous float64 [%d, %d] tensor on %s, got %s %s on %s' % (
+            M, k, q.device, out.dtype, tuple(out.shape), out.device))
+    if _live(q):
+        wsp, wsn = _ws_args(q, int(lib.t2i_knn_dist2_workspace_bytes(M, N, D, k, segments)))
+        check(lib.t2i_knn_dist2(_ptr(q), M, _ptr(r), N, D, k, ex, segments, _ptr(out), wsp, wsn, _stream()), 't2i_knn_dist2')
+    return out
+
+
+def ball_counts(q, r, r2, segments=0):
+    """-> (count int32 [M], dmin float64 [M]): count[m] = #{n : d2(q[m], r[n]) <= r2[n]}, dmin[m] = min_n d2(q[m], r[n]), both from
+    one pass (t2i_ball_counts; d2 as in knn_dist2).  r2: device float64 [N]."""
+    M, N, D, segments = _knn_sets(q, r, 'ball_counts', segments)
+    if r2.dtype != torch.float64 or tuple(r2.shape) != (N,) or not r2.is_contiguous() or r2.device != q.device:
+        raise ValueError('ball_counts: r2 must be a contiguous float64 [%d] tensor on %s, got %s %s on %s' % (
+            N, q.device, r2.dtype, tuple(r2.shape), r2.device))
+    count = torch.empty(M, dtype=torch.int32, device=q.device)
+    dmin = torch.empty(M, dtype=torch.float64, device=q.device)
+    if _live(q):
+        wsp, wsn = _ws_args(q, int(lib.t2i_ball_counts_workspace_bytes(M, N, D, segments)))
+        check(lib.t2i_ball_counts(_ptr(q), M, _ptr(r), N, D, _ptr(r2), segments, _ptr(count), _ptr(dmin), wsp, wsn, _stream()),
+              't2i_ball_counts')
+    return count, dmin

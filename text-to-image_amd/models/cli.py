@@ -6,6 +6,9 @@ import os
 EVAL_MODES = ('is', 'fid', 'imd', 'swd')
 PAIR_MODES = ('msssim',)            # evaluations of pairs of generated images: evaluate_<mode>(pairs=...)
 PAIRINGS = ('random', 'caption')
+FEATURE_MODES = ('prdc',)           # evaluations of the two feature SETS: evaluate_<mode>(nearest_k=...)
+KNN_MAX_K = 8                       # kernels.KNN_MAX_K (not imported: argument errors come before anything touches the device library)
+DEFAULT_NEAREST_K = 5
 
 
 class Parser(argparse.ArgumentParser):
@@ -14,6 +17,7 @@ class Parser(argparse.ArgumentParser):
     def parse_args(self, *args, **kwargs):
         parsed = super(Parser, self).parse_args(*args, **kwargs)
         check_pairs(self, parsed)
+        check_nearest_k(self, parsed)
         return parsed
 
 
@@ -22,13 +26,15 @@ def make_parser(default_cfg):
     ap.add_argument('--cfg', default=default_cfg, help='Relative path to the config of the model')
     mode = ap.add_mutually_exclusive_group()
     mode.add_argument('--train', action='store_true', help='train even if the yml says TRAIN.FLAG: False')
-    mode.add_argument('--eval', choices=EVAL_MODES + PAIR_MODES, default=None, help='Inception score, FID, Inception match distance, '
-                      'sliced Wasserstein distance or multi-scale SSIM between generated pairs of the latest checkpoint (needs the pickled '
-                      'dataset and, except for swd and msssim, an Inception checkpoint in EVAL.INCEP_CHECKPOINT_DIR)')
+    mode.add_argument('--eval', choices=EVAL_MODES + PAIR_MODES + FEATURE_MODES, default=None, help='Inception score, FID, Inception match '
+                      'distance, sliced Wasserstein distance, multi-scale SSIM between generated pairs or precision / recall / density / '
+                      'coverage of the latest checkpoint (needs the pickled dataset and, except for swd and msssim, an Inception '
+                      'checkpoint in EVAL.INCEP_CHECKPOINT_DIR)')
     mode.add_argument('--visualize', action='store_true', help='run the caption visualiser on the latest checkpoint (needs the '
                       'pickled dataset)')
     ap.add_argument('--incep-batch', type=int, default=None, help='--eval: Inception batch size (default EVAL.INCEP_BATCH_SIZE)')
     add_pairs_argument(ap)
+    add_nearest_k_argument(ap)
     ap.add_argument('--interp', type=int, default=0, help='--visualize: rounds of interpolation / captioned sheets (default 0)')
     ap.add_argument('--synthetic', action='store_true', help='--train: synthetic on-device dataset instead of cfg.DATASET_DIR')
     ap.add_argument('--steps', type=int, default=None, help='--train: stop after this many updates')
@@ -47,6 +53,20 @@ def check_pairs(ap, args):
     """--msssim-pairs without --eval msssim is an argument error."""
     if args.msssim_pairs is not None and args.eval not in PAIR_MODES:
         ap.error('--msssim-pairs needs --eval msssim')
+
+
+def add_nearest_k_argument(ap):
+    ap.add_argument('--prdc-k', type=int, default=None, help='--eval prdc: the k of the k-nearest-neighbour balls, 1..%d (default %d, '
+                    'the prdc package\'s; 3 reproduces the precision and recall of Kynkaanniemi et al.)' % (KNN_MAX_K, DEFAULT_NEAREST_K))
+
+
+def check_nearest_k(ap, args):
+    """--prdc-k without --eval prdc, or outside 1..KNN_MAX_K, is an argument error."""
+    if args.prdc_k is not None:
+        if args.eval not in FEATURE_MODES:
+            ap.error('--prdc-k needs --eval prdc')
+        if not 1 <= args.prdc_k <= KNN_MAX_K:
+            ap.error('--prdc-k must be in 1..%d' % KNN_MAX_K)
 
 
 def check_mode(args, cfg, visualiser):
@@ -80,10 +100,16 @@ def make_dirs(cfg):
             os.makedirs(d)
 
 
-EVAL_METHODS = dict(zip(EVAL_MODES + PAIR_MODES, ('evaluate_inception', 'evaluate_fid', 'evaluate_imd', 'evaluate_swd', 'evaluate_msssim')))
+EVAL_METHODS = dict(zip(EVAL_MODES + PAIR_MODES + FEATURE_MODES,
+                        ('evaluate_inception', 'evaluate_fid', 'evaluate_imd', 'evaluate_swd', 'evaluate_msssim', 'evaluate_prdc')))
 
 
-def run_eval(ev, mode, pairs=None):
-    """The requested mode's method only, looked up by name; a pair mode takes the pairing (default random)."""
+def run_eval(ev, mode, pairs=None, nearest_k=None):
+    """The requested mode's method only, looked up by name; a pair mode takes the pairing (default random), a feature mode the k of
+    its nearest-neighbour balls (default 5)."""
     fn = getattr(ev, EVAL_METHODS[mode])
-    return fn(pairs=pairs or PAIRINGS[0]) if mode in PAIR_MODES else fn()
+    if mode in PAIR_MODES:
+        return fn(pairs=pairs or PAIRINGS[0])
+    if mode in FEATURE_MODES:
+        return fn(nearest_k=nearest_k or DEFAULT_NEAREST_K)
+    return fn()

@@ -38,7 +38,7 @@ def main(argv=None):
         from t2i_amd.models.gancls.eval_gancls import GanClsEval
         gancls = GanCls(cfg, build_model=False)          # the evaluator creates and restores the generator's variables only
         dataset = load_dataset(cfg, gancls.device)
-        return run_eval(GanClsEval(sess=None, model=gancls, dataset=dataset, cfg=cfg, incep_batch_size=args.incep_batch), args.eval, args.msssim_pairs)
+        return run_eval(GanClsEval(sess=None, model=gancls, dataset=dataset, cfg=cfg, incep_batch_size=args.incep_batch), args.eval, args.msssim_pairs, args.prdc_k)
     if args.visualize:
         from t2i_amd.models.gancls.visualize_gancls import GanClsVisualizer
         gancls = GanCls(cfg, build_model=False)          # the visualiser creates and restores the generator's variables only

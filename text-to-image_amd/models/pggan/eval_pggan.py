@@ -1,7 +1,7 @@
 """PGGANEval — reference models/pggan/eval_pggan.py: the Inception score of a stage's generator (stage 7, 256 x 256, by default).
 
-    python text-to-image_amd/models/pggan/eval_pggan.py --cfg models/pggan/cfg/flowers.yml --eval is|fid|swd|msssim [--stage 7] [--batch 64]
-                                                        [--msssim-pairs random|caption]
+    python text-to-image_amd/models/pggan/eval_pggan.py --cfg models/pggan/cfg/flowers.yml --eval is|fid|swd|msssim|prdc [--stage 7] [--batch 64]
+                                                        [--msssim-pairs random|caption] [--prdc-k K]
 
 The generator's variables (`g_net`) are restored from CHECKPOINT_DIR/stage%d/; a failed load raises with the reference's
 message.  The dataset is `TextDataset(DATASET_DIR, MODEL.SIZES[stage - 1])` (256 at stage 7, as the reference reads).  Per batch
@@ -25,6 +25,10 @@ batch (default: `--batch`).
 - evaluate_msssim: an addition (evaluation/msssim.py): the multi-scale SSIM between pairs of generated images, the paper's
   diversity metric — `--msssim-pairs random` pairs image i of a batch with image i + batch // 2, `caption` pairs two images of one
   caption and different z.  It needs no Inception net; its five scales need images of at least 16 x 16, so stage 3 or later.
+
+- evaluate_prdc: an addition (evaluation/prdc.py): precision, recall, density and coverage of the generated set against the real
+  test images in Inception feature space (`--prdc-k K` nearest neighbours, default 5).  It needs the Inception checkpoint but not
+  EVAL.ACT_STAT_PATH; `--ema` and `--stage` apply.
 
 The PGGAN generator has no batch norm, so there is no training / inference mode to choose between the two."""
 import argparse
@@ -103,8 +107,9 @@ def main(argv=None, **widths):
     from t2i_amd.utils.config import config_from_yaml
     ap = argparse.ArgumentParser()
     ap.add_argument('--cfg', required=True, help='models/pggan/cfg/flowers.yml or birds.yml')
-    ap.add_argument('--eval', choices=['is', 'fid', 'swd', 'msssim'], default='is')
+    ap.add_argument('--eval', choices=['is', 'fid', 'swd', 'msssim', 'prdc'], default='is')
     cli.add_pairs_argument(ap)
+    cli.add_nearest_k_argument(ap)
     ap.add_argument('--stage', type=int, default=7, help='the stage whose generator is scored [7]')
     ap.add_argument('--batch', type=int, default=64, help='images generated (and scored) per batch [64]')
     ap.add_argument('--incep-batch', type=int, default=None, help='Inception batch (default: --batch)')
@@ -117,6 +122,7 @@ def main(argv=None, **widths):
     if args.eval in ('swd', 'msssim') and args.stage < 3:
         ap.error('--eval %s needs images of at least 16 x 16: --stage 3 or later' % args.eval)
     cli.check_pairs(ap, args)
+    cli.check_nearest_k(ap, args)
     if args.eval == 'msssim' and args.msssim_pairs != 'caption' and args.batch < 2:
         ap.error('--eval msssim pairs image i of a batch with image i + batch // 2: --batch 2 or more (or --msssim-pairs caption)')
     cfg = config_from_yaml(args.cfg)
@@ -129,7 +135,7 @@ def main(argv=None, **widths):
     m = stage_model(cfg, args.stage, args.batch, dataset, dev, **widths)
     ev = PGGANEval(None, m, dataset, cfg, incep_batch_size=args.incep_batch)
     ev.ema = args.ema
-    out = cli.run_eval(ev, args.eval, args.msssim_pairs)
+    out = cli.run_eval(ev, args.eval, args.msssim_pairs, args.prdc_k)
     out.pop('preds', None)
     return out
 

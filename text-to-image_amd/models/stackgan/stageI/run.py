@@ -38,7 +38,7 @@ def main(argv=None):
         from t2i_amd.models.stackgan.stageI.eval_stagei import StageIEval
         stage_i = ConditionalGan(cfg, build_model=False)     # the evaluator creates and restores the generator's variables only
         dataset = load_dataset(cfg, stage_i.device)
-        return run_eval(StageIEval(sess=None, model=stage_i, dataset=dataset, cfg=cfg, incep_batch_size=args.incep_batch), args.eval, args.msssim_pairs)
+        return run_eval(StageIEval(sess=None, model=stage_i, dataset=dataset, cfg=cfg, incep_batch_size=args.incep_batch), args.eval, args.msssim_pairs, args.prdc_k)
     if args.visualize:
         from t2i_amd.models.stackgan.stageI.visualize_stagei import StageIVisualizer
         stage_i = ConditionalGan(cfg, build_model=False)     # the visualiser creates and restores the generator's variables only

@@ -41,7 +41,7 @@ def main(argv=None):
         from t2i_amd.models.stackgan.stageII.eval_stageii import StageIIEval
         stage_ii = ConditionalGan(stage_i, cfg, build_model=False)
         dataset = load_dataset(cfg, stage_ii.device)
-        return run_eval(StageIIEval(sess=None, model=stage_ii, dataset=dataset, cfg=cfg, incep_batch_size=args.incep_batch), args.eval, args.msssim_pairs)
+        return run_eval(StageIIEval(sess=None, model=stage_ii, dataset=dataset, cfg=cfg, incep_batch_size=args.incep_batch), args.eval, args.msssim_pairs, args.prdc_k)
     if args.visualize:
         from t2i_amd.models.stackgan.stageII.visualize_stageii import StageIIVisualizer
         stage_ii = ConditionalGan(stage_i, cfg, build_model=False)
