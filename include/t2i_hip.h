@@ -343,7 +343,8 @@ int t2i_ca_kl_bwd(const float* mean, const float* log_sigma, const float* eps, c
 int t2i_adam_tf(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, const float* lr_t_dev, float beta1,
                 float beta2, float eps, float grad_scale, t2i_stream_t stream);
 /* t2i_adam_tf plus tf.train.ExponentialMovingAverage of the updated weights, in the same launch (v13, added without a version
- * change: no existing argument list moved).  w, m, v after the call are bit for bit what t2i_adam_tf writes from the same inputs;
+ * change: no existing argument list moved).  w, m, v after the call are bit for bit what t2i_adam_tf writes from the same inputs
+ * (the three Adam entries launch instantiations of one kernel template, whose update statements are written once);
  * then, per element, in fp32 and without fma contraction,
  *   omd = 1 - decay;  ema = ema - omd * (ema - w_new)
  * so the shadow equals a step-by-step fp32 restatement on the host bit for bit.  decay is read from *ema_decay_dev when that

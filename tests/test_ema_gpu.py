@@ -1,7 +1,8 @@
 """The generator weight EMA on the GPU: t2i_adam_tf_ema against t2i_adam_tf and a step-by-step fp32
-restatement of the shadow, bit for bit; its refusals; AdamTF.apply under graph replay; PGGAN(g_ema=...) eager and replayed; the
+restatement of the shadow, bit for bit, with t2i_adam_tf itself held to the float64 oracle; its refusals; AdamTF.apply under graph replay; PGGAN(g_ema=...) eager and replayed; the
 stage 1 -> 2t -> 2 schedule with shadows in the checkpoints; visualize_pggan.py --ema."""
 import ctypes
+import math
 import os
 import random
 import sys
@@ -16,6 +17,7 @@ for p in (ROOT, os.path.join(ROOT, 'tests')):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+from test_kernels_gpu import relerr  # noqa: E402
 from test_pggan_real_gpu import _cfg, data  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
@@ -24,6 +26,7 @@ DEV = torch.device('cuda', 0)
 EMA = '/ExponentialMovingAverage'
 TINY = dict(fmap_base=32, fmap_max=16, z_dim=8, embed_dim=32, compr_embed_dim=16)      # tests/test_pggan.py's widths
 BATCH = 3
+ADAM_BOUND = 1e-6                  # the project's bound for an Adam launch (test_adam_golden)
 
 
 def _bits(t):
@@ -44,6 +47,15 @@ def _inputs(n, seed):
     g = torch.Generator(device=DEV).manual_seed(seed)
     r = lambda: torch.randn(n, generator=g, device=DEV)       # noqa: E731
     return dict(w=r(), g=r() * 3.0, m=r() * 0.1, v=r().abs() * 0.01, s=r())
+
+
+def _oracle_step(x, lr_t, beta1, beta2, gscale):
+    """oracle.np_ops.adam_tf in float64 on the inputs of one launch: the fp32 step size and the scaled gradient as the kernel sees them
+    (gscale is a power of two: the product is exact).  At t = 1 the oracle's lr_t is lr * sqrt(1 - beta2) / (1 - beta1)."""
+    from oracle import np_ops as O
+    f64 = lambda t: t.detach().cpu().numpy().astype(np.float64)       # noqa: E731
+    lr = float(np.float32(lr_t)) * (1.0 - beta1) / math.sqrt(1.0 - beta2)
+    return O.adam_tf(f64(x['w']), f64(x['g']) * gscale, f64(x['m']) if beta1 else np.zeros(x['w'].numel()), f64(x['v']), 1, lr, beta1, beta2)
 
 
 @pytest.mark.parametrize('beta1', [0.0, 0.5])
@@ -72,6 +84,11 @@ def test_fused_launch_equals_adam_tf_and_the_host_recursion(n, beta1):
                     torch.cuda.synchronize()
                     what = (n, beta1, lr_dev, decay, decay_dev)
                     assert not torch.equal(w0, x['w']), what
+                    # the plain launch against the float64 oracle: the fused launches below are held to its bits
+                    w_ref, m_ref, v_ref = _oracle_step(x, lr_t, beta1, 0.99, 0.5)
+                    errs = (relerr(w0, w_ref), relerr(v0, v_ref), relerr(m0, m_ref) if beta1 else 0.0)
+                    print('adam_tf vs float64 oracle %s: w %.2e v %.2e m %.2e' % ((what,) + errs))
+                    assert max(errs) <= ADAM_BOUND, (what, errs)
                     assert torch.equal(_bits(w1), _bits(w0)) and torch.equal(_bits(v1), _bits(v0)), what
                     if beta1:
                         assert torch.equal(_bits(m1), _bits(m0)), what

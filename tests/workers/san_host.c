@@ -101,7 +101,38 @@ int main(void) {
     rejected += t2i_trunc_normal(dummy, 4, 1, 0, 0.f, 1.f, 2.f, -2.f, NULL) != T2I_OK;
     rejected += t2i_zero_ranges(dummy, NULL, 3, NULL) != T2I_OK;
     rejected += t2i_zero_ranges(dummy, (const int64_t*)big, 0, NULL) != T2I_OK;
-    if (rejected != 13) { fprintf(stderr, "only %d of 13 invalid calls were rejected\n", rejected); return 3; }
+    /* the three Adam entries: every refusal they share and the slot tables' own, each with its entry's name and reason */
+    _Alignas(16) static float a[6][16];
+    float *w = a[0], *g = a[1], *m = a[2], *v = a[3], *e = a[4];
+    const int64_t* ends = (const int64_t*)a[5];
+    const float* mult = a[5] + 8;
+#define REFUSED(call, text) (rejected += (call) != T2I_OK && strstr(t2i_last_error(), text) != NULL)
+    REFUSED(t2i_adam_tf(NULL, g, m, v, 16, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, NULL), "t2i_adam_tf: bad argument");
+    REFUSED(t2i_adam_tf(w, g, m, v, 0, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, NULL), "t2i_adam_tf: bad argument");
+    REFUSED(t2i_adam_tf(w, g, NULL, v, 16, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, NULL), "t2i_adam_tf: m may be NULL only with beta1 == 0");
+    REFUSED(t2i_adam_tf(w + 1, g, m, v, 12, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, NULL), "t2i_adam_tf: arena must be 16-byte aligned");
+    REFUSED(t2i_adam_tf_ema(w, NULL, m, v, e, 16, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, 0.5f, NULL, NULL), "t2i_adam_tf_ema: bad argument");
+    REFUSED(t2i_adam_tf_ema(w, g, m, v, NULL, 16, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, 0.5f, NULL, NULL), "t2i_adam_tf_ema: ema is NULL");
+    REFUSED(t2i_adam_tf_ema(w, g, NULL, v, e, 16, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, 0.5f, NULL, NULL), "t2i_adam_tf_ema: m may be NULL only with beta1 == 0");
+    REFUSED(t2i_adam_tf_ema(w, g, m, v, e + 1, 12, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, 0.5f, NULL, NULL), "t2i_adam_tf_ema: arena and shadow must be 16-byte aligned");
+    REFUSED(t2i_adam_tf_ema(w, g, m, v, v + 4, 16, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, 0.5f, NULL, NULL), "t2i_adam_tf_ema: ema overlaps");
+    REFUSED(t2i_adam_tf_ema(w, g, m, v, e, 16, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, 1.5f, NULL, NULL), "t2i_adam_tf_ema: ema_decay 1.5 is outside");
+    REFUSED(t2i_adam_tf_slots(w, g, m, v, e, 16, NULL, mult, 1, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, 0.5f, NULL, NULL), "t2i_adam_tf_slots: bad argument");
+    REFUSED(t2i_adam_tf_slots(w, g, m, v, e, 14, ends, mult, 1, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, 0.5f, NULL, NULL), "t2i_adam_tf_slots: n = 14");
+    REFUSED(t2i_adam_tf_slots(w, g, m, v, e, 16, ends, mult, 0, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, 0.5f, NULL, NULL), "t2i_adam_tf_slots: n_slots = 0");
+    REFUSED(t2i_adam_tf_slots(w, g, NULL, v, e, 16, ends, mult, 1, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, 0.5f, NULL, NULL), "grad * grad_scale * grad_mult");
+    REFUSED(t2i_adam_tf_slots(w, g, m, v + 2, e, 8, ends, mult, 1, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, 0.5f, NULL, NULL), "t2i_adam_tf_slots: arena and shadow must be 16-byte aligned");
+    REFUSED(t2i_adam_tf_slots(w, g, m, v, e, 16, (const int64_t*)(a[5] + 1), mult, 1, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, 0.5f, NULL, NULL), "slot_end_dev must be 8-byte aligned");
+    REFUSED(t2i_adam_tf_slots(w, g, m, v, g + 12, 16, ends, mult, 1, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, 0.5f, NULL, NULL), "t2i_adam_tf_slots: ema overlaps");
+    REFUSED(t2i_adam_tf_slots(w, g, m, v, e, 16, (const int64_t*)(e + 14), mult, 1, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, 0.5f, NULL, NULL), "a slot table overlaps an arena");
+    REFUSED(t2i_adam_tf_slots(w, g, m, v, e, 16, ends, mult, 1, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, -0.5f, NULL, NULL), "t2i_adam_tf_slots: ema_decay -0.5 is outside");
+    /* several faults at once: the first in the entry's order is the one reported */
+    REFUSED(t2i_adam_tf_slots(w, g, NULL, v, e, 16, (const int64_t*)(a[5] + 1), mult, 0, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, 7.f, NULL, NULL), "n_slots = 0");
+    REFUSED(t2i_adam_tf_slots(w, g, m, v, w, 16, (const int64_t*)(a[5] + 1), mult, 1, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, 7.f, NULL, NULL), "slot_end_dev must be 8-byte aligned");
+    REFUSED(t2i_adam_tf_slots(w, g, m, v, e, 16, ends, w, 1, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, 7.f, NULL, NULL), "a slot table overlaps an arena");
+    REFUSED(t2i_adam_tf_ema(w, g, NULL, v, NULL, 16, 1e-3f, NULL, 0.5f, 0.99f, 1e-8f, 1.f, 7.f, NULL, NULL), "ema is NULL");
+#undef REFUSED
+    if (rejected != 36) { fprintf(stderr, "only %d of 36 invalid calls were rejected\n", rejected); return 3; }
     if (!t2i_last_error()[0]) { fprintf(stderr, "no error message after a rejected call\n"); return 3; }
   }
   printf("san_host: %d host-side queries, %d invalid compute calls rejected, no sanitizer report (checksum %llu)\n", calls, rejected, acc);

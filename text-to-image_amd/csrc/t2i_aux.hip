@@ -1549,60 +1549,26 @@ hipError_t row_scale_launch(const void* g, const float* coef, int B, int64_t per
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// tf.train.AdamOptimizer over a flat arena
+// tf.train.AdamOptimizer over a flat arena: one kernel template for the plain update (t2i_adam_tf), the update with a shadow
+// (t2i_adam_tf_ema) and either with per-slot multipliers (t2i_adam_tf_slots)
 // ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void adam_tf_kernel(float* __restrict__ w, const float* __restrict__ g,
-                                                      float* __restrict__ m, float* __restrict__ v, size_t n, float lr_val,
-                                                      const float* __restrict__ lr_dev, float b1, float b2, float eps,
-                                                      float gscale) {
-  const float lr_t = lr_dev ? *lr_dev : lr_val;   // device scalar: a captured graph replays with a new step size
-  const size_t n4 = n >> 2;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (size_t i = t; i < n4; i += stride) {
-    float4 W = reinterpret_cast<float4*>(w)[i];
-    const float4 G0 = reinterpret_cast<const float4*>(g)[i];
-    // beta1 == 0 (the wgancls optimizers: Adam(0, 0.9)): m_t = g_t whatever m_{t-1} was — the old moment is not read
-    // (6 instead of 7 streams over the arena); m == NULL (round 4, only with beta1 == 0): it is not written either — m_t is
-    // grad * grad_scale, which the caller can form whenever a checkpoint wants it (5 streams)
-    float4 M = b1 != 0.f ? reinterpret_cast<float4*>(m)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 V = reinterpret_cast<float4*>(v)[i];
-    float gx = G0.x * gscale, gy = G0.y * gscale, gz = G0.z * gscale, gw = G0.w * gscale;
-    M.x = b1 * M.x + (1.f - b1) * gx; M.y = b1 * M.y + (1.f - b1) * gy;
-    M.z = b1 * M.z + (1.f - b1) * gz; M.w = b1 * M.w + (1.f - b1) * gw;
-    V.x = b2 * V.x + (1.f - b2) * gx * gx; V.y = b2 * V.y + (1.f - b2) * gy * gy;
-    V.z = b2 * V.z + (1.f - b2) * gz * gz; V.w = b2 * V.w + (1.f - b2) * gw * gw;
-    W.x -= lr_t * M.x / (sqrtf(V.x) + eps); W.y -= lr_t * M.y / (sqrtf(V.y) + eps);
-    W.z -= lr_t * M.z / (sqrtf(V.z) + eps); W.w -= lr_t * M.w / (sqrtf(V.w) + eps);
-    reinterpret_cast<float4*>(w)[i] = W;
-    if (m) reinterpret_cast<float4*>(m)[i] = M;
-    reinterpret_cast<float4*>(v)[i] = V;
-  }
-  for (size_t i = (n4 << 2) + t; i < n; i += stride) {
-    const float gg = g[i] * gscale;
-    const float mm = b1 * (b1 != 0.f ? m[i] : 0.f) + (1.f - b1) * gg;
-    const float vv = b2 * v[i] + (1.f - b2) * gg * gg;
-    if (m) m[i] = mm;
-    v[i] = vv;
-    w[i] -= lr_t * mm / (sqrtf(vv) + eps);
-  }
-}
-
-hipError_t adam_tf_launch(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, const float* lr_dev,
-                          float b1, float b2, float eps, float gscale, hipStream_t stream) {
-  const int adam_cap = tuning().adam_blocks;
-  size_t nb = ((((size_t)n + 3) >> 2) + 255) / 256;
-  if (nb > (size_t)adam_cap) nb = adam_cap;
-  hipLaunchKernelGGL(adam_tf_kernel, dim3((int)nb), dim3(256), 0, stream, w, g, m, v, (size_t)n,
-                     lr_t, lr_dev, b1, b2, eps, gscale);
-  return hipGetLastError();
+// One element's update under the file's default contraction: the only place the Adam statements are written.  Every instantiation
+// below writes the same w, m, v for the same gs and lr — measured, profiles/adam_fold.txt: which product of a sum the backend fuses
+// is its choice, and it follows the code around the call (see the scalar tail).
+// beta1 == 0 (the wgancls optimizers: Adam(0, 0.9)): m_t = g_t whatever m_{t-1} was — the caller passes m = 0 and does not read the
+// old moment (6 instead of 7 streams over the arena); m == NULL (only with beta1 == 0): it is not written either — m_t is
+// grad * grad_scale, which the caller can form whenever a checkpoint wants it (5 streams).
+__device__ __forceinline__ void adam_step(float& w, float g, float& m, float& v, float gs, float lr, float b1, float b2, float eps) {
+  g = g * gs;
+  m = b1 * m + (1.f - b1) * g;
+  v = b2 * v + (1.f - b2) * g * g;
+  w -= lr * m / (sqrtf(v) + eps);
 }
 
 // tf.train.ExponentialMovingAverage of the weights, formed in the pass that updates them: ema -= (1 - decay) * (ema - w_t).
 // One more read and one more write per element (28 instead of 20 bytes at beta1 == 0; a pass of its own would read w_t again: 12
 // bytes and a launch).  The shadow statement is compiled without fma contraction — it then equals a step-by-step fp32 restatement
-// on the host bit for bit; the Adam arithmetic above it is adam_tf_kernel's, statement for statement, under the file's default
-// contraction, so w, m, v are bit for bit what that kernel writes.
+// on the host bit for bit.
 __device__ __forceinline__ float ema_step(float s, float w, float omd) {
 #pragma clang fp contract(off)
   const float d = s - w;
@@ -1610,144 +1576,98 @@ __device__ __forceinline__ float ema_step(float s, float w, float omd) {
   return s - p;
 }
 
-__global__ __launch_bounds__(256) void adam_tf_ema_kernel(float* __restrict__ w, const float* __restrict__ g,
-                                                          float* __restrict__ m, float* __restrict__ v,
-                                                          float* __restrict__ ema, size_t n, float lr_val,
-                                                          const float* __restrict__ lr_dev, float b1, float b2, float eps,
-                                                          float gscale, float decay_val, const float* __restrict__ decay_dev) {
-  const float lr_t = lr_dev ? *lr_dev : lr_val;
-  const float omd = 1.0f - (decay_dev ? *decay_dev : decay_val);   // device scalar: a captured graph replays with a new decay
-  const size_t n4 = n >> 2;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (size_t i = t; i < n4; i += stride) {
-    float4 W = reinterpret_cast<float4*>(w)[i];
-    const float4 G0 = reinterpret_cast<const float4*>(g)[i];
-    float4 M = b1 != 0.f ? reinterpret_cast<float4*>(m)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 V = reinterpret_cast<float4*>(v)[i];
-    float4 E = reinterpret_cast<float4*>(ema)[i];
-    float gx = G0.x * gscale, gy = G0.y * gscale, gz = G0.z * gscale, gw = G0.w * gscale;
-    M.x = b1 * M.x + (1.f - b1) * gx; M.y = b1 * M.y + (1.f - b1) * gy;
-    M.z = b1 * M.z + (1.f - b1) * gz; M.w = b1 * M.w + (1.f - b1) * gw;
-    V.x = b2 * V.x + (1.f - b2) * gx * gx; V.y = b2 * V.y + (1.f - b2) * gy * gy;
-    V.z = b2 * V.z + (1.f - b2) * gz * gz; V.w = b2 * V.w + (1.f - b2) * gw * gw;
-    W.x -= lr_t * M.x / (sqrtf(V.x) + eps); W.y -= lr_t * M.y / (sqrtf(V.y) + eps);
-    W.z -= lr_t * M.z / (sqrtf(V.z) + eps); W.w -= lr_t * M.w / (sqrtf(V.w) + eps);
-    E.x = ema_step(E.x, W.x, omd); E.y = ema_step(E.y, W.y, omd);
-    E.z = ema_step(E.z, W.z, omd); E.w = ema_step(E.w, W.w, omd);
-    reinterpret_cast<float4*>(w)[i] = W;
-    if (m) reinterpret_cast<float4*>(m)[i] = M;
-    reinterpret_cast<float4*>(v)[i] = V;
-    reinterpret_cast<float4*>(ema)[i] = E;
-  }
-  for (size_t i = (n4 << 2) + t; i < n; i += stride) {
-    const float gg = g[i] * gscale;
-    const float mm = b1 * (b1 != 0.f ? m[i] : 0.f) + (1.f - b1) * gg;
-    const float vv = b2 * v[i] + (1.f - b2) * gg * gg;
-    if (m) m[i] = mm;
-    v[i] = vv;
-    float ww = w[i];
-    ww -= lr_t * mm / (sqrtf(vv) + eps);
-    w[i] = ww;
-    ema[i] = ema_step(ema[i], ww, omd);
-  }
-}
-
-hipError_t adam_tf_ema_launch(float* w, const float* g, float* m, float* v, float* ema, int64_t n, float lr_t, const float* lr_dev,
-                              float b1, float b2, float eps, float gscale, float decay, const float* decay_dev, hipStream_t stream) {
-  const int adam_cap = tuning().adam_blocks;
-  size_t nb = ((((size_t)n + 3) >> 2) + 255) / 256;
-  if (nb > (size_t)adam_cap) nb = adam_cap;
-  hipLaunchKernelGGL(adam_tf_ema_kernel, dim3((int)nb), dim3(256), 0, stream, w, g, m, v, ema, (size_t)n,
-                     lr_t, lr_dev, b1, b2, eps, gscale, decay, decay_dev);
-  return hipGetLastError();
-}
-
-// The same update with two multipliers per arena slot (the equalized learning rate folded into Adam): slot s
-// uses gs = gscale * grad_mult_s in place of gscale and lr_s = lr_t * lr_mult_s in place of lr_t; both products are formed once per
-// slot while the table is staged in LDS, so the loop below is adam_tf_kernel's statement for statement and, given the same two fp32
-// products, writes the same bits.  Slots are 16-byte aligned: a float4 lies in one slot.  A thread's indices only grow, so its cursor
-// into the table only moves forward (binary search over the slots behind the cursor, only when the index has left the current slot).
-// The table selects multipliers and nothing else: the cursor stays in [0, n_slots - 1] whatever the table holds, and no address is
-// formed from a table value.
-template <bool EMA>
-__global__ __launch_bounds__(256) void adam_tf_slots_kernel(float* __restrict__ w, const float* __restrict__ g,
-                                                            float* __restrict__ m, float* __restrict__ v,
-                                                            float* __restrict__ ema, size_t n,
-                                                            const long long* __restrict__ slot_end,
-                                                            const float* __restrict__ slot_mult, int n_slots, float lr_val,
-                                                            const float* __restrict__ lr_dev, float b1, float b2, float eps,
-                                                            float gscale, float decay_val, const float* __restrict__ decay_dev) {
+// EMA: the shadow is read, advanced and written in the same pass.
+// SLOTS: two multipliers per arena slot (the equalized learning rate folded into Adam): slot s uses
+// gs = gscale * grad_mult_s in place of gscale and lr_s = lr_t * lr_mult_s in place of lr_t; both products are formed once per slot
+// while the table is staged in LDS (16 bytes per slot, 32 KiB at T2I_ADAM_MAX_SLOTS).  Slots are 16-byte aligned: a float4 lies in one
+// slot, and n is a multiple of 4 (the entry checked), so there is no scalar tail.  A thread's indices only grow, so its cursor into the
+// table only moves forward (binary search over the slots behind the cursor, only when the index has left the current slot).  The table
+// selects multipliers and nothing else: the cursor stays in [0, n_slots - 1] whatever the table holds, and no address is formed from a
+// table value.  Without SLOTS the table arguments are not touched and the launch takes no LDS.
+template <bool SLOTS, bool EMA>
+__global__ __launch_bounds__(256) void adam_tf_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
+                                                      float* __restrict__ v, float* __restrict__ ema, size_t n,
+                                                      const long long* __restrict__ slot_end, const float* __restrict__ slot_mult,
+                                                      int n_slots, float lr_val, const float* __restrict__ lr_dev, float b1, float b2,
+                                                      float eps, float gscale, float decay_val, const float* __restrict__ decay_dev) {
+  const float lr_t = lr_dev ? *lr_dev : lr_val;   // device scalar: a captured graph replays with a new step size
+  float omd = 0.f;
+  if constexpr (EMA) omd = 1.0f - (decay_dev ? *decay_dev : decay_val);   // ... and with a new decay
   extern __shared__ __align__(16) unsigned char slots_lds[];
   long long* s_end = reinterpret_cast<long long*>(slots_lds);                 // [n_slots]
   float2* s_mul = reinterpret_cast<float2*>(s_end + n_slots);                // [n_slots]: (gs, lr_s)
-  const float lr_t = lr_dev ? *lr_dev : lr_val;
-  float omd = 0.f;
-  if (EMA) omd = 1.0f - (decay_dev ? *decay_dev : decay_val);
-  for (int s = threadIdx.x; s < n_slots; s += blockDim.x) {
-    s_end[s] = slot_end[s];
-    s_mul[s] = make_float2(gscale * slot_mult[2 * s], lr_t * slot_mult[2 * s + 1]);
+  if constexpr (SLOTS) {
+    for (int s = threadIdx.x; s < n_slots; s += blockDim.x) {
+      s_end[s] = slot_end[s];
+      s_mul[s] = make_float2(gscale * slot_mult[2 * s], lr_t * slot_mult[2 * s + 1]);
+    }
+    __syncthreads();
   }
-  __syncthreads();
   const size_t n4 = n >> 2;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int last = n_slots - 1;
   int cur = -1;
   long long cur_end = 0;                 // the first index looks its slot up
-  float gs = 0.f, lr_s = 0.f;
+  float gs = SLOTS ? 0.f : gscale, lr = SLOTS ? 0.f : lr_t;
   for (size_t i = t; i < n4; i += stride) {
-    const long long e = (long long)(i << 2);
-    if (e >= cur_end && cur < last) {
-      int lo = cur + 1, hi = last;       // the first slot behind the cursor whose end lies above e; `last` if none does
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (e < s_end[mid]) hi = mid; else lo = mid + 1;
+    if constexpr (SLOTS) {
+      const long long e = (long long)(i << 2);
+      if (e >= cur_end && cur < last) {
+        int lo = cur + 1, hi = last;       // the first slot behind the cursor whose end lies above e; `last` if none does
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (e < s_end[mid]) hi = mid; else lo = mid + 1;
+        }
+        cur = lo;
+        cur_end = s_end[cur];
+        const float2 mu = s_mul[cur];
+        gs = mu.x; lr = mu.y;
       }
-      cur = lo;
-      cur_end = s_end[cur];
-      const float2 mu = s_mul[cur];
-      gs = mu.x; lr_s = mu.y;
     }
     float4 W = reinterpret_cast<float4*>(w)[i];
-    const float4 G0 = reinterpret_cast<const float4*>(g)[i];
+    const float4 G = reinterpret_cast<const float4*>(g)[i];
     float4 M = b1 != 0.f ? reinterpret_cast<float4*>(m)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     float4 V = reinterpret_cast<float4*>(v)[i];
     float4 E = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (EMA) E = reinterpret_cast<float4*>(ema)[i];
-    float gx = G0.x * gs, gy = G0.y * gs, gz = G0.z * gs, gw = G0.w * gs;
-    M.x = b1 * M.x + (1.f - b1) * gx; M.y = b1 * M.y + (1.f - b1) * gy;
-    M.z = b1 * M.z + (1.f - b1) * gz; M.w = b1 * M.w + (1.f - b1) * gw;
-    V.x = b2 * V.x + (1.f - b2) * gx * gx; V.y = b2 * V.y + (1.f - b2) * gy * gy;
-    V.z = b2 * V.z + (1.f - b2) * gz * gz; V.w = b2 * V.w + (1.f - b2) * gw * gw;
-    W.x -= lr_s * M.x / (sqrtf(V.x) + eps); W.y -= lr_s * M.y / (sqrtf(V.y) + eps);
-    W.z -= lr_s * M.z / (sqrtf(V.z) + eps); W.w -= lr_s * M.w / (sqrtf(V.w) + eps);
-    if (EMA) {
+    if constexpr (EMA) E = reinterpret_cast<float4*>(ema)[i];
+    adam_step(W.x, G.x, M.x, V.x, gs, lr, b1, b2, eps); adam_step(W.y, G.y, M.y, V.y, gs, lr, b1, b2, eps);
+    adam_step(W.z, G.z, M.z, V.z, gs, lr, b1, b2, eps); adam_step(W.w, G.w, M.w, V.w, gs, lr, b1, b2, eps);
+    if constexpr (EMA) {
       E.x = ema_step(E.x, W.x, omd); E.y = ema_step(E.y, W.y, omd);
       E.z = ema_step(E.z, W.z, omd); E.w = ema_step(E.w, W.w, omd);
     }
     reinterpret_cast<float4*>(w)[i] = W;
     if (m) reinterpret_cast<float4*>(m)[i] = M;
     reinterpret_cast<float4*>(v)[i] = V;
-    if (EMA) reinterpret_cast<float4*>(ema)[i] = E;
+    if constexpr (EMA) reinterpret_cast<float4*>(ema)[i] = E;
+  }
+  if constexpr (!SLOTS) {
+    for (size_t i = (n4 << 2) + t; i < n; i += stride) {
+      const float gg = g[i];       // g, m, v, w: the order of these loads decides which product of v's update the backend fuses
+      float mm = b1 != 0.f ? m[i] : 0.f, vv = v[i], ww = w[i];
+      adam_step(ww, gg, mm, vv, gs, lr, b1, b2, eps);
+      if (m) m[i] = mm;
+      v[i] = vv;
+      w[i] = ww;
+      if constexpr (EMA) ema[i] = ema_step(ema[i], ww, omd);
+    }
   }
 }
 
-// n is a multiple of 4 and 1 <= n_slots <= T2I_ADAM_MAX_SLOTS (the caller checked): 16 bytes of LDS per slot, 32 KiB at the cap
-hipError_t adam_tf_slots_launch(float* w, const float* g, float* m, float* v, float* ema, int64_t n, const int64_t* slot_end,
-                                const float* slot_mult, int n_slots, float lr_t, const float* lr_dev, float b1, float b2, float eps,
-                                float gscale, float decay, const float* decay_dev, hipStream_t stream) {
+// slot_end == NULL: no slot table (n_slots is then 0); ema == NULL: no shadow.  With a table, n is a multiple of 4 and
+// 1 <= n_slots <= T2I_ADAM_MAX_SLOTS (the caller checked).
+hipError_t adam_tf_launch(float* w, const float* g, float* m, float* v, float* ema, int64_t n, const int64_t* slot_end,
+                          const float* slot_mult, int n_slots, float lr_t, const float* lr_dev, float b1, float b2, float eps,
+                          float gscale, float decay, const float* decay_dev, hipStream_t stream) {
   const int adam_cap = tuning().adam_blocks;
   size_t nb = ((((size_t)n + 3) >> 2) + 255) / 256;
   if (nb > (size_t)adam_cap) nb = adam_cap;
-  const size_t lds = (size_t)n_slots * (sizeof(long long) + sizeof(float2));
-  const long long* ends = reinterpret_cast<const long long*>(slot_end);
-  if (ema)
-    hipLaunchKernelGGL(adam_tf_slots_kernel<true>, dim3((int)nb), dim3(256), lds, stream, w, g, m, v, ema, (size_t)n, ends, slot_mult,
-                       n_slots, lr_t, lr_dev, b1, b2, eps, gscale, decay, decay_dev);
-  else
-    hipLaunchKernelGGL(adam_tf_slots_kernel<false>, dim3((int)nb), dim3(256), lds, stream, w, g, m, v, ema, (size_t)n, ends, slot_mult,
-                       n_slots, lr_t, lr_dev, b1, b2, eps, gscale, decay, decay_dev);
+  const size_t lds = slot_end ? (size_t)n_slots * (sizeof(long long) + sizeof(float2)) : 0;
+  auto kernel = slot_end ? (ema ? adam_tf_kernel<true, true> : adam_tf_kernel<true, false>)
+                         : (ema ? adam_tf_kernel<false, true> : adam_tf_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3((int)nb), dim3(256), lds, stream, w, g, m, v, ema, (size_t)n,
+                     reinterpret_cast<const long long*>(slot_end), slot_mult, n_slots, lr_t, lr_dev, b1, b2, eps, gscale, decay, decay_dev);
   return hipGetLastError();
 }
 

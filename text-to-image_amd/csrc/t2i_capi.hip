@@ -116,12 +116,8 @@ hipError_t ca_kl_fwd_launch(const float*, const float*, const float*, int, float
 hipError_t ca_kl_bwd_launch(const float*, const float*, const float*, const float*, const float*, int, float*, float*, hipStream_t);
 hipError_t lerp_dev_launch(const float*, const float*, const float*, int, size_t, float*, hipStream_t);
 hipError_t col_reduce_partials_launch(const float*, const float*, int, int, float*, float*, int, hipStream_t);
-hipError_t adam_tf_launch(float*, const float*, float*, float*, int64_t, float, const float*, float, float, float, float,
-                          hipStream_t);
-hipError_t adam_tf_ema_launch(float*, const float*, float*, float*, float*, int64_t, float, const float*, float, float, float, float,
-                              float, const float*, hipStream_t);
-hipError_t adam_tf_slots_launch(float*, const float*, float*, float*, float*, int64_t, const int64_t*, const float*, int, float,
-                                const float*, float, float, float, float, float, const float*, hipStream_t);
+hipError_t adam_tf_launch(float*, const float*, float*, float*, float*, int64_t, const int64_t*, const float*, int, float,
+                          const float*, float, float, float, float, float, const float*, hipStream_t);
 hipError_t kt_sgd_launch(float*, const float*, float, float, hipStream_t);
 hipError_t zero_ranges_launch(float*, const long long*, int, hipStream_t);
 hipError_t trunc_normal_launch(float*, size_t, unsigned long long, unsigned long long, float, float, float, float, hipStream_t);
@@ -1830,82 +1826,89 @@ int t2i_lerp_dev(const float* a, const float* b, const float* t_dev, int32_t mod
   return check(lerp_dev_launch(a, b, t_dev, mode, (size_t)n, out, (hipStream_t)stream), "t2i_lerp_dev");
 }
 
-int t2i_adam_tf(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, const float* lr_t_dev, float beta1,
-                float beta2, float eps,
-                float grad_scale, t2i_stream_t stream) {
-  if (!w || !g || !v || n <= 0) { set_error("t2i_adam_tf: bad argument"); return T2I_ERR_INVALID; }
-  if (!m && beta1 != 0.f) { set_error("t2i_adam_tf: m may be NULL only with beta1 == 0 (the first moment is then grad * grad_scale)"); return T2I_ERR_INVALID; }
-  if (!(aligned16(w) && aligned16(g) && (!m || aligned16(m)) && aligned16(v))) { set_error("t2i_adam_tf: arena must be 16-byte aligned"); return T2I_ERR_INVALID; }
-  filter_cache_invalidate(w, (size_t)n * 4);          // transformed filters of this arena are stale from here on
-  const int rc = check(adam_tf_launch(w, g, m, v, n, lr_t, lr_t_dev, beta1, beta2, eps, grad_scale, (hipStream_t)stream), "t2i_adam_tf");
+// What the three Adam entries refuse alike, each check written once.  An entry asks for the checks in groups, with those only it makes (a
+// required shadow, the slot tables) in between, so the order of its refusals is its own; every message starts with the entry's name.
+enum { ADAM_ARENA = 1, ADAM_MOMENT = 2, ADAM_ALIGNED = 4, ADAM_APART = 8, ADAM_DECAY = 16 };
+struct AdamArgs {
+  const char *name, *moment, *aligned;   // the entry; m_t when m is NULL; what has to be 16-byte aligned
+  float* w; const float* g; float *m, *v, *ema;   // ema == NULL: no shadow
+  int64_t n;
+  float beta1, ema_decay;
+  const float* ema_decay_dev;
+};
+
+static bool ranges_overlap(const void* a, uintptr_t na, const void* b, uintptr_t nb) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a && b && a0 < b0 + nb && b0 < a0 + na;
+}
+
+static bool adam_args_ok(const AdamArgs& a, int checks) {
+  if ((checks & ADAM_ARENA) && (!a.w || !a.g || !a.v || a.n <= 0)) { set_error("%s: bad argument", a.name); return false; }
+  if ((checks & ADAM_MOMENT) && !a.m && a.beta1 != 0.f) {
+    set_error("%s: m may be NULL only with beta1 == 0 (the first moment is then %s)", a.name, a.moment);
+    return false;
+  }
+  if ((checks & ADAM_ALIGNED) && !(aligned16(a.w) && aligned16(a.g) && aligned16(a.m) && aligned16(a.v) && aligned16(a.ema))) {   // (NULL is aligned)
+    set_error("%s: %s must be 16-byte aligned", a.name, a.aligned);
+    return false;
+  }
+  if (checks & ADAM_APART)
+    for (const float* o : {(const float*)a.w, a.g, (const float*)a.m, (const float*)a.v})
+      if (ranges_overlap(a.ema, (uintptr_t)a.n * 4, o, (uintptr_t)a.n * 4)) { set_error("%s: ema overlaps w, g, m or v", a.name); return false; }
+  if ((checks & ADAM_DECAY) && a.ema && !a.ema_decay_dev && !(a.ema_decay >= 0.f && a.ema_decay <= 1.f)) {
+    set_error("%s: ema_decay %g is outside [0, 1]", a.name, (double)a.ema_decay);
+    return false;
+  }
+  return true;
+}
+
+// the launch behind every accepted call (slot_end == NULL: no table)
+static int adam_update(const AdamArgs& a, const int64_t* slot_end, const float* slot_mult, int n_slots, float lr_t, const float* lr_t_dev,
+                       float beta2, float eps, float grad_scale, t2i_stream_t stream) {
+  filter_cache_invalidate(a.w, (size_t)a.n * 4);          // transformed filters of this arena are stale from here on
+  const int rc = check(adam_tf_launch(a.w, a.g, a.m, a.v, a.ema, a.n, slot_end, slot_mult, n_slots, lr_t, lr_t_dev, a.beta1, beta2, eps,
+                                      grad_scale, a.ema_decay, a.ema_decay_dev, (hipStream_t)stream), a.name);
   if (rc != T2I_OK || !tuning().cache_refresh) return rc;
-  return filter_cache_refresh(w, (size_t)n * 4, (hipStream_t)stream);   // ... and regenerated behind the update, all in one launch
+  return filter_cache_refresh(a.w, (size_t)a.n * 4, (hipStream_t)stream);   // ... and regenerated behind the update, all in one launch
+}
+
+int t2i_adam_tf(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, const float* lr_t_dev, float beta1,
+                float beta2, float eps, float grad_scale, t2i_stream_t stream) {
+  const AdamArgs a{"t2i_adam_tf", "grad * grad_scale", "arena", w, g, m, v, nullptr, n, beta1, 0.f, nullptr};
+  if (!adam_args_ok(a, ADAM_ARENA | ADAM_MOMENT | ADAM_ALIGNED)) return T2I_ERR_INVALID;
+  return adam_update(a, nullptr, nullptr, 0, lr_t, lr_t_dev, beta2, eps, grad_scale, stream);
 }
 
 int t2i_adam_tf_ema(float* w, const float* g, float* m, float* v, float* ema, int64_t n, float lr_t, const float* lr_t_dev,
                     float beta1, float beta2, float eps, float grad_scale, float ema_decay, const float* ema_decay_dev,
                     t2i_stream_t stream) {
-  if (!w || !g || !v || n <= 0) { set_error("t2i_adam_tf_ema: bad argument"); return T2I_ERR_INVALID; }
+  const AdamArgs a{"t2i_adam_tf_ema", "grad * grad_scale", "arena and shadow", w, g, m, v, ema, n, beta1, ema_decay, ema_decay_dev};
+  if (!adam_args_ok(a, ADAM_ARENA)) return T2I_ERR_INVALID;
   if (!ema) { set_error("t2i_adam_tf_ema: ema is NULL (t2i_adam_tf is the update without a shadow)"); return T2I_ERR_INVALID; }
-  if (!m && beta1 != 0.f) { set_error("t2i_adam_tf_ema: m may be NULL only with beta1 == 0 (the first moment is then grad * grad_scale)"); return T2I_ERR_INVALID; }
-  if (!(aligned16(w) && aligned16(g) && (!m || aligned16(m)) && aligned16(v) && aligned16(ema))) {
-    set_error("t2i_adam_tf_ema: arena and shadow must be 16-byte aligned");
-    return T2I_ERR_INVALID;
-  }
-  const uintptr_t e0 = reinterpret_cast<uintptr_t>(ema), bytes = (uintptr_t)n * 4;
-  const void* others[4] = {w, g, m, v};
-  for (const void* o : others) {
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(o);
-    if (o && e0 < o0 + bytes && o0 < e0 + bytes) { set_error("t2i_adam_tf_ema: ema overlaps w, g, m or v"); return T2I_ERR_INVALID; }
-  }
-  if (!ema_decay_dev && !(ema_decay >= 0.f && ema_decay <= 1.f)) {
-    set_error("t2i_adam_tf_ema: ema_decay %g is outside [0, 1]", (double)ema_decay);
-    return T2I_ERR_INVALID;
-  }
-  filter_cache_invalidate(w, (size_t)n * 4);          // as t2i_adam_tf: transformed filters of this arena are stale from here on
-  const int rc = check(adam_tf_ema_launch(w, g, m, v, ema, n, lr_t, lr_t_dev, beta1, beta2, eps, grad_scale, ema_decay, ema_decay_dev,
-                                          (hipStream_t)stream), "t2i_adam_tf_ema");
-  if (rc != T2I_OK || !tuning().cache_refresh) return rc;
-  return filter_cache_refresh(w, (size_t)n * 4, (hipStream_t)stream);
+  if (!adam_args_ok(a, ADAM_MOMENT | ADAM_ALIGNED | ADAM_APART | ADAM_DECAY)) return T2I_ERR_INVALID;
+  return adam_update(a, nullptr, nullptr, 0, lr_t, lr_t_dev, beta2, eps, grad_scale, stream);
 }
 
 int t2i_adam_tf_slots(float* w, const float* g, float* m, float* v, float* ema, int64_t n, const int64_t* slot_end_dev,
                       const float* slot_mult_dev, int32_t n_slots, float lr_t, const float* lr_t_dev, float beta1, float beta2,
                       float eps, float grad_scale, float ema_decay, const float* ema_decay_dev, t2i_stream_t stream) {
+  const AdamArgs a{"t2i_adam_tf_slots", "grad * grad_scale * grad_mult", "arena and shadow", w, g, m, v, ema, n, beta1, ema_decay, ema_decay_dev};
   if (!w || !g || !v || !slot_end_dev || !slot_mult_dev) { set_error("t2i_adam_tf_slots: bad argument (w, g, v or a slot table is NULL)"); return T2I_ERR_INVALID; }
   if (n <= 0 || (n & 3)) { set_error("t2i_adam_tf_slots: n = %lld must be a positive multiple of 4", (long long)n); return T2I_ERR_INVALID; }
   if (n_slots < 1 || n_slots > T2I_ADAM_MAX_SLOTS) {
     set_error("t2i_adam_tf_slots: n_slots = %d is outside [1, %d]", (int)n_slots, (int)T2I_ADAM_MAX_SLOTS);
     return T2I_ERR_INVALID;
   }
-  if (!m && beta1 != 0.f) { set_error("t2i_adam_tf_slots: m may be NULL only with beta1 == 0 (the first moment is then grad * grad_scale * grad_mult)"); return T2I_ERR_INVALID; }
-  if (!(aligned16(w) && aligned16(g) && (!m || aligned16(m)) && aligned16(v) && (!ema || aligned16(ema)))) {
-    set_error("t2i_adam_tf_slots: arena and shadow must be 16-byte aligned");
-    return T2I_ERR_INVALID;
-  }
+  if (!adam_args_ok(a, ADAM_MOMENT | ADAM_ALIGNED)) return T2I_ERR_INVALID;
   if (reinterpret_cast<uintptr_t>(slot_end_dev) & 7) { set_error("t2i_adam_tf_slots: slot_end_dev must be 8-byte aligned"); return T2I_ERR_INVALID; }
-  const uintptr_t bytes = (uintptr_t)n * 4;
-  const void* arenas[5] = {w, g, m, v, ema};
-  auto overlaps = [](const void* a, uintptr_t na, const void* b, uintptr_t nb) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a && b && a0 < b0 + nb && b0 < a0 + na;
-  };
-  for (int i = 0; i < 4; ++i)
-    if (overlaps(ema, bytes, arenas[i], bytes)) { set_error("t2i_adam_tf_slots: ema overlaps w, g, m or v"); return T2I_ERR_INVALID; }
-  for (const void* a : arenas)
-    if (overlaps(slot_end_dev, (uintptr_t)n_slots * 8, a, bytes) || overlaps(slot_mult_dev, (uintptr_t)n_slots * 8, a, bytes)) {
+  if (!adam_args_ok(a, ADAM_APART)) return T2I_ERR_INVALID;
+  for (const float* o : {(const float*)w, g, (const float*)m, (const float*)v, (const float*)ema})
+    if (ranges_overlap(slot_end_dev, (uintptr_t)n_slots * 8, o, (uintptr_t)n * 4) || ranges_overlap(slot_mult_dev, (uintptr_t)n_slots * 8, o, (uintptr_t)n * 4)) {
       set_error("t2i_adam_tf_slots: a slot table overlaps an arena");
       return T2I_ERR_INVALID;
     }
-  if (ema && !ema_decay_dev && !(ema_decay >= 0.f && ema_decay <= 1.f)) {
-    set_error("t2i_adam_tf_slots: ema_decay %g is outside [0, 1]", (double)ema_decay);
-    return T2I_ERR_INVALID;
-  }
-  filter_cache_invalidate(w, (size_t)n * 4);          // as t2i_adam_tf: transformed filters of this arena are stale from here on
-  const int rc = check(adam_tf_slots_launch(w, g, m, v, ema, n, slot_end_dev, slot_mult_dev, (int)n_slots, lr_t, lr_t_dev, beta1, beta2,
-                                            eps, grad_scale, ema_decay, ema_decay_dev, (hipStream_t)stream), "t2i_adam_tf_slots");
-  if (rc != T2I_OK || !tuning().cache_refresh) return rc;
-  return filter_cache_refresh(w, (size_t)n * 4, (hipStream_t)stream);
+  if (!adam_args_ok(a, ADAM_DECAY)) return T2I_ERR_INVALID;
+  return adam_update(a, slot_end_dev, slot_mult_dev, (int)n_slots, lr_t, lr_t_dev, beta2, eps, grad_scale, stream);
 }
 
 long long t2i_stat(const char* key) {

@@ -1076,12 +1076,19 @@ def row_scale_div(g, num, den):
     return out
 
 
-def adam_tf(w, g, m, v, lr_t, beta1, beta2, eps=1e-8, grad_scale=1.0, lr_t_dev=None):
-    """In place on flat arenas.  lr_t_dev: optional device scalar that overrides lr_t (graph replay)."""
+def _adam_chk(w, g, m, v, beta1, ema=None):
+    """What the three Adam wrappers check of their arenas (m and ema may be None)."""
     for t in (w, g, v) + ((m,) if m is not None else ()):
         _chk(t)
-    assert w.numel() == g.numel() == v.numel() and (m is None or m.numel() == w.numel())
+    if ema is not None:
+        _chk(ema, 'ema', f32=True)
+    assert w.numel() == g.numel() == v.numel() and (m is None or m.numel() == w.numel()) and (ema is None or ema.numel() == w.numel())
     assert m is not None or beta1 == 0.0, 'the first moment can be skipped only with beta1 == 0'
+
+
+def adam_tf(w, g, m, v, lr_t, beta1, beta2, eps=1e-8, grad_scale=1.0, lr_t_dev=None):
+    """In place on flat arenas.  lr_t_dev: optional device scalar that overrides lr_t (graph replay)."""
+    _adam_chk(w, g, m, v, beta1)
     if _live(w):
         check(lib.t2i_adam_tf(_ptr(w), _ptr(g), _ptr(m), _ptr(v), w.numel(), lr_t, _ptr(lr_t_dev), beta1, beta2, eps, grad_scale,
                               _stream()),
@@ -1091,11 +1098,8 @@ def adam_tf(w, g, m, v, lr_t, beta1, beta2, eps=1e-8, grad_scale=1.0, lr_t_dev=N
 def adam_tf_ema(w, g, m, v, ema, lr_t, beta1, beta2, eps=1e-8, grad_scale=1.0, ema_decay=0.999, lr_t_dev=None, ema_decay_dev=None):
     """adam_tf plus the exponential moving average of the updated weights in the same launch: ema -= (1 - decay) * (ema - w_new).
     ema_decay_dev: optional device scalar that overrides ema_decay (graph replay)."""
-    for t in (w, g, v) + ((m,) if m is not None else ()):
-        _chk(t)
-    _chk(ema, 'ema', f32=True)
-    assert w.numel() == g.numel() == v.numel() == ema.numel() and (m is None or m.numel() == w.numel())
-    assert m is not None or beta1 == 0.0, 'the first moment can be skipped only with beta1 == 0'
+    _chk(ema, 'ema', f32=True)          # required here: None is an error
+    _adam_chk(w, g, m, v, beta1, ema)
     if _live(w):
         check(lib.t2i_adam_tf_ema(_ptr(w), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), w.numel(), lr_t, _ptr(lr_t_dev), beta1, beta2, eps,
                                   grad_scale, ema_decay, _ptr(ema_decay_dev), _stream()),
@@ -1110,17 +1114,12 @@ def adam_tf_slots(w, g, m, v, slot_end, slot_mult, lr_t, beta1, beta2, eps=1e-8,
     """adam_tf (ema=None) / adam_tf_ema with two multipliers per arena slot: slot s, ending at element slot_end[s] (device int64
     [n_slots], ascending multiples of 4, the last == w.numel()), steps with grad_scale * slot_mult[s, 0] and lr_t * slot_mult[s, 1]
     (device float32 [n_slots, 2]).  All ones: the bits of adam_tf / adam_tf_ema."""
-    for t in (w, g, v) + ((m,) if m is not None else ()):
-        _chk(t)
-    if ema is not None:
-        _chk(ema, 'ema', f32=True)
+    _adam_chk(w, g, m, v, beta1, ema)
     _chk(slot_mult, 'slot_mult', f32=True)
     if slot_end.dtype != torch.int64:
         raise TypeError('slot_end must be int64, got %s' % slot_end.dtype)
     if not slot_end.is_contiguous():
         raise ValueError('slot_end must be contiguous (shape %s, strides %s)' % (tuple(slot_end.shape), slot_end.stride()))
-    assert w.numel() == g.numel() == v.numel() and (m is None or m.numel() == w.numel()) and (ema is None or ema.numel() == w.numel())
-    assert m is not None or beta1 == 0.0, 'the first moment can be skipped only with beta1 == 0'
     assert slot_end.dim() == 1 and slot_mult.numel() == 2 * slot_end.numel() and slot_end.device == w.device == slot_mult.device
     if _live(w):
         check(lib.t2i_adam_tf_slots(_ptr(w), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), w.numel(), _ptr(slot_end), _ptr(slot_mult),

@@ -256,16 +256,13 @@ class AdamTF(object):
         with a refresh of everything — pass True where the same capture goes on to use these filters (the critic's update in
         a one-graph iteration)."""
         self.arena.finish_step()
+        kw = dict(lr_t=0.0, beta1=self.beta1, beta2=self.beta2, eps=self.eps, grad_scale=grad_scale, lr_t_dev=self.lr_t_dev)
+        if self.ema is not None:
+            kw.update(ema=self.ema, ema_decay=self.ema_decay, ema_decay_dev=self.ema_decay_dev)
         if self.slot_end is not None:
-            K.adam_tf_slots(self.arena.flat, self.arena.grad, None if self.skip_m else self._m, self.v, self.slot_end, self.slot_mult, 0.0,
-                            self.beta1, self.beta2, self.eps, grad_scale, ema=self.ema, ema_decay=0.0 if self.ema is None else self.ema_decay,
-                            lr_t_dev=self.lr_t_dev, ema_decay_dev=None if self.ema is None else self.ema_decay_dev)
-        elif self.ema is None:
-            K.adam_tf(self.arena.flat, self.arena.grad, None if self.skip_m else self._m, self.v, 0.0, self.beta1, self.beta2, self.eps, grad_scale,
-                      lr_t_dev=self.lr_t_dev)
-        else:
-            K.adam_tf_ema(self.arena.flat, self.arena.grad, None if self.skip_m else self._m, self.v, self.ema, 0.0, self.beta1, self.beta2,
-                          self.eps, grad_scale, self.ema_decay, lr_t_dev=self.lr_t_dev, ema_decay_dev=self.ema_decay_dev)
+            kw.update(slot_end=self.slot_end, slot_mult=self.slot_mult)
+        launch = K.adam_tf_slots if self.slot_end is not None else K.adam_tf if self.ema is None else K.adam_tf_ema
+        launch(self.arena.flat, self.arena.grad, None if self.skip_m else self._m, self.v, **kw)
         if self.skip_m:
             self._last_scale = float(grad_scale)
             self._m_stale = True             # (an eager zero_grad between prepare() and here has formed the PREVIOUS step's moment)
