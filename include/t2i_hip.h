@@ -810,6 +810,33 @@ size_t t2i_ball_counts_workspace_bytes(int64_t M, int64_t N, int32_t D, int32_t 
 int t2i_ball_counts(const float* Q, int64_t M, const float* R, int64_t N, int32_t D, const double* r2, int32_t segments, int32_t* count,
                     double* dmin, void* workspace, size_t workspace_bytes, t2i_stream_t stream);
 
+/* ---- differentiable augmentation (Zhao et al., "Differentiable Augmentation for Data-Efficient GAN Training", NeurIPS 2020; the
+ * reference has no such layer).  Added within ABI v13: no existing argument list changed. ------------------------------------------- */
+/* x [B,H,W,C] fp32 and one row of params [B,9] fp32 = (b, s, c, ty, tx, y0, y1, x0, x1) per sample, the six geometric entries
+ * integer-valued floats (the kernels clamp them to the image's extents before any index is formed, so no table can move an address out
+ * of the tensors), the rectangle clipped to the image, y0 == y1 = no cutout.  With m_pix = the mean over a pixel's channels and M = the mean
+ * over the sample:
+ *   colour       u1 = u + b (only with offset != 0);  u2 = s u1 + (1 - s) m_pix(u1);  u3 = c u2 + (1 - c) M(u2),  M(u2) = M(u) + b
+ *   translation  u4[y, x, :] = u3[y - ty, x - tx, :] inside the image, else 0
+ *   cutout       u5[y, x, :] = 0 for y0 <= y < y1 and x0 <= x < x1, else u4[y, x, :]
+ * policy: a non-empty mask of T2I_DIFFAUG_*; the columns of a policy outside the mask are not read (identity).  Both blends are
+ * evaluated as k a + (1 - k) mean: s = 1 and c = 1 return the input bit for bit.  _adj is the adjoint of the linear part: g masked by
+ * the rectangle, gathered at [y + ty, x + tx] (0 outside the image), then c g3 + (1 - c) M(g3) and s g2 + (1 - s) m_pix(g2).  The
+ * backward of _adj is _fwd with offset = 0, so the pair is closed under differentiation of any order.
+ * With T2I_DIFFAUG_COLOR each entry is two launches: per-sample partial sums (of x, or of the masked, shifted cotangent) into the
+ * workspace in a fixed order, one partial per 4096 floats of a sample, then the apply kernel, which adds a sample's partials itself
+ * in a fixed order; without it one launch and no workspace (the query returns 0; it also returns 0 for a refused shape).  No
+ * atomics; a sample's work is cut by H, W and C alone, so its result is the same bits in whatever batch it sits and calls repeat bit
+ * for bit.  Any C >= 1 (a thread keeps a pixel in registers for C = 3 and 4).  1 <= B <= 65535, 1 <= H, W <= 32768; anything else, a
+ * NULL or misaligned (4 bytes) pointer, an unknown policy bit, an output overlapping its input or a workspace that is NULL or
+ * smaller than the query returns T2I_ERR_INVALID before anything is launched. */
+enum { T2I_DIFFAUG_COLOR = 1, T2I_DIFFAUG_TRANSLATION = 2, T2I_DIFFAUG_CUTOUT = 4 };
+size_t t2i_diff_augment_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C, int32_t policy);
+int t2i_diff_augment_fwd(const float* x, const float* params, int32_t B, int32_t H, int32_t W, int32_t C, int32_t policy, int32_t offset,
+                         float* y, void* ws, size_t ws_bytes, t2i_stream_t stream);
+int t2i_diff_augment_adj(const float* g, const float* params, int32_t B, int32_t H, int32_t W, int32_t C, int32_t policy, float* dx,
+                         void* ws, size_t ws_bytes, t2i_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -864,6 +864,44 @@ class ResizeNearestAdjFn(Function):
         return ResizeNearestFn.apply(gg, ctx.out_hw[0], ctx.out_hw[1]), None, None
 
 
+class DiffAugmentFn(Function):
+    """y = T(x): the differentiable augmentation of DESIGN.md section 4.35 (colour / translation / cutout, one row of the device table P
+    [B,9] per sample).  Affine in x; its backward is DiffAugmentAdjFn, whose backward is this Function again without the brightness
+    offset: closed under differentiation of any order (usable in front of a critic under the gradient penalty).  P carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, P, policy, offset):
+        ctx.save_for_backward(P)
+        ctx.policy = policy
+        ctx.set_materialize_grads(False)
+        return K.diff_augment_fwd(_c(x), P, policy, offset)
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None
+        P, = ctx.saved_tensors
+        return DiffAugmentAdjFn.apply(g, P, ctx.policy), None, None, None
+
+
+class DiffAugmentAdjFn(Function):
+    """dx = A^T g, the adjoint of the linear part A of DiffAugmentFn; backward: A itself (DiffAugmentFn with offset=False)."""
+
+    @staticmethod
+    def forward(ctx, g, P, policy):
+        ctx.save_for_backward(P)
+        ctx.policy = policy
+        ctx.set_materialize_grads(False)
+        return K.diff_augment_adj(_c(g), P, policy)
+
+    @staticmethod
+    def backward(ctx, gg):
+        if gg is None:
+            return None, None, None
+        P, = ctx.saved_tensors
+        return DiffAugmentFn.apply(gg, P, ctx.policy, False), None, None
+
+
 class PoolAvgFn(Function):
     """tf.nn.pool AVG, window = stride = s, SAME, any extents (the mean of the taps inside the image).  Linear; adjoint: PoolAvgAdjFn."""
 

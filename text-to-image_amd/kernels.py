@@ -1863,6 +1863,45 @@ def minibatch_stddev_bwd2(v, x, gs, G, F, eps=1e-8):
     return dxx, dgs
 
 
+DIFFAUG_COLOR, DIFFAUG_TRANSLATION, DIFFAUG_CUTOUT = 1, 2, 4            # T2I_DIFFAUG_*: the policy mask of diff_augment_fwd / _adj
+
+
+def _diffaug_args(x, P, policy):
+    _chk(x, 'x', f32=True); _chk(P, 'params', f32=True)
+    if x.dim() != 4 or tuple(P.shape) != (x.shape[0], 9) or P.device != x.device:
+        raise ValueError('diff_augment: x must be [B,H,W,C] and params [B,9] on the same device, got %s on %s and %s on %s' % (
+            tuple(x.shape), x.device, tuple(P.shape), P.device))
+    policy = int(policy)
+    if policy <= 0 or policy & ~(DIFFAUG_COLOR | DIFFAUG_TRANSLATION | DIFFAUG_CUTOUT):
+        raise ValueError('diff_augment: policy must be a non-empty mask of DIFFAUG_COLOR | DIFFAUG_TRANSLATION | DIFFAUG_CUTOUT, got %d' % policy)
+    return tuple(x.shape) + (policy,)
+
+
+def diff_augment_fwd(x, P, policy, offset=True):
+    """y = T(x) for x [B,H,W,C] and the table P [B,9] = (b, s, c, ty, tx, y0, y1, x0, x1) per sample (include/t2i_hip.h): colour,
+    integer translation with zero padding, rectangular cutout, as the bits of `policy` select.  offset=False leaves the brightness
+    offset b out: the linear part A of T, which is the backward of diff_augment_adj.  Two launches with DIFFAUG_COLOR (per-sample
+    partial sums, then the apply kernel), else one."""
+    B, H, W, C, policy = _diffaug_args(x, P, policy)
+    y = torch.empty_like(x)
+    if _live(x) and x.numel() > 0:
+        wsp, wsn = _ws_args(x, int(lib.t2i_diff_augment_workspace_bytes(B, H, W, C, policy)))
+        check(lib.t2i_diff_augment_fwd(_ptr(x), _ptr(P), B, H, W, C, policy, 1 if offset else 0, _ptr(y), wsp, wsn, _stream()),
+              't2i_diff_augment_fwd')
+    return y
+
+
+def diff_augment_adj(g, P, policy):
+    """dx = A^T g, the adjoint of the linear part of diff_augment_fwd: the cutout mask, the opposite shift, then the two (self-adjoint)
+    colour blends in reverse order.  Two launches with DIFFAUG_COLOR, else one."""
+    B, H, W, C, policy = _diffaug_args(g, P, policy)
+    dx = torch.empty_like(g)
+    if _live(g) and g.numel() > 0:
+        wsp, wsn = _ws_args(g, int(lib.t2i_diff_augment_workspace_bytes(B, H, W, C, policy)))
+        check(lib.t2i_diff_augment_adj(_ptr(g), _ptr(P), B, H, W, C, policy, _ptr(dx), wsp, wsn, _stream()), 't2i_diff_augment_adj')
+    return dx
+
+
 def resize_nearest(x, Ho, Wo):
     """x [B,H,W,C] -> [B,Ho,Wo,C], tf.image.resize_nearest_neighbor (align_corners=False)."""
     _chk(x, 'x', f32=True)

@@ -15,7 +15,11 @@ the generator's Adam launch, that checkpoints carry and `ema_weights()` / `--ema
 not truncated, and gives both optimizers the per-slot multipliers (c, c) for it: Adam on w-hat ~ N(0, 1) used as c * w-hat, restated on
 w = c * w-hat itself, so the convolutions, the checkpoints and the readers see plain weights.  The gain is sqrt(2)
 for every layer: the paper's gain 1 on the last linear layers (to_rgb's 1x1, the critic's last dense) is deliberately left out.  Biases and
-the layer-norm gamma / beta keep the multiplier 1.  `adam_lr=L` sets Adam's step size (default None: the reference's 2e-6).  Reference specifics kept: penalty
+the layer-norm gamma / beta keep the multiplier 1.  `diffaug='color,translation,cutout'` (or any subset; default None) sends every image
+the critic sees, real or generated, through the differentiable augmentation T of Zhao et al. (utils.ops.diff_augment, DESIGN.md section
+4.35): the generator is trained through T, both gradient penalties are gradients of D o T, and the sampler, checkpoints, evaluators and
+summaries never see it; the parameter tables are `feed['aug_d']` [4B, 9] (rows G | x | x_mismatch | x_hat) and `feed['aug_g']` [B, 9],
+drawn when missing.  `adam_lr=L` sets Adam's step size (default None: the reference's 2e-6).  Reference specifics kept: penalty
 coefficient 200, no kt term, G = -D_fake + 5 KL, Adam(2e-6, beta1=0, beta2=0.99) hard-coded (pggan.py:104-110; the
 `learning_rate` placeholder is fed but unused), eps of x_hat drawn in-graph (pggan.py:68 overrides the placeholder),
 `to_rgb` = k2 s1 SAME 9-channel relu conv + 1x1, every kernel He-initialised by utils/ops.py's defaults.
@@ -35,13 +39,22 @@ from ... import autograd as A
 from ... import kernels as K
 from ... import optim
 from ... import scope as S
-from ...utils.ops import concat_tile, conv2d, fc, layer_norm, lerp, lrelu_act, minibatch_stddev_stat, pixel_norm, pool, relu, upscale
+from ...utils.ops import (concat_tile, conv2d, diff_augment, diff_augment_params, diff_augment_policy, fc, layer_norm, lerp, lrelu_act,
+                          minibatch_stddev_stat, pixel_norm, pool, relu, upscale)
 
 
 class PGGAN(object):
     def __init__(self, batch_size, steps, check_dir_write, check_dir_read, dataset, sample_path, log_dir, stage, trans,
                  build_model=True, device=None, seed=0, store=None, fmap_base=1024, fmap_max=512, z_dim=128, embed_dim=1024,
-                 compr_embed_dim=128, dp=None, critic_norm=None, critic_mbstd=None, g_ema=None, equalized_lr=False, adam_lr=None):
+                 compr_embed_dim=128, dp=None, critic_norm=None, critic_mbstd=None, g_ema=None, equalized_lr=False, adam_lr=None,
+                 diffaug=None):
+        if diffaug is not None:
+            try:
+                diff_augment_policy(diffaug, 'diffaug')
+            except ValueError:
+                raise ValueError("diffaug must be None or a comma-separated, non-empty subset of 'color,translation,cutout' (the "
+                                 "differentiable augmentation in front of the critic), got %r" % (diffaug,))
+        self.diffaug = diffaug
         if adam_lr is not None and (isinstance(adam_lr, bool) or not isinstance(adam_lr, (int, float)) or not (math.isfinite(adam_lr) and adam_lr > 0.0)):
             raise ValueError("adam_lr must be None (the reference's 2e-6) or a finite step size > 0, got %r" % (adam_lr,))
         self.adam_lr = 0.000002 if adam_lr is None else float(adam_lr)
@@ -153,6 +166,14 @@ class PGGAN(object):
             n = K.trunc_normal_(torch.empty_like(like))
         return n
 
+    def _aug_table(self, feed, key, rows, like):
+        """The fed parameter table of the differentiable augmentation ([rows, 9], utils.ops.diff_augment), or a fresh draw (under data
+        parallelism each rank draws its own)."""
+        P = feed.get(key)
+        if P is None:
+            P = diff_augment_params(rows, like.shape[1], like.shape[2], self.diffaug, device=like.device)
+        return P
+
     def d_losses(self, feed):
         """What sess.run([D_optim, D_loss]) evaluates before the update (pggan.py:62-73,84-100).  Gradients -> d_arena."""
         x, xm, cond, z = feed['x'], feed['x_mismatch'], feed['cond'], feed['z']
@@ -167,11 +188,19 @@ class PGGAN(object):
         # D(G), D(x), D(x_mismatch) as one pass over 3B samples: without critic_mbstd the critic has no batch coupling; with it the
         # coupling is inside groups of contiguous rows whose size divides B, so no group straddles two of the three parts, and the
         # statistic of the 3B rows is bit for bit that of three B-row passes
-        logits = self.discriminator(torch.cat([G, x, xm], 0), torch.cat([cond, cond, cond], 0), reuse=True, stages=st, t=t).view(3, B)
+        images = torch.cat([G, x, xm], 0)
+        aug = None
+        if self.diffaug is not None:
+            # every image the critic sees goes through T: rows [G | x | x_mismatch | x_hat] of one table, the 3B
+            # pass as one call (a sample's result does not depend on its batch); both penalties are gradients of D o T
+            aug = self._aug_table(feed, 'aug_d', 4 * B, x)
+            images = diff_augment(images, aug[:3 * B], self.diffaug)
+        logits = self.discriminator(images, torch.cat([cond, cond, cond], 0), reuse=True, stages=st, t=t).view(3, B)
         Dg_logit, Dx_logit, Dxmi_logit = logits[0], logits[1], logits[2]
-        x_hat.requires_grad_(True)
+        x_hat.requires_grad_(True)            # before T: the penalty differentiates the adjoint kernel, and its backward
         cond_inp = (cond + 0.0).requires_grad_(True)
-        Dx_hat_logit = self.discriminator(x_hat, cond_inp, reuse=True, stages=st, t=t)
+        Dx_hat_logit = self.discriminator(x_hat if aug is None else diff_augment(x_hat, aug[3 * B:], self.diffaug), cond_inp, reuse=True,
+                                          stages=st, t=t)
         with A.input_grads_only():
             gx, gc = torch.autograd.grad(Dx_hat_logit.sum(), [x_hat, cond_inp], create_graph=True)
         real_gp, real_gp2 = self._penalty(gx), self._penalty(gc)
@@ -191,8 +220,9 @@ class PGGAN(object):
         cond, z = feed['cond'], feed['z']
         self._ca = self._noise(feed, 'ca_noise_g', cond[:, :self.compr_embed_dim])
         G, mean, log_sigma = self.generator(z, cond, stages=self.stage, t=self.trans, reuse=True)
+        G_seen = G if self.diffaug is None else diff_augment(G, self._aug_table(feed, 'aug_g', G.shape[0], G), self.diffaug)
         with self.store.frozen('d_net'):
-            Dg_logit = self.discriminator(G, cond, reuse=True, stages=self.stage, t=self.trans)
+            Dg_logit = self.discriminator(G_seen, cond, reuse=True, stages=self.stage, t=self.trans)
         G_kl_loss = self.kl_std_normal_loss(mean, log_sigma)
         G_loss = -Dg_logit.mean() + self.kl_coeff * G_kl_loss
         self.g_arena.zero_grad()
@@ -225,10 +255,13 @@ class PGGAN(object):
         from ...graphs import StepGraphs
         B, dev = feed['x'].shape[0], self.device
         feed = dict(feed)
-        for k, shape in (('eps_graph', (B,)), ('ca_noise_d', (B, self.compr_embed_dim)), ('ca_noise_g', (B, self.compr_embed_dim))):
+        drawn = (('eps_graph', (B,)), ('ca_noise_d', (B, self.compr_embed_dim)), ('ca_noise_g', (B, self.compr_embed_dim)))
+        if self.diffaug is not None:          # the two parameter tables of the augmentation: static buffers, re-drawn like eps_graph
+            drawn += (('aug_d', (4 * B, 9)), ('aug_g', (B, 9)))
+        for k, shape in drawn:
             if feed.get(k) is None:
                 feed[k] = torch.empty(shape, device=dev)
-        self._graphs = StepGraphs(feed, ('x', 'x_mismatch', 'cond', 'z', 'eps_graph', 'ca_noise_d', 'ca_noise_g'),
+        self._graphs = StepGraphs(feed, ('x', 'x_mismatch', 'cond', 'z') + tuple(k for k, _ in drawn),
                                   filters=(self.d_arena.flat, self.g_arena.flat))
         self._redraw(feed)
         self._graphs.load(feed)
@@ -255,6 +288,11 @@ class PGGAN(object):
         for k in ('ca_noise_d', 'ca_noise_g'):
             if feed.get(k) is None or feed[k] is st[k]:
                 K.trunc_normal_(st[k])
+        if self.diffaug is not None:
+            size = st['x'].shape[1:3]
+            for k in ('aug_d', 'aug_g'):
+                if feed.get(k) is None or feed[k] is st[k]:
+                    diff_augment_params(st[k].shape[0], size[0], size[1], self.diffaug, out=st[k])
 
     def iteration(self, idx, feed):
         """One D update then one G update (pggan.py:196-197)."""

@@ -104,6 +104,9 @@ def main(argv=None):
                     help="the paper's equalized learning rate: kernels drawn from N(0, 2 / fan_in) and stepped by Adam as c * w-hat with "
                          "w-hat ~ N(0, 1), c = sqrt(2 / fan_in), through per-slot multipliers in the Adam launch (default: the reference's "
                          "He initialisation and plain Adam)")
+    ap.add_argument('--diffaug', default=None, metavar='POLICY',
+                    help="differentiable augmentation of every image the critic sees (Zhao et al. 2020): a comma-separated subset of "
+                         "color,translation,cutout (default: none)")
     ap.add_argument('--lr', type=float, default=None, metavar='L', help="Adam's step size (default: the reference's hard-coded 2e-6)")
     ap.add_argument('--eager', action='store_true', help='--bench: keep eager launches instead of hipGraph replay')
     ap.add_argument('--bench', action='store_true', help='time `--iters` iterations of each entry instead of training with side effects')
@@ -116,6 +119,12 @@ def main(argv=None):
         ap.error('--g-ema %r: the decay must lie in (0, 1)' % args.g_ema)
     if args.lr is not None and not (0.0 < args.lr < float('inf')):      # (NaN fails both comparisons)
         ap.error('--lr %r: the step size must be a finite number > 0' % args.lr)
+    if args.diffaug is not None:
+        from t2i_amd.utils.ops import diff_augment_policy
+        try:
+            diff_augment_policy(args.diffaug, '--diffaug')
+        except ValueError as e:
+            ap.error(str(e))
     cfg = None
     if args.cfg is not None:
         from t2i_amd.utils.config import config_from_yaml
@@ -146,7 +155,8 @@ def main(argv=None):
                       dataset=dataset_for(size, dev) if cfg is None else real_dataset(cfg, STAGE[i], dev), sample_path=sample_path,
                       log_dir=logs_dir, stage=STAGE[i], trans=t, device=dev, critic_norm=args.critic_norm,
                       critic_mbstd=args.critic_mbstd, **({} if args.g_ema is None else {'g_ema': args.g_ema}),
-                      **({'equalized_lr': True} if args.equalized_lr else {}), **({} if args.lr is None else {'adam_lr': args.lr}))
+                      **({'equalized_lr': True} if args.equalized_lr else {}), **({} if args.lr is None else {'adam_lr': args.lr}),
+                      **({} if args.diffaug is None else {'diffaug': args.diffaug}))
         if args.bench:
             gen = torch.Generator(device=dev).manual_seed(0)
             feed = pggan.make_feed(gen)

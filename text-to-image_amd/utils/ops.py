@@ -18,6 +18,8 @@ Every public name of the reference's utils/ops.py exists here with its signature
 ``layer_norm``, ``pixel_norm`` and ``minibatch_stddev`` (not in the reference: the PGGAN paper's critic layer) are differentiable twice
 (what a critic under the gradient penalty needs),
 like ``pool``, ``resize_nearest_neighbor``, ``gn``, ``lerp``, ``add`` and the convolutions; ``batch_norm`` / ``batch_renorm`` are first order.
+``diff_augment`` / ``diff_augment_params`` (not in the reference either: the differentiable augmentation of Zhao et al. 2020, DESIGN.md
+section 4.35) take fp32 tensors only, with the same refusals, and are differentiable to any order.
 """
 import math
 
@@ -388,6 +390,85 @@ def minibatch_stddev_stat(x, group_size=4, num_features=1, eps=1e-8):
 def minibatch_stddev(x, group_size=4, num_features=1, eps=1e-8):
     """x [B,H,W,C] -> [B,H,W,C + num_features]: minibatch_stddev_stat tiled over the map and appended as the last channels (concat_tile)."""
     return concat_tile(x, minibatch_stddev_stat(x, group_size, num_features, eps))
+
+
+DIFFAUG_POLICIES = {'color': K.DIFFAUG_COLOR, 'translation': K.DIFFAUG_TRANSLATION, 'cutout': K.DIFFAUG_CUTOUT}
+
+
+def diff_augment_policy(policy, op='diff_augment'):
+    """'color,translation,cutout' or any non-empty subset, in any order -> the kernels' bit mask; anything else is a ValueError."""
+    names = [p.strip() for p in policy.split(',')] if isinstance(policy, str) else None
+    if not names or any(p not in DIFFAUG_POLICIES for p in names):
+        raise ValueError("%s: policy must be a comma-separated, non-empty subset of 'color,translation,cutout', got %r" % (op, policy))
+    mask = 0
+    for p in names:
+        mask |= DIFFAUG_POLICIES[p]
+    return mask
+
+
+def diff_augment(x, params, policy='color,translation,cutout'):
+    """Differentiable augmentation (Zhao et al., NeurIPS 2020; not in the reference): x [B,H,W,C] (contiguous
+    NHWC, fp32) -> T(x) of the same shape, sample n transformed by row n of `params` [B,9] = (b, s, c, ty, tx, y0, y1, x0, x1), a float32
+    tensor on x's device (diff_augment_params draws one):
+      color        u + b, then s u + (1 - s) * (the pixel's channel mean), then c u + (1 - c) * (the sample's mean)
+      translation  shift by (ty, tx) pixels, zeros moving in
+      cutout       zeros in rows [y0, y1) x columns [x0, x1)
+    The columns of a policy that is not named are not read.  At most two launches (one without 'color'); differentiable in x to any
+    order — the backward is the adjoint kernel, whose backward is the forward again — so it may sit in front of a critic under the
+    gradient penalty.  No gradient flows to `params`.  A sample's result does not depend on the batch it sits in, bit for bit."""
+    op = 'diff_augment'
+    _fp32_plain(x, op)
+    mask = diff_augment_policy(policy, op)
+    if not x.is_contiguous():
+        raise ValueError('%s works on physically NHWC data; got a non-contiguous tensor (shape %s, strides %s) - convert a logical NCHW '
+                         'view with to_nhwc first' % (op, tuple(x.shape), x.stride()))
+    if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or tuple(params.shape) != (x.shape[0], 9):
+        raise ValueError('%s: params must be a float32 tensor of shape [%d, 9] (one row per sample), got %s' % (
+            op, x.shape[0], '%s %s' % (params.dtype, tuple(params.shape)) if isinstance(params, torch.Tensor) else type(params).__name__))
+    if params.device != x.device:
+        raise ValueError('%s: params live on %s, x on %s' % (op, params.device, x.device))
+    if not params.is_contiguous():
+        raise ValueError('%s: params must be contiguous (strides %s)' % (op, params.stride()))
+    return A.DiffAugmentFn.apply(x, params.detach(), mask, True)
+
+
+def diff_augment_params(n, H, W, policy='color,translation,cutout', generator=None, out=None, device=None):
+    """One table [n, 9] for diff_augment on H x W images, drawn with the publication's distributions: b ~ U(-0.5, 0.5), s ~ U(0, 2),
+    c ~ U(0.5, 1.5); ty, tx uniform integers in [-r, r], r = int(size / 8 + 0.5); a cutout of extent int(size / 2 + 0.5) whose centre
+    offset is a uniform integer in [0, size - extent mod 2], clipped to the image (never empty).  A policy that is not named gets its
+    identity columns (b 0, s 1, c 1, no shift, an empty rectangle).  Plain tensor-library calls on `out`'s device (or `device`, or
+    the generator's, else the CPU); with `out` ([n, 9] float32) the table is written in place — a captured graph's static buffer is
+    redrawn this way."""
+    op = 'diff_augment_params'
+    mask = diff_augment_policy(policy, op)
+    n, H, W = int(n), int(H), int(W)
+    if n < 1 or H < 1 or W < 1:
+        raise ValueError('%s: n, H and W must be positive, got %d, %d, %d' % (op, n, H, W))
+    if out is None:
+        dev = device if device is not None else (generator.device if generator is not None else 'cpu')
+        out = torch.empty((n, 9), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n, 9):
+        raise ValueError('%s: out must be a float32 tensor of shape [%d, 9], got %s %s' % (op, n, out.dtype, tuple(out.shape)))
+    dev = out.device
+    with torch.no_grad():
+        out.zero_()
+        out[:, 1:3].fill_(1.0)
+        if mask & K.DIFFAUG_COLOR:
+            u = torch.rand((n, 3), generator=generator, device=dev, dtype=torch.float32)
+            out[:, 0] = u[:, 0] - 0.5
+            out[:, 1] = u[:, 1] * 2.0
+            out[:, 2] = u[:, 2] + 0.5
+        if mask & K.DIFFAUG_TRANSLATION:
+            for col, size in ((3, H), (4, W)):
+                r = int(size / 8.0 + 0.5)
+                out[:, col] = torch.randint(-r, r + 1, (n,), generator=generator, device=dev).float()
+        if mask & K.DIFFAUG_CUTOUT:
+            for col, size in ((5, H), (7, W)):
+                ext = int(size / 2.0 + 0.5)
+                lo = torch.randint(0, size - ext % 2 + 1, (n,), generator=generator, device=dev) - ext // 2
+                out[:, col] = lo.clamp(min=0).float()
+                out[:, col + 1] = (lo + ext).clamp(max=size).float()
+    return out
 
 
 def pool(x, s=2, p_type='AVG', df=NHWC):

@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """The memory-bound kernels of csrc/t2i_ops.hip (pixel_norm, nearest resize and its adjoint, pool AVG / MAX with their backward maps,
 gn, the double backward of pixel_norm and layer_norm, the minibatch standard deviation) at PGGAN-sized tensors, and the Adam launch with and
-without the weight EMA (`--only adam_ema`) and with per-slot multipliers (`--only adam_slots`) at the sizes of two generator arenas: one JSON line per kernel with the time per call, the bytes the algorithm moves (reads + writes, from the
+without the weight EMA (`--only adam_ema`) and with per-slot multipliers (`--only adam_slots`) at the sizes of two generator arenas, and the
+differentiable augmentation of csrc/t2i_augment.hip at the PGGAN trainer's shapes next to the same policy from tensor-library calls
+(`--only diff_augment`): one JSON line per kernel with the time per call, the bytes the algorithm moves (reads + writes, from the
 shapes), bytes per second, and the ratio of that rate to a device-to-device copy that moves the SAME number of bytes (half read, half
 written), timed in the same process.  Per measurement: 10 warm-up launches, then REPS rounds of 100 back-to-back launches between
 device events, kernel and copy rounds alternating; the median round is reported.  Read the ratio, not the absolute rate, as the share
@@ -38,22 +40,49 @@ def _round(fn, iters):
     return s.elapsed_time(e) / iters * 1e-3
 
 
-def measure(name, shape, nbytes, fn, reps, iters):
+def measure(name, shape, nbytes, fn, reps, iters, composed=None):
+    """composed: the same operation as tensor-library calls, timed in the same alternating rounds ('composed_us', 'ratio_to_composed')"""
     src = torch.empty(nbytes // 8, dtype=torch.float32, device='cuda').normal_()
     dst = torch.empty_like(src)
     copy = lambda: dst.copy_(src)          # moves nbytes: nbytes / 2 read + nbytes / 2 written
     for _ in range(10):
         fn(); copy()
+        if composed is not None:
+            composed()
     torch.cuda.synchronize()
-    tk, tc = [], []
+    tk, tc, tl = [], [], []
     for _ in range(reps):
         tk.append(_round(fn, iters))
         tc.append(_round(copy, iters))
+        if composed is not None:
+            tl.append(_round(composed, iters))
     t, c = statistics.median(tk), statistics.median(tc)
-    print(json.dumps({'kernel': name, 'shape': list(shape), 'us_per_call': round(t * 1e6, 2), 'bytes': nbytes,
-                      'working_set_MB': round(nbytes / 1e6, 1), 'in_infinity_cache': nbytes <= INFINITY_CACHE // 2,
-                      'GB_per_s': round(nbytes / t / 1e9, 1), 'copy_us': round(c * 1e6, 2), 'copy_GB_per_s': round(nbytes / c / 1e9, 1),
-                      'ratio_to_copy': round(c / t, 3), 'spread_us': [round(min(tk) * 1e6, 2), round(max(tk) * 1e6, 2)]}), flush=True)
+    line = {'kernel': name, 'shape': list(shape), 'us_per_call': round(t * 1e6, 2), 'bytes': nbytes,
+            'working_set_MB': round(nbytes / 1e6, 1), 'in_infinity_cache': nbytes <= INFINITY_CACHE // 2,
+            'GB_per_s': round(nbytes / t / 1e9, 1), 'copy_us': round(c * 1e6, 2), 'copy_GB_per_s': round(nbytes / c / 1e9, 1),
+            'ratio_to_copy': round(c / t, 3), 'spread_us': [round(min(tk) * 1e6, 2), round(max(tk) * 1e6, 2)]}
+    if composed is not None:
+        line.update(composed_us=round(statistics.median(tl) * 1e6, 2), ratio_to_composed=round(statistics.median(tl) / t, 2))
+    print(json.dumps(line), flush=True)
+
+
+def composed_diff_augment(x, P):
+    """The policy 'color,translation,cutout' of utils.ops.diff_augment from tensor-library calls, the way the publication's code builds it
+    (blends around the means, a padded index gather for the shift, a multiplicative mask for the cutout), NHWC, from the same table"""
+    B, H, W, C = x.shape
+    col = lambda j: P[:, j].view(B, 1, 1, 1)
+    u = x + col(0)
+    m = u.mean(3, keepdim=True)
+    u = (u - m) * col(1) + m
+    m = u.mean((1, 2, 3), keepdim=True)
+    u = (u - m) * col(2) + m
+    ar = lambda n, shape: torch.arange(n, device=x.device).view(shape)
+    gy = (ar(H, (1, H, 1)) - P[:, 3].long().view(B, 1, 1) + 1).clamp(0, H + 1)
+    gx = (ar(W, (1, 1, W)) - P[:, 4].long().view(B, 1, 1) + 1).clamp(0, W + 1)
+    u = torch.nn.functional.pad(u, [0, 0, 1, 1, 1, 1])[ar(B, (B, 1, 1)), gy, gx]
+    yy, xx = ar(H, (1, H, 1)), ar(W, (1, 1, W))
+    inside = (yy >= P[:, 5].view(B, 1, 1)) & (yy < P[:, 6].view(B, 1, 1)) & (xx >= P[:, 7].view(B, 1, 1)) & (xx < P[:, 8].view(B, 1, 1))
+    return u * (~inside).unsqueeze(3).to(u.dtype)
 
 
 def main():
@@ -168,6 +197,28 @@ def main():
             m('adam_slots: t2i_adam_tf_slots + shadow beta1=0 m=NULL, %s (4r + 3w)' % tag, (n,), 28 * n,
               lambda: K.adam_tf_slots(w, g, None, v, slot_end, slot_mult, 0.0, 0.0, 0.99, 1e-8, 1.0, ema=s, ema_decay=0.999, lr_t_dev=lr,
                                       ema_decay_dev=dec))
+
+    # differentiable augmentation at the PGGAN trainer's shapes, the 3B-row critic pass of stages 3, 5 and 7 (batch
+    # 16, 16, 8), policy 'color,translation,cutout': the partial-sum pass reads the tensor, the apply kernel reads it again and writes it
+    # (2r + w).  Next to each line: the same policy from tensor-library calls on the same table (for the adjoint, autograd's backward of that
+    # composition on a retained graph), checked against the kernels before anything is timed.
+    if a.only in 'diff_augment' or 'diff_augment' in a.only:
+        from t2i_amd.utils import ops
+        for shape in ((48, 16, 16, 3), (48, 64, 64, 3), (24, 256, 256, 3)):
+            x = torch.randn(shape, device='cuda')
+            g = torch.randn(shape, device='cuda')
+            P = ops.diff_augment_params(shape[0], shape[1], shape[2], device='cuda')
+            n = x.numel()
+            xr = x.clone().requires_grad_(True)
+            yr = composed_diff_augment(xr, P)
+            back = lambda: torch.autograd.grad(yr, xr, g, retain_graph=True)
+            assert float((K.diff_augment_fwd(x, P, 7) - yr.detach()).abs().max()) <= 1e-4
+            assert float((K.diff_augment_adj(g, P, 7) - back()[0]).abs().max()) <= 1e-4
+            with torch.no_grad():
+                m2 = lambda name, fn, comp: measure(name, shape, 12 * n, fn, a.reps, a.iters, comp) if a.only in name else None
+                m2('diff_augment_fwd color,translation,cutout (2r + w)', lambda: K.diff_augment_fwd(x, P, 7), lambda: composed_diff_augment(x, P))
+            m2('diff_augment_adj color,translation,cutout (2r + w)', lambda: K.diff_augment_adj(g, P, 7), back)
+            m('diff_augment_fwd translation,cutout, one launch (r + w)', shape, 8 * n, lambda: K.diff_augment_fwd(x, P, 6))
 
 
 if __name__ == '__main__':
