@@ -202,7 +202,8 @@ int t2i_bn_stats(const float* x, int64_t rows, int32_t C, float* sum, float* m2,
 int t2i_bn_stats_tiles(const float* part_sum, const float* part_m2, int32_t chunks, int32_t tile_rows, int64_t rows, int32_t C,
                        float* sum, float* m2, t2i_stream_t stream);
 /* Statistics AND the finalize step in one chain (stage 1 + one stage-2 launch): exactly one of x (the tensor, [rows, C];
- * workspace as t2i_col_reduce) or the tile partials of t2i_conv2d_fwd_stats (part_sum / part_m2 / chunks / tile_rows).
+ * workspace as t2i_col_reduce) or the tile partials of t2i_conv2d_fwd_stats (part_sum / part_m2 / chunks / tile_rows;
+ * chunks = ceil(rows / tile_rows) as for t2i_bn_stats_tiles, anything else is refused).
  * Outputs as t2i_bn_finalize.  What the training-mode batch norm of utils/ops.py:7-29 launches in front of t2i_bn_apply. */
 int t2i_bn_train_fwd_stats(const void* x, const float* part_sum, const float* part_m2, int32_t chunks, int32_t tile_rows, int64_t rows,
                            int32_t C, const float* gamma, const float* beta, float eps, float decay, float* mean, float* rstd,

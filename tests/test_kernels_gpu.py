@@ -693,8 +693,10 @@ def test_bf16_filter_gradient_dma_and_transposing_reads(K, case):
 def test_bn_stats_are_stable_against_a_large_mean(K, rows, C, offset):
     """t2i_bn_stats: (sum, sum (x - mean)^2) by shifted per-chunk moments + Chan merging.  x = offset + unit noise: the
     two-moment formula sum(x^2)/n - mean^2 that round 1 used loses (offset/std)^2 * 2^-24 of the variance (offset 1000, std 1:
-    6 % relative error — and a rank-2 batch norm over a batch of 2 is the extreme case); the stable form must give the
-    variance to 1e-5 and the normalised output of batch norm to 1e-5 * the offset's own representation error."""
+    6 % relative error — and a rank-2 batch norm over a batch of 2 is the extreme case); the stable form must give the column
+    sums to 1e-6, the centred second moments to 1e-5, and the backward's centred sum of dy * (x - mean) to 1e-4 of their largest
+    entry.  The normalised output y and the gradient dx, which cancel once more where |mean| >> std, are not formed here:
+    tests/test_col_bn_gpu.py test_large_mean holds them to bounds derived from the kernels' arithmetic."""
     rng = np.random.default_rng(rows + C)
     x = (offset + rng.standard_normal((rows, C))).astype(np.float32)
     xd = x.astype(np.float64)

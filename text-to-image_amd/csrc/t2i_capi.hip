@@ -1231,8 +1231,11 @@ int t2i_bn_train_fwd_stats(const void* x, const float* part_sum, const float* pa
                            float* scale, float* shift, float* moving_mean, float* moving_var, void* ws, size_t ws_bytes,
                            int32_t dtype, t2i_stream_t stream) {
   if (!gamma || !beta || !mean || !rstd || !scale || !shift || rows <= 0 || C <= 0 || ((moving_mean == nullptr) != (moving_var == nullptr)) ||
-      ((x == nullptr) == (part_sum == nullptr)) || (part_sum && (!part_m2 || chunks <= 0 || tile_rows <= 0))) {
-    set_error("t2i_bn_train_fwd_stats: bad argument (exactly one of x / tile partials)");
+      ((x == nullptr) == (part_sum == nullptr)) ||
+      (part_sum && (!part_m2 || chunks <= 0 || tile_rows <= 0 || (int64_t)chunks * tile_rows < rows || (int64_t)(chunks - 1) * tile_rows >= rows))) {
+    // (as t2i_bn_stats_tiles: a tile that starts behind the last row has <= 0 rows: 1/n = inf, NaN statistics in the moving averages;
+    //  tiles that stop short of it give the statistics of fewer rows than the normalisation divides by)
+    set_error("t2i_bn_train_fwd_stats: bad argument (exactly one of x / tile partials; exactly ceil(rows / tile_rows) tiles)");
     return T2I_ERR_INVALID;
   }
   if (x) {
