@@ -811,6 +811,25 @@ size_t t2i_ball_counts_workspace_bytes(int64_t M, int64_t N, int32_t D, int32_t 
 int t2i_ball_counts(const float* Q, int64_t M, const float* R, int64_t N, int32_t D, const double* r2, int32_t segments, int32_t* count,
                     double* dmin, void* workspace, size_t workspace_bytes, t2i_stream_t stream);
 
+/* ---- the kernel sums of the polynomial-kernel MMD^2 (evaluation/mmd.py: the Kernel Inception distance of Binkowski et al. 2018,
+ * "Demystifying MMD GANs"; the reference has no such metric).  Added within ABI v13: no existing argument list changed. ------------- */
+/* X [NX, D] and Y [NY, D] are dense row-major fp32 on the device (they may be one tensor); ix and iy are device int32 [S, m]: subset s
+ * is the rows ix[s, 0..m) of X and iy[s, 0..m) of Y.  With k(a, b) = (gamma a.b + coef0)^degree, every a.b one fp64 sum over ascending
+ * d of the inputs widened exactly, t = fma(gamma, a.b, coef0) and degree - 1 multiplications by t:
+ *   sums[s, 0] = P_xx = sum_{i<j} k(x_i, x_j)     sums[s, 1] = P_yy likewise     sums[s, 2] = S_xy = sum_{i,j} k(x_i, y_j)
+ * with i and j POSITIONS in the subset: a row named twice forms a pair with itself, a position never does.  No m x m matrix and no
+ * copy of a subset is written; tiles of the two symmetric products below the diagonal are not computed.  One double per tile goes to the
+ * workspace and a second launch adds each sum's tiles in ascending order: no atomics, results are bit-identical from call to call.
+ * An index outside 0..N-1 is not dereferenced: its row counts as NaNs, so exactly the sums of its subset that it enters are NaN.
+ * Every refusal returns T2I_ERR_INVALID before anything is launched: a NULL pointer; NX, NY, D or S < 1; m < 2; degree outside 1..8;
+ * gamma or coef0 not finite; NX D or NY D >= 2^31 * 64; more than 2^30 work items (tiles of all subsets and products: the grid of the
+ * one launch); a workspace smaller than the query; sums or the workspace overlapping an input, an index table or each other; a
+ * misaligned pointer (4 bytes for fp32 and int32, 8 for fp64 and the workspace).  The entry only enqueues work. */
+size_t t2i_poly_mmd_sums_workspace_bytes(int64_t NX, int64_t NY, int32_t D, int32_t S, int32_t m);
+int t2i_poly_mmd_sums(const float* X, int64_t NX, const float* Y, int64_t NY, int32_t D, const int32_t* ix, const int32_t* iy, int32_t S,
+                      int32_t m, int32_t degree, double gamma, double coef0, double* sums, void* workspace, size_t workspace_bytes,
+                      t2i_stream_t stream);
+
 /* ---- differentiable augmentation (Zhao et al., "Differentiable Augmentation for Data-Efficient GAN Training", NeurIPS 2020; the
  * reference has no such layer).  Added within ABI v13: no existing argument list changed. ------------------------------------------- */
 /* x [B,H,W,C] fp32 and one row of params [B,9] fp32 = (b, s, c, ty, tx, y0, y1, x0, x1) per sample, the six geometric entries

@@ -166,6 +166,8 @@ SIGNATURES = {
     't2i_knn_dist2': (ctypes.c_int, [_p, _i64, _p, _i64, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),
     't2i_ball_counts_workspace_bytes': (_sz, [_i64, _i64, _i32, _i32]),
     't2i_ball_counts': (ctypes.c_int, [_p, _i64, _p, _i64, _i32, _p, _i32, _p, _p, _p, _sz, _p]),
+    't2i_poly_mmd_sums_workspace_bytes': (_sz, [_i64, _i64, _i32, _i32, _i32]),
+    't2i_poly_mmd_sums': (ctypes.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _i32, _i32, _i32, ctypes.c_double, ctypes.c_double, _p, _p, _sz, _p]),
     't2i_diff_augment_workspace_bytes': (_sz, [_i32, _i32, _i32, _i32, _i32]),
     't2i_diff_augment_fwd': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),
     't2i_diff_augment_adj': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),

@@ -92,6 +92,11 @@ size_t knn_dist2_ws(int64_t M, int64_t N, int segments);
 size_t ball_counts_ws(int64_t M, int64_t N, int segments);
 hipError_t knn_dist2_launch(const float*, int64_t, const float*, int64_t, int, int, int, int, double*, void*, hipStream_t);
 hipError_t ball_counts_launch(const float*, int64_t, const float*, int64_t, int, const double*, int, int32_t*, double*, void*, hipStream_t);
+// implemented in t2i_mmd.hip
+int64_t poly_mmd_items_per_subset(int64_t m);
+size_t poly_mmd_sums_ws(int64_t S, int64_t m);
+hipError_t poly_mmd_sums_launch(const float*, int64_t, const float*, int64_t, int, const int32_t*, const int32_t*, int64_t, int64_t, int, double,
+                                double, double*, void*, hipStream_t);
 // implemented in t2i_preprocess.hip
 int pillow_table_taps(int filter, int in_size, int out_size);
 hipError_t pillow_tables_launch(int, const int32_t*, int64_t, int, int32_t*, int32_t*, int, hipStream_t);
@@ -2290,6 +2295,46 @@ int t2i_ball_counts(const float* Q, int64_t M, const float* R, int64_t N, int32_
   }
   return check(ball_counts_launch(Q, M, R, N, D, r2, segments ? segments : knn_auto_segments(M, N), count, dmin, workspace,
                                   (hipStream_t)stream), "t2i_ball_counts");
+}
+
+// ---- the kernel sums of the polynomial-kernel MMD^2 (t2i_mmd.hip) -------------------------------------------------------------------
+static const int64_t kMmdMaxItems = (int64_t)1 << 30;       // work items = workgroups of the one launch
+
+static bool mmd_shape_ok(int64_t NX, int64_t NY, int32_t D, int32_t S, int32_t m) {
+  if (!(NX >= 1 && NY >= 1 && D >= 1 && S >= 1 && m >= 2 && NX < (kKnnLim + D - 1) / D && NY < (kKnnLim + D - 1) / D)) return false;
+  const int64_t per = poly_mmd_items_per_subset(m);          // at most 3 * 2^49
+  return per <= kMmdMaxItems && (int64_t)S * per <= kMmdMaxItems;
+}
+
+size_t t2i_poly_mmd_sums_workspace_bytes(int64_t NX, int64_t NY, int32_t D, int32_t S, int32_t m) {
+  if (!mmd_shape_ok(NX, NY, D, S, m)) return 0;
+  return poly_mmd_sums_ws(S, m);
+}
+
+int t2i_poly_mmd_sums(const float* X, int64_t NX, const float* Y, int64_t NY, int32_t D, const int32_t* ix, const int32_t* iy, int32_t S,
+                      int32_t m, int32_t degree, double gamma, double coef0, double* sums, void* workspace, size_t workspace_bytes,
+                      t2i_stream_t stream) {
+  bool ok = X && Y && ix && iy && sums && workspace && aligned4(X) && aligned4(Y) && aligned4(ix) && aligned4(iy) && aligned8(sums) &&
+            aligned8(workspace) && mmd_shape_ok(NX, NY, D, S, m) && degree >= 1 && degree <= 8 && std::isfinite(gamma) && std::isfinite(coef0);
+  size_t need = 0;
+  if (ok) {
+    need = t2i_poly_mmd_sums_workspace_bytes(NX, NY, D, S, m);
+    const void* in[4] = {X, Y, ix, iy};
+    const uint64_t in_bytes[4] = {(uint64_t)NX * D * 4, (uint64_t)NY * D * 4, (uint64_t)S * m * 4, (uint64_t)S * m * 4};
+    const uint64_t sums_bytes = (uint64_t)S * 3 * 8;
+    for (int j = 0; j < 4; ++j) ok = ok && !swd_overlap(sums, sums_bytes, in[j], in_bytes[j]) && !swd_overlap(workspace, need, in[j], in_bytes[j]);
+    ok = ok && !swd_overlap(sums, sums_bytes, workspace, need) && workspace_bytes >= need;
+  }
+  if (!ok) {
+    set_error("t2i_poly_mmd_sums: bad argument (NX=%lld NY=%lld D=%d S=%d m=%d degree=%d gamma=%g coef0=%g, X %s, Y %s, ix %s, iy %s, sums %s, "
+              "workspace %s of %zu bytes, need %zu; NX, NY, D, S >= 1, m >= 2, NX D and NY D < 2^37, degree in 1..8, finite gamma and "
+              "coef0, at most 2^30 work items, aligned tensors, sums and the workspace apart from the inputs and each other)",
+              (long long)NX, (long long)NY, D, S, m, degree, gamma, coef0, X ? "given" : "NULL", Y ? "given" : "NULL", ix ? "given" : "NULL",
+              iy ? "given" : "NULL", sums ? "given" : "NULL", workspace ? "given" : "NULL", workspace_bytes, need);
+    return T2I_ERR_INVALID;
+  }
+  return check(poly_mmd_sums_launch(X, NX, Y, NY, D, ix, iy, S, m, degree, gamma, coef0, sums, workspace, (hipStream_t)stream),
+               "t2i_poly_mmd_sums");
 }
 
 }  // extern "C"

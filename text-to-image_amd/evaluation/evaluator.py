@@ -18,6 +18,7 @@ resolution level; it needs no Inception net and no EVAL.ACT_STAT_PATH.  evaluate
 evaluation that compares generated images with each other: the multi-scale structural similarity of pairs of them, which is 1 for a
 generator that ignores z; it needs no Inception net either.  evaluate_prdc (evaluation/prdc.py) asks where the generated SET lies:
 precision, recall, density and coverage from k-nearest-neighbour balls around the PreLogits features of evaluate_imd's batches.
+evaluate_mmd (evaluation/mmd.py) is the Kernel Inception distance of the same two feature sets, the distance for small test splits.
 
 A model's evaluator states what differs (DESIGN.md has the table): restore(), dims(), generate_batch(), and the attributes below."""
 import os
@@ -28,7 +29,7 @@ import torch
 from .. import kernels as K
 from ..models.inception.model import IMAGE_SIZE, load_inception_inference
 from ..utils.saver import restore_g_net
-from . import fid, imd, inception_score, msssim, prdc, swd
+from . import fid, imd, inception_score, mmd, msssim, prdc, swd
 
 
 class GeneratorEval(object):
@@ -267,24 +268,48 @@ class GeneratorEval(object):
         every radius would collapse); generated features are kept for all SIZE // bs batches."""
         if int(nearest_k) != nearest_k or not 1 <= int(nearest_k) <= K.KNN_MAX_K:
             raise ValueError('evaluate_prdc: nearest_k must be in 1..%d, got %r' % (K.KNN_MAX_K, nearest_k))
+        mm = self._feature_sets(lambda dim: prdc.ManifoldMetrics(dim, self.model.device, nearest_k), keep_samples)
+        out = mm.finalize()
+        print('PRDC (k = %d) | precision: %.4f recall: %.4f density: %.4f coverage: %.4f | %d real, %d generated' % (
+            out['nearest_k'], out['precision'], out['recall'], out['density'], out['coverage'], out['n_real'], out['n_gen']))
+        return self._with_kept_sets(out, mm, keep_samples, keep_features)
+
+    def _feature_sets(self, make, keep_samples):
+        """The loop evaluate_prdc and evaluate_mmd share: -> make(dim), fed with the PreLogits features of evaluate_imd's batches, the
+        real ones for the first num_examples // bs batches only."""
         net = self._inception()
         self.restore()
         c = self.incep_batch_size
         real_batches = self.dataset.test.num_examples // self.bs
-        mm = None
+        sets = None
         for i, (real, gen) in enumerate(self._batches(False, keep_samples, with_real=True)):
             for s in range(0, self.bs, c):
                 pre_real, pre_gen = imd.pair_features(real[s:s + c], gen[s:s + c], net)
-                if mm is None:
-                    mm = prdc.ManifoldMetrics(pre_gen.shape[1], self.model.device, nearest_k)
+                if sets is None:
+                    sets = make(pre_gen.shape[1])
                 if i < real_batches:
-                    mm.add_real(pre_real)
-                mm.add_gen(pre_gen)
-        out = mm.finalize()
-        print('PRDC (k = %d) | precision: %.4f recall: %.4f density: %.4f coverage: %.4f | %d real, %d generated' % (
-            out['nearest_k'], out['precision'], out['recall'], out['density'], out['coverage'], out['n_real'], out['n_gen']))
+                    sets.add_real(pre_real)
+                sets.add_gen(pre_gen)
+        return sets
+
+    def _with_kept_sets(self, out, sets, keep_samples, keep_features):
         if keep_samples:
             out.update(real=np.concatenate([r for r, _ in self._kept]), gen=np.concatenate([g for _, g in self._kept]))
         if keep_features:
-            out.update(real_features=mm.real.rows().cpu().numpy(), gen_features=mm.gen.rows().cpu().numpy())
+            out.update(real_features=sets.real.rows().cpu().numpy(), gen_features=sets.gen.rows().cpu().numpy())
         return out
+
+    def evaluate_mmd(self, num_subsets=100, max_subset_size=1000, keep_samples=False, keep_features=False):
+        """-> KernelDistance.finalize()'s dict (kid, kid_std, subsets, subset_size, n_real, n_gen, degree, gamma, coef0) (+ real, gen
+        and real_features, gen_features as evaluate_prdc): the Kernel Inception distance (evaluation/mmd.py) of the feature sets of
+        evaluate_prdc, by the same batches, chunks and one-epoch rule for the real set; the draws from the global np.random are those
+        of evaluate_imd (the subsets come from the metric's own generator)."""
+        if int(num_subsets) != num_subsets or not 1 <= int(num_subsets) <= mmd.MAX_SUBSETS:
+            raise ValueError('evaluate_mmd: num_subsets must be in 1..%d, got %r' % (mmd.MAX_SUBSETS, num_subsets))
+        if int(max_subset_size) != max_subset_size or int(max_subset_size) < 2:
+            raise ValueError('evaluate_mmd: max_subset_size must be at least 2, got %r' % (max_subset_size,))
+        kd = self._feature_sets(lambda dim: mmd.KernelDistance(dim, self.model.device, num_subsets, max_subset_size), keep_samples)
+        out = kd.finalize()
+        print('KID x 1e3 (--eval mmd) | mean: %.4f std: %.4f | %d subsets of %d | %d real, %d generated' % (
+            1e3 * out['kid'], 1e3 * out['kid_std'], out['subsets'], out['subset_size'], out['n_real'], out['n_gen']))
+        return self._with_kept_sets(out, kd, keep_samples, keep_features)

@@ -39,12 +39,12 @@ def ratios(cnt_gen, cnt_real, covered, nearest_k):
 class _Rows(object):
     """[n, dim] float32 rows on the device; the buffer doubles when it is full."""
 
-    def __init__(self, dim, device):
-        self.dim, self.device, self.n, self.buf = dim, device, 0, None
+    def __init__(self, dim, device, owner='ManifoldMetrics'):
+        self.dim, self.device, self.n, self.buf, self.owner = dim, device, 0, None, owner
 
     def add(self, feat, name):
         if feat.dim() != 2 or feat.shape[1] != self.dim:
-            raise ValueError('ManifoldMetrics.%s: features must be [n, %d], got %s' % (name, self.dim, tuple(feat.shape)))
+            raise ValueError('%s.%s: features must be [n, %d], got %s' % (self.owner, name, self.dim, tuple(feat.shape)))
         feat = feat.detach().to(device=self.device, dtype=torch.float32)
         need = self.n + feat.shape[0]
         if self.buf is None or need > self.buf.shape[0]:

@@ -2208,3 +2208,62 @@ def ball_counts(q, r, r2, segments=0):
         check(lib.t2i_ball_counts(_ptr(q), M, _ptr(r), N, D, _ptr(r2), segments, _ptr(count), _ptr(dmin), wsp, wsn, _stream()),
               't2i_ball_counts')
     return count, dmin
+
+
+# ---- the kernel sums of the polynomial-kernel MMD^2 in fp64 (csrc/t2i_mmd.hip; evaluation/mmd.py is the caller) ------------------
+MMD_MAX_DEGREE = 8
+MMD_MAX_ITEMS = 1 << 30
+
+
+def poly_mmd_items(S, m):
+    """Work items (= workgroups) of poly_mmd_sums: per subset the 64 x 128 tiles of x.y and, of x.x and y.y, those that hold a pair
+    i < j (row tile ti has the column tiles ti // 2 and above)."""
+    nrt, nct = (m + 63) // 64, (m + 127) // 128
+    a = nrt // 2                                          # row tiles 2 a' and 2 a' + 1 have nct - a' column tiles each
+    sym = 2 * a * nct - a * (a - 1) + (nct - a if nrt % 2 else 0)
+    return S * (2 * sym + nrt * nct)
+
+
+def poly_mmd_sums(x, y, ix, iy, degree=3, gamma=None, coef0=1.0, check_indices=True):
+    """-> float64 [S, 3]: per subset s the sums P_xx = sum_{i<j} k(x_i, x_j), P_yy and S_xy = sum_{i,j} k(x_i, y_j) of the polynomial
+    kernel k(a, b) = (gamma a.b + coef0)^degree over the rows x[ix[s]] and y[iy[s]], i and j positions in the subset
+    (t2i_poly_mmd_sums: every product in fp64, no m x m matrix, no gathered copy).  x [NX, D], y [NY, D] device float32 (they may be
+    the same tensor), ix, iy device int32 [S, m]; gamma None = 1 / D.  check_indices does one device min / max over the tables and
+    raises on an index out of range (a synchronisation: pass False inside a graph capture, where such an index makes its subset's
+    sums NaN and is never dereferenced)."""
+    name = 'poly_mmd_sums'
+    _f32_nd(x, '%s: x' % name, 2); _f32_nd(y, '%s: y' % name, 2)
+    if x.shape[1] != y.shape[1] or x.device != y.device:
+        raise ValueError('%s: x %s on %s and y %s on %s must share the feature dimension and the device' % (
+            name, tuple(x.shape), x.device, tuple(y.shape), y.device))
+    for t, tn in ((ix, 'ix'), (iy, 'iy')):
+        if t.dtype != torch.int32 or t.dim() != 2 or not t.is_contiguous() or t.device != x.device:
+            raise ValueError('%s: %s must be a contiguous int32 [S, m] tensor on %s, got %s %s on %s' % (
+                name, tn, x.device, t.dtype, tuple(t.shape), t.device))
+    if tuple(ix.shape) != tuple(iy.shape):
+        raise ValueError('%s: ix %s and iy %s must have the same shape' % (name, tuple(ix.shape), tuple(iy.shape)))
+    NX, D = (int(s) for s in x.shape)
+    NY = int(y.shape[0])
+    S, m = (int(s) for s in ix.shape)
+    degree, coef0 = int(degree), float(coef0)
+    gamma = 1.0 / max(D, 1) if gamma is None else float(gamma)
+    if min(NX, NY, D, S) < 1 or m < 2 or max(NX, NY) * D >= 1 << 37 or m >= 1 << 31 or S >= 1 << 31:
+        raise ValueError('%s: x %s, y %s, tables %s: NX, NY, D, S >= 1, m >= 2, fewer than 2^37 elements per set' % (
+            name, tuple(x.shape), tuple(y.shape), tuple(ix.shape)))
+    if not 1 <= degree <= MMD_MAX_DEGREE or not (np.isfinite(gamma) and np.isfinite(coef0)):
+        raise ValueError('%s: degree %d, gamma %r, coef0 %r: degree in 1..%d, gamma and coef0 finite' % (
+            name, degree, gamma, coef0, MMD_MAX_DEGREE))
+    if poly_mmd_items(S, m) > MMD_MAX_ITEMS:
+        raise ValueError('%s: %d subsets of %d rows are %d work items, more than 2^30: score the subsets in several calls' % (
+            name, S, m, poly_mmd_items(S, m)))
+    sums = torch.empty((S, 3), dtype=torch.float64, device=x.device)
+    if _live(x):
+        if check_indices:
+            for t, tn, n in ((ix, 'ix', NX), (iy, 'iy', NY)):
+                lo, hi = (int(v) for v in torch.stack(torch.aminmax(t)).cpu())
+                if lo < 0 or hi >= n:
+                    raise ValueError('%s: %s holds indices %d..%d, the set has rows 0..%d' % (name, tn, lo, hi, n - 1))
+        wsp, wsn = _ws_args(x, int(lib.t2i_poly_mmd_sums_workspace_bytes(NX, NY, D, S, m)))
+        check(lib.t2i_poly_mmd_sums(_ptr(x), NX, _ptr(y), NY, D, _ptr(ix), _ptr(iy), S, m, degree, gamma, coef0, _ptr(sums), wsp, wsn,
+                                    _stream()), 't2i_poly_mmd_sums')
+    return sums

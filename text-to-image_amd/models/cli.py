@@ -9,6 +9,9 @@ PAIRINGS = ('random', 'caption')
 FEATURE_MODES = ('prdc',)           # evaluations of the two feature SETS: evaluate_<mode>(nearest_k=...)
 KNN_MAX_K = 8                       # kernels.KNN_MAX_K (not imported: argument errors come before anything touches the device library)
 DEFAULT_NEAREST_K = 5
+SUBSET_MODES = ('mmd',)             # evaluations over random subsets of the two feature sets: evaluate_<mode>(num_subsets=..., max_subset_size=...)
+MAX_SUBSETS = 10000                 # evaluation.mmd.MAX_SUBSETS (not imported, as above)
+DEFAULT_SUBSETS = (100, 1000)       # subsets, rows per subset at most: the published KID protocol
 
 
 class Parser(argparse.ArgumentParser):
@@ -18,6 +21,7 @@ class Parser(argparse.ArgumentParser):
         parsed = super(Parser, self).parse_args(*args, **kwargs)
         check_pairs(self, parsed)
         check_nearest_k(self, parsed)
+        check_subsets(self, parsed)
         return parsed
 
 
@@ -26,15 +30,16 @@ def make_parser(default_cfg):
     ap.add_argument('--cfg', default=default_cfg, help='Relative path to the config of the model')
     mode = ap.add_mutually_exclusive_group()
     mode.add_argument('--train', action='store_true', help='train even if the yml says TRAIN.FLAG: False')
-    mode.add_argument('--eval', choices=EVAL_MODES + PAIR_MODES + FEATURE_MODES, default=None, help='Inception score, FID, Inception match '
-                      'distance, sliced Wasserstein distance, multi-scale SSIM between generated pairs or precision / recall / density / '
-                      'coverage of the latest checkpoint (needs the pickled dataset and, except for swd and msssim, an Inception '
-                      'checkpoint in EVAL.INCEP_CHECKPOINT_DIR)')
+    mode.add_argument('--eval', choices=EVAL_MODES + PAIR_MODES + FEATURE_MODES + SUBSET_MODES, default=None, help='Inception score, FID, '
+                      'Inception match distance, sliced Wasserstein distance, multi-scale SSIM between generated pairs, precision / recall / '
+                      'density / coverage or the Kernel Inception distance (KID: --eval mmd) of the latest checkpoint (needs the pickled '
+                      'dataset and, except for swd and msssim, an Inception checkpoint in EVAL.INCEP_CHECKPOINT_DIR)')
     mode.add_argument('--visualize', action='store_true', help='run the caption visualiser on the latest checkpoint (needs the '
                       'pickled dataset)')
     ap.add_argument('--incep-batch', type=int, default=None, help='--eval: Inception batch size (default EVAL.INCEP_BATCH_SIZE)')
     add_pairs_argument(ap)
     add_nearest_k_argument(ap)
+    add_subsets_arguments(ap)
     ap.add_argument('--interp', type=int, default=0, help='--visualize: rounds of interpolation / captioned sheets (default 0)')
     ap.add_argument('--synthetic', action='store_true', help='--train: synthetic on-device dataset instead of cfg.DATASET_DIR')
     ap.add_argument('--steps', type=int, default=None, help='--train: stop after this many updates')
@@ -69,6 +74,28 @@ def check_nearest_k(ap, args):
             ap.error('--prdc-k must be in 1..%d' % KNN_MAX_K)
 
 
+def add_subsets_arguments(ap):
+    ap.add_argument('--mmd-subsets', type=int, default=None, help='--eval mmd (KID): the number of random subsets the estimate is '
+                    'averaged over, 1..%d (default %d)' % (MAX_SUBSETS, DEFAULT_SUBSETS[0]))
+    ap.add_argument('--mmd-subset-size', type=int, default=None, help='--eval mmd (KID): rows per subset, at least 2; the smaller set '
+                    'caps it (default %d)' % DEFAULT_SUBSETS[1])
+
+
+def check_subsets(ap, args):
+    """--mmd-subsets or --mmd-subset-size without --eval mmd, or out of range, is an argument error."""
+    for flag, value, lo, hi in (('--mmd-subsets', args.mmd_subsets, 1, MAX_SUBSETS), ('--mmd-subset-size', args.mmd_subset_size, 2, None)):
+        if value is not None:
+            if args.eval not in SUBSET_MODES:
+                ap.error('%s needs --eval mmd' % flag)
+            if value < lo or (hi is not None and value > hi):
+                ap.error('%s must be %s' % (flag, 'in %d..%d' % (lo, hi) if hi is not None else 'at least %d' % lo))
+
+
+def subsets_of(args):
+    """-> run_eval's `subsets`: (--mmd-subsets, --mmd-subset-size), None where a flag was not given."""
+    return (args.mmd_subsets, args.mmd_subset_size)
+
+
 def check_mode(args, cfg, visualiser):
     """The mode errors, raised before any device work and before a directory is created."""
     if args.incep_batch is not None and (not args.eval or args.incep_batch <= 0):
@@ -100,16 +127,21 @@ def make_dirs(cfg):
             os.makedirs(d)
 
 
-EVAL_METHODS = dict(zip(EVAL_MODES + PAIR_MODES + FEATURE_MODES,
-                        ('evaluate_inception', 'evaluate_fid', 'evaluate_imd', 'evaluate_swd', 'evaluate_msssim', 'evaluate_prdc')))
+EVAL_METHODS = dict(zip(EVAL_MODES + PAIR_MODES + FEATURE_MODES + SUBSET_MODES,
+                        ('evaluate_inception', 'evaluate_fid', 'evaluate_imd', 'evaluate_swd', 'evaluate_msssim', 'evaluate_prdc',
+                         'evaluate_mmd')))
 
 
-def run_eval(ev, mode, pairs=None, nearest_k=None):
+def run_eval(ev, mode, pairs=None, nearest_k=None, subsets=None):
     """The requested mode's method only, looked up by name; a pair mode takes the pairing (default random), a feature mode the k of
-    its nearest-neighbour balls (default 5)."""
+    its nearest-neighbour balls (default 5), a subset mode `subsets` = (number of subsets, rows per subset at most), None or a None
+    entry standing for the default (100, 1000)."""
     fn = getattr(ev, EVAL_METHODS[mode])
     if mode in PAIR_MODES:
         return fn(pairs=pairs or PAIRINGS[0])
     if mode in FEATURE_MODES:
         return fn(nearest_k=nearest_k or DEFAULT_NEAREST_K)
+    if mode in SUBSET_MODES:
+        n, size = subsets or (None, None)
+        return fn(num_subsets=n or DEFAULT_SUBSETS[0], max_subset_size=size or DEFAULT_SUBSETS[1])
     return fn()

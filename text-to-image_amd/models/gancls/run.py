@@ -18,7 +18,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))))
 
 import t2i_amd  # noqa: E402,F401
-from t2i_amd.models.cli import check_mode, make_dirs, make_parser, run_eval  # noqa: E402
+from t2i_amd.models.cli import check_mode, make_dirs, make_parser, run_eval, subsets_of  # noqa: E402
 from t2i_amd.utils.config import config_from_yaml  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -38,7 +38,7 @@ def main(argv=None):
         from t2i_amd.models.gancls.eval_gancls import GanClsEval
         gancls = GanCls(cfg, build_model=False)          # the evaluator creates and restores the generator's variables only
         dataset = load_dataset(cfg, gancls.device)
-        return run_eval(GanClsEval(sess=None, model=gancls, dataset=dataset, cfg=cfg, incep_batch_size=args.incep_batch), args.eval, args.msssim_pairs, args.prdc_k)
+        return run_eval(GanClsEval(sess=None, model=gancls, dataset=dataset, cfg=cfg, incep_batch_size=args.incep_batch), args.eval, args.msssim_pairs, args.prdc_k, subsets_of(args))
     if args.visualize:
         from t2i_amd.models.gancls.visualize_gancls import GanClsVisualizer
         gancls = GanCls(cfg, build_model=False)          # the visualiser creates and restores the generator's variables only

@@ -14,7 +14,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))))
 
 import t2i_amd  # noqa: E402,F401
-from t2i_amd.models.cli import check_mode, make_dirs, make_parser, run_eval  # noqa: E402
+from t2i_amd.models.cli import check_mode, make_dirs, make_parser, run_eval, subsets_of  # noqa: E402
 from t2i_amd.utils.config import config_from_yaml  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -41,7 +41,7 @@ def main(argv=None):
         from t2i_amd.models.stackgan.stageII.eval_stageii import StageIIEval
         stage_ii = ConditionalGan(stage_i, cfg, build_model=False)
         dataset = load_dataset(cfg, stage_ii.device)
-        return run_eval(StageIIEval(sess=None, model=stage_ii, dataset=dataset, cfg=cfg, incep_batch_size=args.incep_batch), args.eval, args.msssim_pairs, args.prdc_k)
+        return run_eval(StageIIEval(sess=None, model=stage_ii, dataset=dataset, cfg=cfg, incep_batch_size=args.incep_batch), args.eval, args.msssim_pairs, args.prdc_k, subsets_of(args))
     if args.visualize:
         from t2i_amd.models.stackgan.stageII.visualize_stageii import StageIIVisualizer
         stage_ii = ConditionalGan(stage_i, cfg, build_model=False)

@@ -1,7 +1,7 @@
 """Entry point of the wgancls model — reference models/wgancls/run.py:13-74.
 
-    python -m t2i_amd.models.wgancls.run --cfg <yaml> [--train | --visualize [--interp N] | --eval is|fid|swd|msssim|prdc [--incep-batch N]
-                                         [--msssim-pairs random|caption] [--prdc-k K]]
+    python -m t2i_amd.models.wgancls.run --cfg <yaml> [--train | --visualize [--interp N] | --eval is|fid|swd|msssim|prdc|mmd [--incep-batch N]
+                                         [--msssim-pairs random|caption] [--prdc-k K] [--mmd-subsets S] [--mmd-subset-size M]]
                                          [--synthetic] [--steps N] [--batch B] [--graphs 0|1]
 
 Behaviour of the reference's main(): read the config, create CHECKPOINT_DIR / SAMPLE_DIR / LOGS_DIR, load the pickled
@@ -16,7 +16,9 @@ Inception-score or FID evaluator (eval_wgan.py) whatever EVAL.FLAG says, with `-
 EVAL.INCEP_BATCH_SIZE, `--eval swd` the sliced Wasserstein distance per pyramid level (evaluation/swd.py; no Inception net) and
 `--eval msssim` the multi-scale SSIM between pairs of generated images (evaluation/msssim.py; `--msssim-pairs caption` pairs two
 images of one caption), `--eval prdc` precision, recall, density and coverage of the generated set in Inception feature space
-(evaluation/prdc.py; `--prdc-k K` nearest neighbours, default 5; needs the Inception checkpoint but not EVAL.ACT_STAT_PATH) —
+(evaluation/prdc.py; `--prdc-k K` nearest neighbours, default 5; needs the Inception checkpoint but not EVAL.ACT_STAT_PATH),
+`--eval mmd` the Kernel Inception distance (KID) of the same feature sets (evaluation/mmd.py; `--mmd-subsets S` subsets, default 100,
+of `--mmd-subset-size M` rows at most, default 1000) —
 EVAL.FLAG: True without it still raises, for the same reason; `--synthetic` replaces the pickled dataset by the on-device synthetic one
 (t2i_amd.data) for machines without the data; `--steps` / `--batch` override TRAIN.MAX_STEPS / TRAIN.BATCH_SIZE."""
 import argparse
@@ -56,12 +58,13 @@ def main(argv=None):
     mode.add_argument('--train', action='store_true', help='train even if the yml says TRAIN.FLAG: False')
     mode.add_argument('--visualize', action='store_true', help='run the caption visualiser on the latest checkpoint (needs the '
                       'pickled dataset)')
-    mode.add_argument('--eval', choices=('is', 'fid', 'swd', 'msssim', 'prdc'), default=None, help='run the Inception-score, FID, '
-                      'sliced-Wasserstein, multi-scale-SSIM or precision / recall / density / coverage evaluator on the latest checkpoint (needs the pickled dataset and, except '
+    mode.add_argument('--eval', choices=('is', 'fid', 'swd', 'msssim', 'prdc', 'mmd'), default=None, help='run the Inception-score, FID, '
+                      'sliced-Wasserstein, multi-scale-SSIM, precision / recall / density / coverage or Kernel Inception distance (mmd) evaluator on the latest checkpoint (needs the pickled dataset and, except '
                       'for swd and msssim, an Inception checkpoint in EVAL.INCEP_CHECKPOINT_DIR)')
     ap.add_argument('--incep-batch', type=int, default=None, help='--eval: Inception batch size (default EVAL.INCEP_BATCH_SIZE)')
     cli.add_pairs_argument(ap)
     cli.add_nearest_k_argument(ap)
+    cli.add_subsets_arguments(ap)
     ap.add_argument('--interp', type=int, default=0, help='--visualize: rounds of interpolation / captioned sheets (default 0)')
     ap.add_argument('--synthetic', action='store_true', help='synthetic on-device dataset instead of cfg.DATASET_DIR')
     ap.add_argument('--steps', type=int, default=None, help='override TRAIN.MAX_STEPS')
@@ -70,6 +73,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     cli.check_pairs(ap, args)
     cli.check_nearest_k(ap, args)
+    cli.check_subsets(ap, args)
     print(args.cfg)
     cfg = config_from_yaml(args.cfg)
     if args.batch:
@@ -90,7 +94,7 @@ def main(argv=None):
         wgan = WGanCls(cfg, build_model=False)           # the evaluator creates and restores the generator's variables only
         dataset = load_dataset(cfg, wgan.device)
         ev = WGanClsEval(sess=None, model=wgan, dataset=dataset, cfg=cfg, incep_batch_size=args.incep_batch)
-        return cli.run_eval(ev, args.eval, args.msssim_pairs, args.prdc_k)
+        return cli.run_eval(ev, args.eval, args.msssim_pairs, args.prdc_k, cli.subsets_of(args))
     if cfg.EVAL.FLAG:
         raise NotImplementedError('EVAL.FLAG: pass --eval is or --eval fid to run the Inception-score / FID evaluation '
                                   '(reference models/wgancls/eval_wgan.py)')
