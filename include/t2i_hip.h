@@ -857,6 +857,43 @@ int t2i_diff_augment_fwd(const float* x, const float* params, int32_t B, int32_t
 int t2i_diff_augment_adj(const float* g, const float* params, int32_t B, int32_t H, int32_t W, int32_t C, int32_t policy, float* dx,
                          void* ws, size_t ws_bytes, t2i_stream_t stream);
 
+/* ---- the parameter table drawn on the device with probability p, and p steered from the critic's outputs (Karras et al., "Training
+ * Generative Adversarial Networks with Limited Data", NeurIPS 2020).  Added within ABI v13: no existing argument list changed. --------
+ * t2i_diffaug_state: sixteen 32-bit words (64 bytes) of device memory, 16-byte aligned, written by the host once and by the two
+ * kernels afterwards:
+ *   word 0, 1   seed lo, hi (u32)                      word 7      calls (u32): observe calls since the last adjustment
+ *   word 2, 3   call counter lo, hi (u32)              word 8      last_r (f32): the statistic at the last adjustment, 0 before the first
+ *   word 4      p (f32, in [0, 1])                     word 9      updates (u32): adjustments so far
+ *   word 5      acc_sign (f32): running sum of signs   word 10-15  reserved: 0 from the host, left alone by the kernels
+ *   word 6      acc_n (f32): real logits seen
+ * t2i_diff_augment_draw writes params_out [n, 9] fp32, the table of t2i_diff_augment_fwd for H x W images, and advances the call
+ * counter by one (64-bit, the carry from word 2 into word 3 included); it writes no other word.  Row i of call k takes three blocks
+ * of Philox4x32-10 (multipliers D2511F53, CD9E8D57; Weyl constants 9E3779B9, BB67AE85; ten rounds) with key (seed lo, seed hi) and
+ * counter (i, j, k lo, k hi), j = 0 colour, 1 translation, 2 cutout.  With u(w) = float(w >> 8) * 2^-24 and below(w, m) =
+ * (uint64(w) * m) >> 32:
+ *   j = 0   b = u(w1) - 0.5f,  s = 2 u(w2),  c = u(w3) + 0.5f
+ *   j = 1   ty = below(w1, 2 r_H + 1) - r_H,  tx = below(w2, 2 r_W + 1) - r_W,  r_size = int(size / 8 + 0.5)
+ *   j = 2   offset = below(w1 | w2, size - extent % 2 + 1) - extent / 2 along y | x, extent = int(size / 2 + 0.5); the rectangle is
+ *           [max(offset, 0), min(offset + extent, size))
+ * A transform is applied to a row iff its bit is in `policy` and u(w0) of its block < p (p = 0 never, p = 1 always); otherwise its
+ * columns are the identity's (b 0, s 1, c 1, no shift, an empty rectangle), under which t2i_diff_augment_fwd returns the sample bit
+ * for bit.  Every float is one rounding of an exact value, so the stream of tables is a pure function of (seed, call, row) that any
+ * IEEE implementation reproduces bit for bit.  One launch of one workgroup, no host work: it may be captured in a graph, and every
+ * replay draws the next call's table.  1 <= n <= 65535, 1 <= H, W <= 32768; anything else, a NULL pointer, a state not aligned to
+ * 16 bytes, a table not aligned to 4 or an unknown or empty policy mask returns T2I_ERR_INVALID before anything is launched.
+ * t2i_diffaug_observe adds sum_i sign(d_real[i] - theta) to acc_sign (sign(0) = 0), n to acc_n and 1 to calls; theta = 0 under
+ * T2I_ADA_LOGIT (the publication's r_t for a critic with a logistic loss; d_fake may be NULL) and (mean d_real + mean d_fake) / 2
+ * under T2I_ADA_MIDPOINT (the same statistic for a critic whose outputs have no fixed zero).  On the call that brings calls to
+ * `interval`:  r = acc_sign / acc_n;  p <- clamp(p + sign(r - target) acc_n / ramp_images, 0, 1);  last_r <- r;  updates += 1;
+ * acc_sign, acc_n and calls <- 0.  Words 0-3 and 10-15 are not written.  One launch of one workgroup, every sum in a fixed order.
+ * A NULL state or d_real, a NULL d_fake under T2I_ADA_MIDPOINT, n outside 1..65535, an unknown mode, interval < 1, ramp_images not
+ * positive and finite, target outside (-1, 1), a state not aligned to 16 bytes or a logit vector not to 4 returns T2I_ERR_INVALID
+ * before anything is launched. */
+enum { T2I_ADA_LOGIT = 0, T2I_ADA_MIDPOINT = 1 };
+int t2i_diff_augment_draw(void* state, int32_t n, int32_t H, int32_t W, int32_t policy, float* params_out, t2i_stream_t stream);
+int t2i_diffaug_observe(void* state, const float* d_real, const float* d_fake, int32_t n, int32_t mode, float target, int32_t interval,
+                        float ramp_images, t2i_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -171,6 +171,8 @@ SIGNATURES = {
     't2i_diff_augment_workspace_bytes': (_sz, [_i32, _i32, _i32, _i32, _i32]),
     't2i_diff_augment_fwd': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),
     't2i_diff_augment_adj': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),
+    't2i_diff_augment_draw': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _p]),
+    't2i_diffaug_observe': (ctypes.c_int, [_p, _p, _p, _i32, _i32, _f, _i32, _f, _p]),
 }
 
 if not os.path.exists(LIB_PATH):

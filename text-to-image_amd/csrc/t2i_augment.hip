@@ -7,7 +7,10 @@
 // workspace in a fixed order and the apply kernels add a sample's partials themselves, in a fixed order too — two launches, no
 // join launch, no atomics.  A sample is cut into workgroups by H, W and C alone, so its result is the same bits in whatever batch
 // it sits, and calls repeat bit for bit.  Without colour each way is one launch.  The apply kernels give a thread whole pixels
-// (C = 3 is the case that matters: 12-byte pixels under arbitrary shifts, a gather per pixel).  The entry points (declared in
+// (C = 3 is the case that matters: 12-byte pixels under arbitrary shifts, a gather per pixel).  Two one-workgroup kernels feed them
+// (Karras et al., "Training Generative Adversarial Networks with Limited Data", NeurIPS 2020): aug_draw_kernel fills a table from a
+// Philox4x32-10 stream, applying each transform to a row with a probability p kept in device memory next to the seed and the call
+// counter, and aug_observe_kernel steers p from the critic's outputs on real images.  The entry points (declared in
 // include/t2i_hip.h) are at the end of this file: they validate and enqueue on the caller's stream — no allocation, no synchronisation.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -250,6 +253,129 @@ inline dim3 aug_grid(int32_t B, int32_t H, int32_t W) {
   return dim3((unsigned)(((long long)H * W + per_block - 1) / per_block), (unsigned)B);
 }
 
+// ---- the parameter table drawn on the device, and the controller of its probability p (include/t2i_hip.h: t2i_diffaug_state) ----------
+
+// Philox4x32-10 (Salmon et al., "Parallel Random Numbers: As Easy as 1, 2, 3", SC 2011): counter (c0, c1, c2, c3), key (k0, k1).
+struct Philox4 { uint32_t w[4]; };
+
+__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return Philox4{{c0, c1, c2, c3}};
+}
+
+// the top 24 bits as a float in [0, 1): the conversion and the scaling by a power of two are both exact
+__device__ __forceinline__ float aug_u01(uint32_t w) { return (float)(w >> 8) * 5.9604644775390625e-8f; }
+// a uniform integer in [0, m), m >= 1
+__device__ __forceinline__ int aug_below(uint32_t w, int m) { return (int)(((uint64_t)w * (uint32_t)m) >> 32); }
+
+// Row i of call k of the table: three Philox blocks (colour, translation, cutout) with the counter (i, block, k_lo, k_hi) and the
+// state's seed as the key.  A transform is applied iff it is in the policy and u(word 0 of its block) < p; otherwise its columns
+// are the identity's, which the apply kernels return their sample under bit for bit.  Each float below is one rounding of an exact
+// value (no product feeds a sum), so there is nothing to contract and a restatement in numpy gives the same bits.  One workgroup:
+// every thread reads words 0-4 before the barrier, thread 0 writes the advanced counter (words 2, 3, one 8-byte store) after it.
+__global__ __launch_bounds__(kThreads) void aug_draw_kernel(uint32_t* __restrict__ state, int n, int H, int W, int policy,
+                                                             float* __restrict__ P) {
+  const uint32_t k0 = state[0], k1 = state[1], klo = state[2], khi = state[3];
+  const float p = __uint_as_float(state[4]);
+  const bool col = policy & T2I_DIFFAUG_COLOR, tr = policy & T2I_DIFFAUG_TRANSLATION, cut = policy & T2I_DIFFAUG_CUTOUT;
+  const int rh = (H + 4) / 8, rw = (W + 4) / 8;                       // int(size / 8 + 0.5)
+  const int eh = (H + 1) / 2, ew = (W + 1) / 2;                       // int(size / 2 + 0.5)
+  for (int i = threadIdx.x; i < n; i += kThreads) {
+    float b = 0.f, s = 1.f, c = 1.f;
+    int ty = 0, tx = 0, y0 = 0, y1 = 0, x0 = 0, x1 = 0;
+    if (col) {
+      const Philox4 r = philox4x32_10((uint32_t)i, 0u, klo, khi, k0, k1);
+      if (aug_u01(r.w[0]) < p) {
+        b = aug_u01(r.w[1]) - 0.5f;
+        s = 2.f * aug_u01(r.w[2]);
+        c = aug_u01(r.w[3]) + 0.5f;
+      }
+    }
+    if (tr) {
+      const Philox4 r = philox4x32_10((uint32_t)i, 1u, klo, khi, k0, k1);
+      if (aug_u01(r.w[0]) < p) {
+        ty = aug_below(r.w[1], 2 * rh + 1) - rh;
+        tx = aug_below(r.w[2], 2 * rw + 1) - rw;
+      }
+    }
+    if (cut) {
+      const Philox4 r = philox4x32_10((uint32_t)i, 2u, klo, khi, k0, k1);
+      if (aug_u01(r.w[0]) < p) {
+        const int oy = aug_below(r.w[1], H - eh % 2 + 1) - eh / 2, ox = aug_below(r.w[2], W - ew % 2 + 1) - ew / 2;
+        y0 = max(oy, 0); y1 = min(oy + eh, H);
+        x0 = max(ox, 0); x1 = min(ox + ew, W);
+      }
+    }
+    float* row = P + (size_t)i * 9;
+    row[0] = b; row[1] = s; row[2] = c;
+    row[3] = (float)ty; row[4] = (float)tx;
+    row[5] = (float)y0; row[6] = (float)y1; row[7] = (float)x0; row[8] = (float)x1;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) *reinterpret_cast<uint64_t*>(state + 2) = (((uint64_t)khi << 32) | klo) + 1ull;
+}
+
+// The sum of v over the workgroup, the same bits in every thread: the wave butterfly, then the four waves added in a fixed order
+// (as aug_partial_kernel).  `slot` is 4 floats of shared memory of the caller's; two calls need two slots or a barrier between.
+__device__ __forceinline__ float aug_block_sum(float v, float* slot) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (slot[0] + slot[1]) + (slot[2] + slot[3]);
+}
+
+// The controller (Karras et al., "Training Generative Adversarial Networks with Limited Data", NeurIPS 2020, section 3): the statistic
+// r = E[sign(d_real - theta)] accumulated over `interval` calls, then p moved by acc_n / ramp towards r = target.  theta = 0
+// (T2I_ADA_LOGIT, the publication's r_t) or the midpoint of the two batch means (T2I_ADA_MIDPOINT).  One workgroup; every sum in
+// a fixed order: thread t adds elements t, t + 256, ..., then aug_block_sum.  The signs are small integers, exact in fp32.  Thread 0
+// alone writes words 4-9; words 0-3 and 10-15 are not touched.
+__global__ __launch_bounds__(kThreads) void aug_observe_kernel(uint32_t* __restrict__ state, const float* __restrict__ d_real,
+                                                                const float* __restrict__ d_fake, int n, int mode, float target,
+                                                                int interval, float ramp) {
+  __shared__ float slots[3][kThreads / 64];
+  float theta = 0.f;
+  if (mode == T2I_ADA_MIDPOINT) {
+    float sr = 0.f, sf = 0.f;
+    for (int i = threadIdx.x; i < n; i += kThreads) { sr += d_real[i]; sf += d_fake[i]; }
+    sr = aug_block_sum(sr, slots[0]);
+    sf = aug_block_sum(sf, slots[1]);
+    theta = 0.5f * (sr / (float)n + sf / (float)n);
+  }
+  float sg = 0.f;
+  for (int i = threadIdx.x; i < n; i += kThreads) {
+    const float d = d_real[i] - theta;
+    sg += d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+  }
+  sg = aug_block_sum(sg, slots[2]);
+  if (threadIdx.x != 0) return;
+  float p = __uint_as_float(state[4]);
+  float acc_sign = __uint_as_float(state[5]) + sg, acc_n = __uint_as_float(state[6]) + (float)n;
+  uint32_t calls = state[7] + 1u;
+  if (calls >= (uint32_t)interval) {
+    const float r = acc_sign / acc_n;
+    const float step = acc_n / ramp;
+    p = r > target ? p + step : (r < target ? p - step : p);
+    p = fminf(fmaxf(p, 0.f), 1.f);
+    state[4] = __float_as_uint(p);
+    state[8] = __float_as_uint(r);
+    state[9] = state[9] + 1u;
+    acc_sign = 0.f; acc_n = 0.f; calls = 0u;
+  }
+  state[5] = __float_as_uint(acc_sign);
+  state[6] = __float_as_uint(acc_n);
+  state[7] = calls;
+}
+
 }  // namespace
 }  // namespace t2i
 
@@ -300,4 +426,44 @@ int t2i_diff_augment_adj(const float* g, const float* params, int32_t B, int32_t
   else if (C == 4) hipLaunchKernelGGL(aug_adj_kernel<4>, grid, dim3(kThreads), 0, st, g, params, H, W, C, div_w, policy, part, nblk, dx);
   else hipLaunchKernelGGL(aug_adj_kernel<0>, grid, dim3(kThreads), 0, st, g, params, H, W, C, div_w, policy, part, nblk, dx);
   return launched("t2i_diff_augment_adj");
+}
+
+int t2i_diff_augment_draw(void* state, int32_t n, int32_t H, int32_t W, int32_t policy, float* params_out, t2i_stream_t stream) {
+  const int32_t all = T2I_DIFFAUG_COLOR | T2I_DIFFAUG_TRANSLATION | T2I_DIFFAUG_CUTOUT;
+  if (!state || !params_out || n < 1 || n > 65535 || H < 1 || W < 1 || H > kMaxSide || W > kMaxSide || policy <= 0 || (policy & ~all)) {
+    set_error("t2i_diff_augment_draw: bad argument (a NULL state or table, n=%d %dx%d policy=%d; 1 <= n <= 65535, 1 <= H, W <= %d, policy a "
+              "non-empty mask of T2I_DIFFAUG_*)", n, H, W, policy, kMaxSide);
+    return T2I_ERR_INVALID;
+  }
+  if ((reinterpret_cast<uintptr_t>(state) & 15) || (reinterpret_cast<uintptr_t>(params_out) & 3)) {
+    set_error("t2i_diff_augment_draw: bad argument (the state is not aligned to 16 bytes or the table not to 4)");
+    return T2I_ERR_INVALID;
+  }
+  hipLaunchKernelGGL(aug_draw_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, reinterpret_cast<uint32_t*>(state), n, H, W, policy,
+                     params_out);
+  return launched("t2i_diff_augment_draw");
+}
+
+int t2i_diffaug_observe(void* state, const float* d_real, const float* d_fake, int32_t n, int32_t mode, float target, int32_t interval,
+                        float ramp_images, t2i_stream_t stream) {
+  if (mode != T2I_ADA_LOGIT && mode != T2I_ADA_MIDPOINT) {
+    set_error("t2i_diffaug_observe: bad argument (mode=%d; T2I_ADA_LOGIT or T2I_ADA_MIDPOINT)", mode);
+    return T2I_ERR_INVALID;
+  }
+  if (!state || !d_real || (!d_fake && mode != T2I_ADA_LOGIT) || n < 1 || n > 65535) {
+    set_error("t2i_diffaug_observe: bad argument (a NULL state or d_real, a NULL d_fake under T2I_ADA_MIDPOINT, n=%d; 1 <= n <= 65535)", n);
+    return T2I_ERR_INVALID;
+  }
+  if (interval < 1 || !(ramp_images > 0.f) || !isfinite(ramp_images) || !(target > -1.f && target < 1.f)) {
+    set_error("t2i_diffaug_observe: bad argument (interval=%d ramp_images=%g target=%g; interval >= 1, ramp_images positive and finite, "
+              "-1 < target < 1)", interval, (double)ramp_images, (double)target);
+    return T2I_ERR_INVALID;
+  }
+  if ((reinterpret_cast<uintptr_t>(state) & 15) || (reinterpret_cast<uintptr_t>(d_real) & 3) || (reinterpret_cast<uintptr_t>(d_fake) & 3)) {
+    set_error("t2i_diffaug_observe: bad argument (the state is not aligned to 16 bytes or a logit vector not to 4)");
+    return T2I_ERR_INVALID;
+  }
+  hipLaunchKernelGGL(aug_observe_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, reinterpret_cast<uint32_t*>(state), d_real,
+                     mode == T2I_ADA_MIDPOINT ? d_fake : d_real, n, mode, target, interval, ramp_images);
+  return launched("t2i_diffaug_observe");
 }

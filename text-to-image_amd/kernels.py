@@ -1902,6 +1902,55 @@ def diff_augment_adj(g, P, policy):
     return dx
 
 
+ADA_LOGIT, ADA_MIDPOINT = 0, 1                                          # T2I_ADA_*: the threshold of diffaug_observe's statistic
+
+
+def _diffaug_state(state, op):
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.int32 or tuple(state.shape) != (16,) or not state.is_contiguous():
+        raise ValueError('%s: state must be a contiguous int32 tensor of 16 words (t2i_diffaug_state), got %s' % (
+            op, '%s %s' % (state.dtype, tuple(state.shape)) if isinstance(state, torch.Tensor) else type(state).__name__))
+    return state
+
+
+def diff_augment_draw(state, out, H, W, policy):
+    """Fills `out` [n, 9] with call k's parameter table of diff_augment_fwd for H x W images and advances the call counter of `state`
+    (16 int32 words on out's device: include/t2i_hip.h, t2i_diffaug_state) to k + 1.  Philox4x32-10 keyed by the state's seed; each
+    transform of `policy` is applied to a row with the state's probability p, else the row has its identity columns.  One launch, no
+    host work: capturable, and every replay draws the next table."""
+    op = 'diff_augment_draw'
+    _diffaug_state(state, op)
+    _chk(out, 'out', f32=True)
+    if out.dim() != 2 or out.shape[1] != 9 or out.device != state.device:
+        raise ValueError('%s: out must be [n, 9] on the state\'s device, got %s on %s (state on %s)' % (op, tuple(out.shape), out.device, state.device))
+    policy = int(policy)
+    if policy <= 0 or policy & ~(DIFFAUG_COLOR | DIFFAUG_TRANSLATION | DIFFAUG_CUTOUT):
+        raise ValueError('%s: policy must be a non-empty mask of DIFFAUG_COLOR | DIFFAUG_TRANSLATION | DIFFAUG_CUTOUT, got %d' % (op, policy))
+    if _live(out):
+        check(lib.t2i_diff_augment_draw(_ptr(state), out.shape[0], int(H), int(W), policy, _ptr(out), _stream()), 't2i_diff_augment_draw')
+    return out
+
+
+def diffaug_observe(state, d_real, d_fake, mode, target, interval, ramp_images):
+    """One observation of the controller of p (include/t2i_hip.h, t2i_diffaug_observe): the signs of d_real [n] against 0 (ADA_LOGIT;
+    d_fake may be None) or against the midpoint of the batch means of d_real and d_fake [n] (ADA_MIDPOINT) are added to the state's
+    accumulators, and on every `interval`-th call p moves by (logits seen) / ramp_images towards the statistic `target`.  One launch."""
+    op = 'diffaug_observe'
+    _diffaug_state(state, op)
+    _chk(d_real, 'd_real', f32=True)
+    if d_real.dim() != 1 or d_real.device != state.device:
+        raise ValueError('%s: d_real must be a vector on the state\'s device, got %s on %s' % (op, tuple(d_real.shape), d_real.device))
+    if d_fake is not None:
+        _chk(d_fake, 'd_fake', f32=True)
+        if d_fake.shape != d_real.shape or d_fake.device != state.device:
+            raise ValueError('%s: d_fake must match d_real %s on %s, got %s on %s' % (op, tuple(d_real.shape), d_real.device,
+                                                                                       tuple(d_fake.shape), d_fake.device))
+    elif mode != ADA_LOGIT:
+        raise ValueError('%s: d_fake may be None only under ADA_LOGIT' % op)
+    if _live(d_real):
+        check(lib.t2i_diffaug_observe(_ptr(state), _ptr(d_real), _ptr(d_fake), d_real.shape[0], int(mode), float(target), int(interval),
+                                      float(ramp_images), _stream()), 't2i_diffaug_observe')
+
+
 def resize_nearest(x, Ho, Wo):
     """x [B,H,W,C] -> [B,Ho,Wo,C], tf.image.resize_nearest_neighbor (align_corners=False)."""
     _chk(x, 'x', f32=True)

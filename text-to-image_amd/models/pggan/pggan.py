@@ -19,7 +19,10 @@ the layer-norm gamma / beta keep the multiplier 1.  `diffaug='color,translation,
 the critic sees, real or generated, through the differentiable augmentation T of Zhao et al. (utils.ops.diff_augment, DESIGN.md section
 4.35): the generator is trained through T, both gradient penalties are gradients of D o T, and the sampler, checkpoints, evaluators and
 summaries never see it; the parameter tables are `feed['aug_d']` [4B, 9] (rows G | x | x_mismatch | x_hat) and `feed['aug_g']` [B, 9],
-drawn when missing.  `adam_lr=L` sets Adam's step size (default None: the reference's 2e-6).  Reference specifics kept: penalty
+drawn when missing.  `diffaug_p=P` applies each transform with probability P and `diffaug_adapt=True` steers that probability from D(x) and
+D(G) at the end of the critic step; either one moves the draw of a missing table into the step, as one launch of the
+sampler's (utils.ops.DiffAugmentSampler: `diffaug_sampler`, or the model's own), which a captured graph holds; the critic step then also returns
+`Dx_logit`, `Dg_logit` and `aug_p`, all on the device.  `adam_lr=L` sets Adam's step size (default None: the reference's 2e-6).  Reference specifics kept: penalty
 coefficient 200, no kt term, G = -D_fake + 5 KL, Adam(2e-6, beta1=0, beta2=0.99) hard-coded (pggan.py:104-110; the
 `learning_rate` placeholder is fed but unused), eps of x_hat drawn in-graph (pggan.py:68 overrides the placeholder),
 `to_rgb` = k2 s1 SAME 9-channel relu conv + 1x1, every kernel He-initialised by utils/ops.py's defaults.
@@ -39,15 +42,15 @@ from ... import autograd as A
 from ... import kernels as K
 from ... import optim
 from ... import scope as S
-from ...utils.ops import (concat_tile, conv2d, diff_augment, diff_augment_params, diff_augment_policy, fc, layer_norm, lerp, lrelu_act,
-                          minibatch_stddev_stat, pixel_norm, pool, relu, upscale)
+from ...utils.ops import (DiffAugmentSampler, concat_tile, conv2d, diff_augment, diff_augment_params, diff_augment_policy, fc, layer_norm,
+                          lerp, lrelu_act, minibatch_stddev_stat, pixel_norm, pool, relu, upscale)
 
 
 class PGGAN(object):
     def __init__(self, batch_size, steps, check_dir_write, check_dir_read, dataset, sample_path, log_dir, stage, trans,
                  build_model=True, device=None, seed=0, store=None, fmap_base=1024, fmap_max=512, z_dim=128, embed_dim=1024,
                  compr_embed_dim=128, dp=None, critic_norm=None, critic_mbstd=None, g_ema=None, equalized_lr=False, adam_lr=None,
-                 diffaug=None):
+                 diffaug=None, diffaug_p=None, diffaug_adapt=False, diffaug_sampler=None):
         if diffaug is not None:
             try:
                 diff_augment_policy(diffaug, 'diffaug')
@@ -55,6 +58,20 @@ class PGGAN(object):
                 raise ValueError("diffaug must be None or a comma-separated, non-empty subset of 'color,translation,cutout' (the "
                                  "differentiable augmentation in front of the critic), got %r" % (diffaug,))
         self.diffaug = diffaug
+        if diffaug_p is not None and (isinstance(diffaug_p, bool) or not isinstance(diffaug_p, (int, float)) or not 0.0 <= diffaug_p <= 1.0):
+            raise ValueError('diffaug_p must be None or a probability in [0, 1] (each transform of diffaug is applied with it), got %r' % (diffaug_p,))
+        if not isinstance(diffaug_adapt, bool):
+            raise ValueError('diffaug_adapt must be True or False, got %r' % (diffaug_adapt,))
+        if diffaug_sampler is not None and not isinstance(diffaug_sampler, DiffAugmentSampler):
+            raise ValueError('diffaug_sampler must be None or a utils.ops.DiffAugmentSampler, got %r' % (diffaug_sampler,))
+        if diffaug is None and (diffaug_p is not None or diffaug_adapt or diffaug_sampler is not None):
+            raise ValueError('diffaug_p, diffaug_adapt and diffaug_sampler need diffaug (the policy they apply), which is None')
+        if diffaug_sampler is not None and diffaug_sampler.mask != diff_augment_policy(diffaug, 'diffaug'):
+            raise ValueError('diffaug_sampler draws for the policy %r, diffaug is %r' % (diffaug_sampler.policy, diffaug))
+        if diffaug_sampler is not None and diffaug_adapt and diffaug_sampler.adapt is None:
+            raise ValueError('diffaug_adapt=True, but the diffaug_sampler that was passed has adapt=None')
+        self.diffaug_p, self.diffaug_adapt = diffaug_p, diffaug_adapt
+        self.aug_sampler = diffaug_sampler        # (the model's own is made below, on the store's device)
         if adam_lr is not None and (isinstance(adam_lr, bool) or not isinstance(adam_lr, (int, float)) or not (math.isfinite(adam_lr) and adam_lr > 0.0)):
             raise ValueError("adam_lr must be None (the reference's 2e-6) or a finite step size > 0, got %r" % (adam_lr,))
         self.adam_lr = 0.000002 if adam_lr is None else float(adam_lr)
@@ -98,6 +115,11 @@ class PGGAN(object):
         # backward when eager, exchanged between captured graph segments under replay (same contract as models/wgancls)
         self.dp = dp
         self._capturing = False
+        if self.aug_sampler is None and (diffaug_p is not None or diffaug_adapt):
+            # device tables with probability p; adapting alone starts from p = 0 like the publication; under
+            # data parallelism each rank draws its own stream and steers its own p, as each rank draws its own table without this
+            self.aug_sampler = DiffAugmentSampler(diffaug, p=0.0 if diffaug_p is None else float(diffaug_p), seed=seed + (dp.rank if dp is not None else 0),
+                                                  device=self.device, adapt='midpoint' if diffaug_adapt else None)
         if build_model:
             self.build_model()
             self.define_losses()
@@ -166,18 +188,21 @@ class PGGAN(object):
             n = K.trunc_normal_(torch.empty_like(like))
         return n
 
-    def _aug_table(self, feed, key, rows, like):
+    def _aug_table(self, feed, key, rows, size):
         """The fed parameter table of the differentiable augmentation ([rows, 9], utils.ops.diff_augment), or a fresh draw (under data
-        parallelism each rank draws its own)."""
+        parallelism each rank draws its own): by the sampler's kernel when there is one (a launch, capturable), else by the tensor library."""
         P = feed.get(key)
-        if P is None:
-            P = diff_augment_params(rows, like.shape[1], like.shape[2], self.diffaug, device=like.device)
+        if P is None and self.aug_sampler is not None:
+            P = self.aug_sampler.draw(rows, size[0], size[1])
+        elif P is None:
+            P = diff_augment_params(rows, size[0], size[1], self.diffaug, device=self.device)
         return P
 
     def d_losses(self, feed):
         """What sess.run([D_optim, D_loss]) evaluates before the update (pggan.py:62-73,84-100).  Gradients -> d_arena."""
         x, xm, cond, z = feed['x'], feed['x_mismatch'], feed['cond'], feed['z']
         B, st, t = x.shape[0], self.stage, self.trans
+        aug = self._aug_table(feed, 'aug_d', 4 * B, x.shape[1:3]) if self.aug_sampler is not None else None      # the first launch: the sampler's call k
         eps = feed.get('eps_graph')
         if eps is None:        # tf.random_uniform([B,1,1,1]) in the graph: the fed `epsilon` placeholder is shadowed
             eps = torch.rand(B, device=x.device)
@@ -189,11 +214,11 @@ class PGGAN(object):
         # coupling is inside groups of contiguous rows whose size divides B, so no group straddles two of the three parts, and the
         # statistic of the 3B rows is bit for bit that of three B-row passes
         images = torch.cat([G, x, xm], 0)
-        aug = None
         if self.diffaug is not None:
             # every image the critic sees goes through T: rows [G | x | x_mismatch | x_hat] of one table, the 3B
             # pass as one call (a sample's result does not depend on its batch); both penalties are gradients of D o T
-            aug = self._aug_table(feed, 'aug_d', 4 * B, x)
+            if aug is None:
+                aug = self._aug_table(feed, 'aug_d', 4 * B, x.shape[1:3])
             images = diff_augment(images, aug[:3 * B], self.diffaug)
         logits = self.discriminator(images, torch.cat([cond, cond, cond], 0), reuse=True, stages=st, t=t).view(3, B)
         Dg_logit, Dx_logit, Dxmi_logit = logits[0], logits[1], logits[2]
@@ -212,15 +237,27 @@ class PGGAN(object):
             self.dp.arm(self.d_arena)           # bucketed all-reduce overlaps the rest of this backward
         D_loss.backward(inputs=list(self.d_vars.values()))
         A.side_join()
-        return dict(D_loss=D_loss.detach(), wdist=wdist.detach(), wdist2=wdist2.detach(), real_gp=real_gp.detach(),
-                    real_gp2=real_gp2.detach(), reg_loss=(Dxmi_logit.detach() ** 2).mean(), G=G, Dx_hat_logit=Dx_hat_logit.detach(),
-                    D_loss_real=D_loss_real.detach(), D_loss_fake=D_loss_fake.detach(), D_loss_mismatch=D_loss_mismatch.detach())
+        out = dict(D_loss=D_loss.detach(), wdist=wdist.detach(), wdist2=wdist2.detach(), real_gp=real_gp.detach(),
+                   real_gp2=real_gp2.detach(), reg_loss=(Dxmi_logit.detach() ** 2).mean(), G=G, Dx_hat_logit=Dx_hat_logit.detach(),
+                   D_loss_real=D_loss_real.detach(), D_loss_fake=D_loss_fake.detach(), D_loss_mismatch=D_loss_mismatch.detach())
+        if self.aug_sampler is not None:
+            # the controller sees D(x) and D(G) alone (x_mismatch and x_hat take no part): the last launch of the step; p stays on the device
+            out.update(Dx_logit=Dx_logit.detach(), Dg_logit=Dg_logit.detach())
+            if self.diffaug_adapt:
+                self.aug_sampler.observe(out['Dx_logit'], out['Dg_logit'])
+            out['aug_p'] = self.aug_sampler.p_tensor().clone()
+        return out
 
     def g_losses(self, feed):
         cond, z = feed['cond'], feed['z']
+        aug = None
+        if self.aug_sampler is not None:          # the first launch, as in d_losses: call k + 1
+            aug = self._aug_table(feed, 'aug_g', z.shape[0], (self.out_size, self.out_size))
         self._ca = self._noise(feed, 'ca_noise_g', cond[:, :self.compr_embed_dim])
         G, mean, log_sigma = self.generator(z, cond, stages=self.stage, t=self.trans, reuse=True)
-        G_seen = G if self.diffaug is None else diff_augment(G, self._aug_table(feed, 'aug_g', G.shape[0], G), self.diffaug)
+        if self.diffaug is not None and aug is None:
+            aug = self._aug_table(feed, 'aug_g', G.shape[0], G.shape[1:3])
+        G_seen = G if self.diffaug is None else diff_augment(G, aug, self.diffaug)
         with self.store.frozen('d_net'):
             Dg_logit = self.discriminator(G_seen, cond, reuse=True, stages=self.stage, t=self.trans)
         G_kl_loss = self.kl_std_normal_loss(mean, log_sigma)
@@ -256,12 +293,14 @@ class PGGAN(object):
         B, dev = feed['x'].shape[0], self.device
         feed = dict(feed)
         drawn = (('eps_graph', (B,)), ('ca_noise_d', (B, self.compr_embed_dim)), ('ca_noise_g', (B, self.compr_embed_dim)))
-        if self.diffaug is not None:          # the two parameter tables of the augmentation: static buffers, re-drawn like eps_graph
+        if self.diffaug is not None and self.aug_sampler is None:      # the two parameter tables of the augmentation: static buffers, re-drawn like eps_graph
             drawn += (('aug_d', (4 * B, 9)), ('aug_g', (B, 9)))
         for k, shape in drawn:
             if feed.get(k) is None:
                 feed[k] = torch.empty(shape, device=dev)
-        self._graphs = StepGraphs(feed, ('x', 'x_mismatch', 'cond', 'z') + tuple(k for k, _ in drawn),
+        # with a sampler the tables are drawn inside the captured bodies (one launch each); a table that is fed stays a static input
+        fed = ('aug_d', 'aug_g') if self.aug_sampler is not None else ()
+        self._graphs = StepGraphs(feed, ('x', 'x_mismatch', 'cond', 'z') + tuple(k for k, _ in drawn) + fed,
                                   filters=(self.d_arena.flat, self.g_arena.flat))
         self._redraw(feed)
         self._graphs.load(feed)
@@ -288,7 +327,7 @@ class PGGAN(object):
         for k in ('ca_noise_d', 'ca_noise_g'):
             if feed.get(k) is None or feed[k] is st[k]:
                 K.trunc_normal_(st[k])
-        if self.diffaug is not None:
+        if self.diffaug is not None and self.aug_sampler is None:
             size = st['x'].shape[1:3]
             for k in ('aug_d', 'aug_g'):
                 if feed.get(k) is None or feed[k] is st[k]:
@@ -298,6 +337,8 @@ class PGGAN(object):
         """One D update then one G update (pggan.py:196-197)."""
         self.set_alpha(float(idx) / float(self.steps))           # alpha_assign (see the module docstring)
         if self._graphs is not None:
+            if self.aug_sampler is not None and any(feed.get(k) is not None and k not in self._graphs.static for k in ('aug_d', 'aug_g')):
+                raise ValueError('a parameter table is fed, but the graphs were captured drawing it: feed aug_d / aug_g to enable_graphs too')
             self._redraw(feed)
             self._graphs.load(feed)
             self.D_optimizer.prepare(self.adam_lr)
@@ -494,6 +535,8 @@ class PGGAN(object):
                          ('reg_loss', 'reg_loss'), ('wdist', 'wdist'), ('wdist2', 'wdist2'), ('d_loss_mismatch', 'D_loss_mismatch'),
                          ('real_gp2', 'real_gp2')):
             vals.append(S.scalar(tag, float(d[key])))
+        if self.aug_sampler is not None:          # the augmentation's probability after this step, and the controller's last statistic
+            vals += [S.scalar('aug_p', float(d['aug_p'])), S.scalar('aug_r', self.aug_sampler.last_r)]
         self.writer.add_summary(vals, idx)
         self.writer.flush()
 
@@ -507,13 +550,21 @@ class PGGAN(object):
         from ...utils.utils import get_balanced_factorization, save_captions, save_images
         log = log or (lambda s: (sys.stdout.write(s + '\n'), sys.stdout.flush()))
         shadows = [self.G_optimizer] if self.g_ema is not None else None      # both savers: a transition restores the previous stage's shadows too
-        saver = Saver(self.store, var_list=self.get_variables_up_to_stage(self.stage), max_to_keep=2, shadows=shadows)
+        # the augmentation sampler's sixteen state words travel with every checkpoint (and only with a sampler: without one the files
+        # are what they were); a checkpoint written without them leaves the sampler as it is
+        words_loaded = []
+        extra = None if self.aug_sampler is None else {
+            'diffaug/state': (self.aug_sampler.state_dict, lambda w: (self.aug_sampler.load_state_dict(w), words_loaded.append(True)))}
+        saver = Saver(self.store, var_list=self.get_variables_up_to_stage(self.stage), max_to_keep=2, shadows=shadows, extra=extra)
         if side_effects and self.stage != 1:
-            src = Saver(self.store, var_list=self.get_variables_up_to_stage(self.stage - 1), shadows=shadows) if self.trans else saver
+            src = Saver(self.store, var_list=self.get_variables_up_to_stage(self.stage - 1), shadows=shadows, extra=extra) if self.trans else saver
             could_load, step = load(src, None, self.check_dir_read)
             if not could_load:
                 raise RuntimeError('Could not load previous stage during transition' if self.trans else 'Could not load current stage')
             self.restored = (self.check_dir_read, step, list(src.var_list))
+            if self.aug_sampler is not None and not words_loaded:
+                log('the checkpoint in %s carries no augmentation state: p stays %.6f, call counter %d' % (
+                    self.check_dir_read, self.aug_sampler.p, self.aug_sampler.counter))
         gen = torch.Generator(device=self.device).manual_seed(1234)
         if side_effects:
             sample_z = torch.randn((self.sample_num, self.z_dim), generator=gen, device=self.device)

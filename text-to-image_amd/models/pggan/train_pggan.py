@@ -107,6 +107,16 @@ def main(argv=None):
     ap.add_argument('--diffaug', default=None, metavar='POLICY',
                     help="differentiable augmentation of every image the critic sees (Zhao et al. 2020): a comma-separated subset of "
                          "color,translation,cutout (default: none)")
+    ap.add_argument('--diffaug-p', type=float, default=None, metavar='P',
+                    help='apply each transform of --diffaug to an image with probability P in [0, 1]; the tables are then drawn on the '
+                         'device inside the step (default: every transform on every image, tables drawn by the tensor library)')
+    ap.add_argument('--diffaug-adapt', action='store_true',
+                    help="steer that probability from the critic's outputs on real images (Karras et al. 2020, restated for a "
+                         "Wasserstein critic; starts from --diffaug-p, or 0); checkpoints carry it")
+    ap.add_argument('--diffaug-target', type=float, default=None, metavar='R', help='--diffaug-adapt: the statistic to hold, in (-1, 1) (default 0.6)')
+    ap.add_argument('--diffaug-interval', type=int, default=None, metavar='N', help='--diffaug-adapt: critic steps per adjustment (default 4)')
+    ap.add_argument('--diffaug-ramp', type=float, default=None, metavar='IMAGES',
+                    help='--diffaug-adapt: real images over which the probability can move from 0 to 1 (default 500000)')
     ap.add_argument('--lr', type=float, default=None, metavar='L', help="Adam's step size (default: the reference's hard-coded 2e-6)")
     ap.add_argument('--eager', action='store_true', help='--bench: keep eager launches instead of hipGraph replay')
     ap.add_argument('--bench', action='store_true', help='time `--iters` iterations of each entry instead of training with side effects')
@@ -125,6 +135,18 @@ def main(argv=None):
             diff_augment_policy(args.diffaug, '--diffaug')
         except ValueError as e:
             ap.error(str(e))
+    if args.diffaug is None and (args.diffaug_p is not None or args.diffaug_adapt):
+        ap.error('--diffaug-p / --diffaug-adapt need --diffaug (the policy they apply)')
+    if args.diffaug_p is not None and not 0.0 <= args.diffaug_p <= 1.0:          # (NaN fails both comparisons)
+        ap.error('--diffaug-p %r: the probability must lie in [0, 1]' % args.diffaug_p)
+    if not args.diffaug_adapt and (args.diffaug_target is not None or args.diffaug_interval is not None or args.diffaug_ramp is not None):
+        ap.error('--diffaug-target / --diffaug-interval / --diffaug-ramp are the numbers of --diffaug-adapt, which is not given')
+    if args.diffaug_target is not None and not -1.0 < args.diffaug_target < 1.0:
+        ap.error('--diffaug-target %r: the statistic lies in (-1, 1)' % args.diffaug_target)
+    if args.diffaug_interval is not None and args.diffaug_interval < 1:
+        ap.error('--diffaug-interval %r: need at least one critic step per adjustment' % args.diffaug_interval)
+    if args.diffaug_ramp is not None and not (0.0 < args.diffaug_ramp < float('inf')):
+        ap.error('--diffaug-ramp %r: the number of images must be positive and finite' % args.diffaug_ramp)
     cfg = None
     if args.cfg is not None:
         from t2i_amd.utils.config import config_from_yaml
@@ -134,6 +156,14 @@ def main(argv=None):
         check_real_run(cfg, args.first, args.last, args.bench)
     K.set_math(args.math)
     dev = torch.device('cuda')
+    aug_sampler = None
+    if args.diffaug_p is not None or args.diffaug_adapt:
+        # one sampler for the run, handed to every entry's model: p and the call counter carry over from entry to entry
+        from t2i_amd.utils.ops import DiffAugmentSampler
+        numbers = {k: v for k, v in (('target', args.diffaug_target), ('interval', args.diffaug_interval), ('ramp_images', args.diffaug_ramp))
+                   if v is not None}
+        aug_sampler = DiffAugmentSampler(args.diffaug, p=0.0 if args.diffaug_p is None else args.diffaug_p, device=dev,
+                                         adapt='midpoint' if args.diffaug_adapt else None, **numbers)
     records = []
     for i in range(args.first, args.last + 1):
         t = (i % 2 == 1)
@@ -156,7 +186,8 @@ def main(argv=None):
                       log_dir=logs_dir, stage=STAGE[i], trans=t, device=dev, critic_norm=args.critic_norm,
                       critic_mbstd=args.critic_mbstd, **({} if args.g_ema is None else {'g_ema': args.g_ema}),
                       **({'equalized_lr': True} if args.equalized_lr else {}), **({} if args.lr is None else {'adam_lr': args.lr}),
-                      **({} if args.diffaug is None else {'diffaug': args.diffaug}))
+                      **({} if args.diffaug is None else {'diffaug': args.diffaug}),
+                      **({} if aug_sampler is None else {'diffaug_sampler': aug_sampler, 'diffaug_adapt': args.diffaug_adapt}))
         if args.bench:
             gen = torch.Generator(device=dev).manual_seed(0)
             feed = pggan.make_feed(gen)

@@ -19,7 +19,8 @@ Every public name of the reference's utils/ops.py exists here with its signature
 (what a critic under the gradient penalty needs),
 like ``pool``, ``resize_nearest_neighbor``, ``gn``, ``lerp``, ``add`` and the convolutions; ``batch_norm`` / ``batch_renorm`` are first order.
 ``diff_augment`` / ``diff_augment_params`` (not in the reference either: the differentiable augmentation of Zhao et al. 2020, DESIGN.md
-section 4.35) take fp32 tensors only, with the same refusals, and are differentiable to any order.
+section 4.35) take fp32 tensors only, with the same refusals, and are differentiable to any order.  ``DiffAugmentSampler`` (DESIGN.md section
+4.39) draws those tables on the device with a probability ``p`` per transform and can steer ``p`` from a critic's outputs.
 """
 import math
 
@@ -469,6 +470,122 @@ def diff_augment_params(n, H, W, policy='color,translation,cutout', generator=No
                 out[:, col] = lo.clamp(min=0).float()
                 out[:, col + 1] = (lo + ext).clamp(max=size).float()
     return out
+
+
+class DiffAugmentSampler(object):
+    """The parameter tables of diff_augment drawn on the device, each transform applied to a row with probability p, and p optionally
+    steered from the critic's outputs (Karras et al., "Training Generative Adversarial Networks with Limited Data", NeurIPS 2020;
+    DESIGN.md section 4.39).  Owns the sixteen state words of include/t2i_hip.h (t2i_diffaug_state) on `device`: seed, call counter, p and
+    the controller's accumulators.  draw() is one launch with no host work, so it may sit in a captured graph, and the table of call k is
+    a pure function of (seed, k, row) — Philox4x32-10 — that tests restate in numpy bit for bit.
+      adapt=None        p stays what it is; observe() does nothing
+      adapt='logit'     the publication's r_t = E[sign(D(real))], for a critic with a logistic loss
+      adapt='midpoint'  the same statistic against the midpoint of the batch means of D(real) and D(fake): this project's translation to a
+                        Wasserstein critic, whose outputs have no fixed zero (not the publication's; no training run has judged it)
+    Every `interval` observations p moves by (real logits seen) / ramp_images, up when the statistic exceeds `target` and down when it
+    is below, clamped to [0, 1]; the defaults are the publication's."""
+    ADAPT = {None: None, 'logit': K.ADA_LOGIT, 'midpoint': K.ADA_MIDPOINT}
+
+    def __init__(self, policy, p=1.0, seed=0, device=None, adapt=None, target=0.6, interval=4, ramp_images=500000):
+        op = 'DiffAugmentSampler'
+        self.mask = diff_augment_policy(policy, op)
+        self.policy = policy
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0:            # (NaN fails both comparisons)
+            raise ValueError('%s: p must be a probability in [0, 1], got %r' % (op, p))
+        if isinstance(adapt, bool) or adapt not in self.ADAPT:
+            raise ValueError("%s: adapt must be None, 'midpoint' or 'logit', got %r" % (op, adapt))
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+            raise ValueError('%s: seed must be an integer in [0, 2^64), got %r' % (op, seed))
+        if isinstance(interval, bool) or not isinstance(interval, int) or interval < 1:
+            raise ValueError('%s: interval must be an integer >= 1, got %r' % (op, interval))
+        if isinstance(target, bool) or not isinstance(target, (int, float)) or not -1.0 < target < 1.0:
+            raise ValueError('%s: target must lie in (-1, 1), got %r' % (op, target))
+        if isinstance(ramp_images, bool) or not isinstance(ramp_images, (int, float)) or not (math.isfinite(ramp_images) and ramp_images > 0):
+            raise ValueError('%s: ramp_images must be positive and finite, got %r' % (op, ramp_images))
+        self.adapt, self.mode = adapt, self.ADAPT[adapt]
+        self.target, self.interval, self.ramp_images = float(target), interval, float(ramp_images)
+        if device is None:
+            device = 'cuda' if torch.cuda.is_available() else 'cpu'
+        import numpy as np
+        words = np.zeros(16, np.int64)
+        words[0], words[1] = seed & 0xffffffff, seed >> 32
+        words[4] = int(np.float32(p).view(np.uint32))
+        self.state = torch.zeros(16, dtype=torch.int32, device=torch.device(device))
+        self.device = self.state.device           # ('cuda' resolved to the current device's index: tensors are compared against it)
+        self.load_state_dict(words)
+
+    def draw(self, n, H, W, out=None):
+        """The next table [n, 9] for H x W images (into `out`, a contiguous float32 [n, 9] on the state's device, when given); the call
+        counter advances by one."""
+        op = 'DiffAugmentSampler.draw'
+        n, H, W = int(n), int(H), int(W)
+        if not (1 <= n <= 65535 and 1 <= H <= 32768 and 1 <= W <= 32768):
+            raise ValueError('%s: need 1 <= n <= 65535 and 1 <= H, W <= 32768, got %d, %d, %d' % (op, n, H, W))
+        if out is None:
+            out = torch.empty((n, 9), dtype=torch.float32, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (n, 9) or out.device != self.device
+              or not out.is_contiguous()):
+            raise ValueError('%s: out must be a contiguous float32 tensor of shape [%d, 9] on %s, got %s' % (
+                op, n, self.device, '%s %s on %s' % (out.dtype, tuple(out.shape), out.device) if isinstance(out, torch.Tensor) else type(out).__name__))
+        return K.diff_augment_draw(self.state, out, H, W, self.mask)
+
+    def _logits(self, d, name):
+        op = 'DiffAugmentSampler.observe'
+        if (not isinstance(d, torch.Tensor) or d.dtype != torch.float32 or d.dim() != 1 or not d.is_contiguous() or d.device != self.device
+                or not 1 <= d.shape[0] <= 65535):
+            raise ValueError('%s: %s must be a contiguous float32 vector of 1..65535 logits on %s, got %s' % (
+                op, name, self.device, '%s %s on %s' % (d.dtype, tuple(d.shape), d.device) if isinstance(d, torch.Tensor) else type(d).__name__))
+        return d.detach()
+
+    def observe(self, d_real, d_fake=None):
+        """One batch of critic outputs for the controller (nothing when adapt is None): d_real, and under 'midpoint' d_fake of the same
+        length.  One launch; p changes on every `interval`-th call."""
+        if self.mode is None:
+            return
+        d_real = self._logits(d_real, 'd_real')
+        if d_fake is not None or self.mode == K.ADA_MIDPOINT:
+            if d_fake is None:
+                raise ValueError("DiffAugmentSampler.observe: adapt='midpoint' needs d_fake")
+            d_fake = self._logits(d_fake, 'd_fake')
+            if d_fake.shape != d_real.shape:
+                raise ValueError('DiffAugmentSampler.observe: d_fake has %d logits, d_real %d' % (d_fake.shape[0], d_real.shape[0]))
+        K.diffaug_observe(self.state, d_real, d_fake, self.mode, self.target, self.interval, self.ramp_images)
+
+    def p_tensor(self):
+        """p as a float32 device scalar that aliases the state: no launch, no synchronisation"""
+        return self.state[4:5].view(torch.float32)[0]
+
+    def _word(self, i, as_float):
+        w = self.state[i:i + 1]
+        return float(w.view(torch.float32).cpu()[0]) if as_float else int(w.cpu()[0]) & 0xffffffff
+
+    @property
+    def p(self):
+        return self._word(4, True)
+
+    @property
+    def last_r(self):
+        return self._word(8, True)
+
+    @property
+    def updates(self):
+        return self._word(9, False)
+
+    @property
+    def counter(self):
+        return self._word(2, False) | (self._word(3, False) << 32)
+
+    def state_dict(self):
+        """The sixteen words as an int64 array of values in [0, 2^32): any checkpoint format holds them."""
+        return self.state.cpu().numpy().view('uint32').astype('int64')
+
+    def load_state_dict(self, words):
+        import numpy as np
+        words = np.asarray(words)
+        if words.shape != (16,) or words.dtype.kind not in 'iu' or bool(((words < 0) | (words > 0xffffffff)).any()):
+            raise ValueError('DiffAugmentSampler.load_state_dict: expected 16 integer words in [0, 2^32), got %s %s' % (words.dtype, words.shape))
+        with torch.no_grad():
+            self.state.copy_(torch.from_numpy(words.astype(np.uint32).view(np.int32).copy()))
 
 
 def pool(x, s=2, p_type='AVG', df=NHWC):

@@ -220,6 +220,16 @@ def main():
             m2('diff_augment_adj color,translation,cutout (2r + w)', lambda: K.diff_augment_adj(g, P, 7), back)
             m('diff_augment_fwd translation,cutout, one launch (r + w)', shape, 8 * n, lambda: K.diff_augment_fwd(x, P, 6))
 
+    # the parameter table drawn on the device: one launch of the sampler against diff_augment_params(out=) — the
+    # tensor library's fifteen or so launches — into the same buffer, at the PGGAN trainer's two table heights (4B rows, B = 16 and 64)
+    if a.only in 'diff_augment_draw' or 'diff_augment_draw' in a.only:
+        from t2i_amd.utils import ops
+        for rows, size in ((64, 16), (256, 64)):
+            out = torch.empty(rows, 9, device='cuda')
+            s = ops.DiffAugmentSampler('color,translation,cutout', p=1.0, device='cuda')
+            measure('diff_augment_draw color,translation,cutout p=1 (w)', (rows, 9), 36 * rows, lambda: s.draw(rows, size, size, out=out),
+                    a.reps, a.iters, lambda: ops.diff_augment_params(rows, size, size, out=out))
+
 
 if __name__ == '__main__':
     main()
