@@ -894,6 +894,41 @@ int t2i_diff_augment_draw(void* state, int32_t n, int32_t H, int32_t W, int32_t 
 int t2i_diffaug_observe(void* state, const float* d_real, const float* d_fake, int32_t n, int32_t mode, float target, int32_t interval,
                         float ramp_images, t2i_stream_t stream);
 
+/* ---- spectral normalisation of the matrices of an arena (Miyato et al., "Spectral Normalization for Generative Adversarial
+ * Networks", ICLR 2018).  Added within ABI v13: no existing argument list changed. ------------------------------------------------
+ * An arena of n floats (a positive multiple of 4) holds n_slots normalised matrices, 1 <= n_slots <= T2I_SPECTRAL_MAX_SLOTS.  Row s
+ * of table_dev (device int64 [n_slots, T2I_SPECTRAL_COLS], 8-byte aligned) is
+ *   (off, R, C, u_off, v_off, part_off, iterate)
+ * the row-major matrix M [R, C] at element `off` of the arena, its u [C] at u_off of `u` (nu floats), its v [R] at v_off of `v` (nv
+ * floats), its partial sums at part_off of the workspace and whether the power iteration advances it.  off, u_off and v_off are
+ * multiples of 4; the slots ascend and do not overlap; sigma is float [n_slots].  A matrix is cut into work items of
+ * rb = min(R, clamp(8192 / C, 1, 2048)) rows, ceil(R / rb) of them: max_items is the largest count of any slot and max_col_blocks
+ * the largest ceil(C / 64) (both at most T2I_SPECTRAL_MAX_ITEMS), a slot needs items * C + items + ceil(C / 64) floats of workspace at
+ * part_off (column partials, the items' |t|^2, the column blocks' |s|^2), and part_floats is the end of the last such region.  The table lives in device memory, so the entries cannot read it: THE CALLER validates its rows before the upload (the
+ * package does, in kernels.spectral_table), and a kernel forms addresses from rows that passed there.
+ * t2i_spectral_grad: grad <- (grad - <grad, flat>_s v_s u_s^T) / max(sigma_s, 1e-12) inside every slot, in place; <,>_s the sum of
+ * the slot's products, from per-item partials added in ascending order.  Elements outside the slots are left alone.  Two launches.
+ * t2i_spectral_normalize: `iterations` (0..T2I_SPECTRAL_MAX_ITERATIONS) times, for every slot with iterate != 0:
+ *   t = M u;  v = t / max(|t|, 1e-12);  s = M^T v;  sigma = |s|;  u = s / max(sigma, 1e-12)         (M read from `raw`)
+ * then flat[i] = raw[i] / max(sigma_s, 1e-12) for every element of every slot (iterate or not) and flat[i] = raw[i] elsewhere: the
+ * other variables of the arena and the padding.  3 iterations + 1 launches; treats the filter cache as t2i_adam_tf does for `flat`.
+ * Both: no floating-point atomics and every sum in a fixed order, so a call repeats bit for bit and a matrix gives the same bits
+ * whatever else its table holds; graph-capturable, no allocation, no synchronisation.  Refused with T2I_ERR_INVALID before any launch:
+ * a NULL pointer; n, nu or nv not a positive multiple of 4, nu or nv above n; n_slots, max_items, max_col_blocks or iterations out of
+ * range; part_floats < 1 or above 4 n + 8 n_slots; an arena, u, v or the workspace not 16-byte aligned, the table not 8-byte, sigma not 4-byte; a workspace smaller than
+ * t2i_spectral_workspace_bytes(part_floats) (0 for a refused count); any two of the buffers, the table and the workspace overlapping. */
+#define T2I_SPECTRAL_MAX_SLOTS 2048
+#define T2I_SPECTRAL_MAX_ITEMS (1 << 22)
+#define T2I_SPECTRAL_MAX_ITERATIONS 64
+#define T2I_SPECTRAL_COLS 7
+size_t t2i_spectral_workspace_bytes(int64_t part_floats);
+int t2i_spectral_grad(float* grad, const float* flat, int64_t n, const int64_t* table_dev, int32_t n_slots, int32_t max_items, const float* u,
+                      int64_t nu, const float* v, int64_t nv, const float* sigma, int64_t part_floats, void* ws, size_t ws_bytes,
+                      t2i_stream_t stream);
+int t2i_spectral_normalize(float* flat, const float* raw, int64_t n, const int64_t* table_dev, int32_t n_slots, int32_t max_items,
+                           int32_t max_col_blocks, float* u, int64_t nu, float* v, int64_t nv, float* sigma, int32_t iterations,
+                           int64_t part_floats, void* ws, size_t ws_bytes, t2i_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -173,6 +173,9 @@ SIGNATURES = {
     't2i_diff_augment_adj': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),
     't2i_diff_augment_draw': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _p]),
     't2i_diffaug_observe': (ctypes.c_int, [_p, _p, _p, _i32, _i32, _f, _i32, _f, _p]),
+    't2i_spectral_workspace_bytes': (_sz, [_i64]),
+    't2i_spectral_grad': (ctypes.c_int, [_p, _p, _i64, _p, _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p, _sz, _p]),
+    't2i_spectral_normalize': (ctypes.c_int, [_p, _p, _i64, _p, _i32, _i32, _i32, _p, _i64, _p, _i64, _p, _i32, _i64, _p, _sz, _p]),
 }
 
 if not os.path.exists(LIB_PATH):

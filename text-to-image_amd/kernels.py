@@ -1128,6 +1128,101 @@ def adam_tf_slots(w, g, m, v, slot_end, slot_mult, lr_t, beta1, beta2, eps=1e-8,
               't2i_adam_tf_slots')
 
 
+# ---- spectral normalisation of the matrices of an arena (csrc/t2i_spectral.hip) -----------------------------
+SPECTRAL_MAX_SLOTS, SPECTRAL_MAX_ITEMS, SPECTRAL_MAX_ITERATIONS, SPECTRAL_COLS = 2048, 1 << 22, 64, 7    # T2I_SPECTRAL_* (include/t2i_hip.h)
+
+
+def spectral_items(R, C):
+    """(rows per work item, work items) of an [R, C] matrix: the cut of csrc/t2i_spectral.hip, a function of (R, C) alone."""
+    rb = min(R, max(1, min(8192 // C, 2048)))
+    return rb, (R + rb - 1) // rb
+
+
+class SpectralTable(object):
+    """The validated slot table of spectral_grad_ / spectral_normalize: `host` the int64 rows (off, R, C, u_off, v_off, part_off,
+    iterate), `dev` their copy on the device, and the sizes the entries are told.  Made by spectral_table() only: the kernels form
+    addresses from the rows, so no row reaches the device before it passed the checks there."""
+
+    def __init__(self, host, dev, numel, nu, nv, max_items, part_floats):
+        self.host, self.dev, self.numel, self.nu, self.nv, self.max_items, self.part_floats = host, dev, numel, nu, nv, max_items, part_floats
+        self.max_col_blocks = max((int(C) + 63) // 64 for C in host[:, 2])
+        self.n_slots = int(host.shape[0])
+        self.ws_floats = (part_floats * 4 + 255) // 256 * 256 // 4          # t2i_spectral_workspace_bytes(part_floats) / 4
+
+    def only(self, rows):
+        """The same table with the power iteration advancing the given rows alone (every slot still takes part in flat = raw / sigma)."""
+        host = self.host.copy()
+        host[:, 6] = 0
+        host[list(rows), 6] = 1
+        return SpectralTable(host, torch.from_numpy(host).to(self.dev.device), self.numel, self.nu, self.nv, self.max_items, self.part_floats)
+
+
+def spectral_table(slots, numel, device):
+    """slots: one (offset, slot elements, R, C) per normalised variable in arena order; numel: the arena's size.  Lays u, v and the
+    partial sums out in 16-byte slots and validates every row: R * C equal to the slot's element count, the slots inside the arena,
+    ascending and apart, 4-element aligned."""
+    name = 'spectral_table'
+    slots = [tuple(int(x) for x in s) for s in slots]
+    if not 1 <= len(slots) <= SPECTRAL_MAX_SLOTS:
+        raise ValueError('%s: %d slots, one launch takes 1..%d' % (name, len(slots), SPECTRAL_MAX_SLOTS))
+    if numel <= 0 or numel % 4:
+        raise ValueError('%s: the arena has %d elements, not a positive multiple of 4' % (name, numel))
+    rows, uo, vo, po, prev_end, max_items = [], 0, 0, 0, 0, 1
+    for off, k, R, C in slots:
+        if R < 1 or C < 1 or R >= 1 << 30 or C >= 1 << 30 or R * C != k:
+            raise ValueError('%s: a slot of %d elements cannot be the matrix [%d, %d]' % (name, k, R, C))
+        if off % 4 or off < prev_end or off + k > numel:
+            raise ValueError('%s: the slot at %d (%d elements) is misaligned, outside the arena of %d elements, out of order or overlaps '
+                             'the slot before it (which ends at %d)' % (name, off, k, numel, prev_end))
+        prev_end = off + (k + 3) // 4 * 4
+        items = spectral_items(R, C)[1]
+        if items > SPECTRAL_MAX_ITEMS:
+            raise ValueError('%s: the matrix [%d, %d] has %d work items, a launch takes at most %d' % (name, R, C, items, SPECTRAL_MAX_ITEMS))
+        max_items = max(max_items, items)
+        rows.append((off, R, C, uo, vo, po, 1))
+        uo += (C + 3) // 4 * 4
+        vo += (R + 3) // 4 * 4
+        po += (items * C + items + (C + 63) // 64 + 3) // 4 * 4          # column partials, the items' |t|^2, the column blocks' |s|^2
+    host = np.asarray(rows, dtype=np.int64).reshape(len(rows), SPECTRAL_COLS)
+    return SpectralTable(host, torch.from_numpy(host).to(device), int(numel), uo, vo, max_items, po)
+
+
+def _spectral_chk(name, tab, arenas, u, v, sigma, ws):
+    if not isinstance(tab, SpectralTable):
+        raise TypeError('%s: the table must come from spectral_table(), got %r' % (name, type(tab).__name__))
+    for label, t in arenas + (('u', u), ('v', v), ('sigma', sigma), ('workspace', ws)):
+        _chk(t, label, f32=True)
+        if t.device != tab.dev.device:
+            raise ValueError('%s: %s is on %s, the table on %s' % (name, label, t.device, tab.dev.device))
+    for label, t in arenas:
+        if t.numel() != tab.numel:
+            raise ValueError('%s: %s has %d elements, the table was built for an arena of %d' % (name, label, t.numel(), tab.numel))
+    if u.numel() != tab.nu or v.numel() != tab.nv or sigma.numel() != tab.n_slots or ws.numel() < tab.ws_floats:
+        raise ValueError('%s: u, v, sigma and the workspace must have %d, %d, %d and at least %d elements, got %d, %d, %d and %d' % (
+            name, tab.nu, tab.nv, tab.n_slots, tab.ws_floats, u.numel(), v.numel(), sigma.numel(), ws.numel()))
+
+
+def spectral_grad_(grad, flat, tab, u, v, sigma, ws):
+    """In place on the gradient arena: inside every slot of `tab`, grad <- (grad - <grad, flat> v u^T) / sigma — the chain rule from
+    dL/dW to dL/draw of W = raw / sigma with u and v constant.  Two launches, sums in a fixed order."""
+    _spectral_chk('spectral_grad_', tab, (('grad', grad), ('flat', flat)), u, v, sigma, ws)
+    if _live(grad):
+        check(lib.t2i_spectral_grad(_ptr(grad), _ptr(flat), tab.numel, _ptr(tab.dev), tab.n_slots, tab.max_items, _ptr(u), tab.nu, _ptr(v), tab.nv,
+                                    _ptr(sigma), tab.part_floats, _ptr(ws), ws.numel() * 4, _stream()), 't2i_spectral_grad')
+
+
+def spectral_normalize(flat, raw, tab, u, v, sigma, ws, iterations=1):
+    """`iterations` power iterations on the matrices of `raw` that `tab` marks (u, v, sigma in place), then flat = raw / sigma inside
+    every slot and flat = raw elsewhere.  iterations = 0 only rewrites flat from the stored sigma.  3 * iterations + 1 launches."""
+    if isinstance(iterations, bool) or not isinstance(iterations, int) or not 0 <= iterations <= SPECTRAL_MAX_ITERATIONS:
+        raise ValueError('spectral_normalize: iterations must be an integer in 0..%d, got %r' % (SPECTRAL_MAX_ITERATIONS, iterations))
+    _spectral_chk('spectral_normalize', tab, (('flat', flat), ('raw', raw)), u, v, sigma, ws)
+    if _live(flat):
+        check(lib.t2i_spectral_normalize(_ptr(flat), _ptr(raw), tab.numel, _ptr(tab.dev), tab.n_slots, tab.max_items, tab.max_col_blocks, _ptr(u), tab.nu, _ptr(v),
+                                         tab.nv, _ptr(sigma), iterations, tab.part_floats, _ptr(ws), ws.numel() * 4, _stream()),
+              't2i_spectral_normalize')
+
+
 def device_info(device=0):
     cu, clk = ctypes.c_int32(0), ctypes.c_int32(0)
     arch = ctypes.create_string_buffer(64)

@@ -22,7 +22,10 @@ summaries never see it; the parameter tables are `feed['aug_d']` [4B, 9] (rows G
 drawn when missing.  `diffaug_p=P` applies each transform with probability P and `diffaug_adapt=True` steers that probability from D(x) and
 D(G) at the end of the critic step; either one moves the draw of a missing table into the step, as one launch of the
 sampler's (utils.ops.DiffAugmentSampler: `diffaug_sampler`, or the model's own), which a captured graph holds; the critic step then also returns
-`Dx_logit`, `Dg_logit` and `aug_p`, all on the device.  `adam_lr=L` sets Adam's step size (default None: the reference's 2e-6).  Reference specifics kept: penalty
+`Dx_logit`, `Dg_logit` and `aug_p`, all on the device.  `critic_sn=True` (default False) divides every conv2d / fc kernel of the critic by an estimate
+of its largest singular value (Miyato et al. 2018): `self.critic_spectral`, an optim.SpectralNorm, keeps the raw weights the critic's Adam steps
+and advances one power iteration per step, inside D_optimizer.apply(); the variables, and so the checkpoints and every reader, hold the
+normalised weights, and checkpoints also carry `<variable>/spectral_raw`, `_u`, `_v`, `_sigma`.  `adam_lr=L` sets Adam's step size (default None: the reference's 2e-6).  Reference specifics kept: penalty
 coefficient 200, no kt term, G = -D_fake + 5 KL, Adam(2e-6, beta1=0, beta2=0.99) hard-coded (pggan.py:104-110; the
 `learning_rate` placeholder is fed but unused), eps of x_hat drawn in-graph (pggan.py:68 overrides the placeholder),
 `to_rgb` = k2 s1 SAME 9-channel relu conv + 1x1, every kernel He-initialised by utils/ops.py's defaults.
@@ -50,7 +53,12 @@ class PGGAN(object):
     def __init__(self, batch_size, steps, check_dir_write, check_dir_read, dataset, sample_path, log_dir, stage, trans,
                  build_model=True, device=None, seed=0, store=None, fmap_base=1024, fmap_max=512, z_dim=128, embed_dim=1024,
                  compr_embed_dim=128, dp=None, critic_norm=None, critic_mbstd=None, g_ema=None, equalized_lr=False, adam_lr=None,
-                 diffaug=None, diffaug_p=None, diffaug_adapt=False, diffaug_sampler=None):
+                 diffaug=None, diffaug_p=None, diffaug_adapt=False, diffaug_sampler=None, critic_sn=False):
+        if not isinstance(critic_sn, bool):
+            raise ValueError('critic_sn must be True or False, got %r' % (critic_sn,))
+        self.critic_sn = critic_sn
+        self.critic_spectral = None
+        self.spectral_synced = None               # train(): how many normalised kernels the last restore had to sync from their weights
         if diffaug is not None:
             try:
                 diff_augment_policy(diffaug, 'diffaug')
@@ -155,9 +163,18 @@ class PGGAN(object):
     def define_losses(self):
         """pggan.py:84-130 (the optimizers; the loss expressions are in d_losses / g_losses)."""
         self.gp_coeff, self.kl_coeff = 200.0, 5.0
-        self.D_optimizer = optim.AdamTF(self.d_arena, 0.0, 0.99, slot_scales=self.kernel_scales(self.d_vars))
+        if self.critic_sn:
+            # over the kernels kernel_scales selects: every 4-D `weights` and 2-D `kernel` of the critic; the same u on every rank
+            self.critic_spectral = optim.SpectralNorm(self.d_arena, self.kernel_names(self.d_vars))
+        self.D_optimizer = optim.AdamTF(self.d_arena, 0.0, 0.99, slot_scales=self.kernel_scales(self.d_vars),
+                                        **({} if self.critic_spectral is None else {'spectral': self.critic_spectral}))
         self.G_optimizer = optim.AdamTF(self.g_arena, 0.0, 0.99, ema_decay=self.g_ema,       # (None: no shadow, the plain launch)
                                         slot_scales=self.kernel_scales(self.g_vars))
+
+    @staticmethod
+    def kernel_names(variables):
+        """The conv2d (`weights` [kh, kw, Cin, f]) and fc (`kernel` [in, units]) kernels among `variables`."""
+        return [n for n, v in variables.items() if (n.endswith('/weights') and v.dim() == 4) or (n.endswith('/kernel') and v.dim() == 2)]
 
     def kernel_scales(self, variables):
         """equalized_lr: name -> c = sqrt(2 / fan_in) for every conv2d (`weights` [kh, kw, Cin, f]) and fc (`kernel` [in, units])
@@ -555,6 +572,14 @@ class PGGAN(object):
         words_loaded = []
         extra = None if self.aug_sampler is None else {
             'diffaug/state': (self.aug_sampler.state_dict, lambda w: (self.aug_sampler.load_state_dict(w), words_loaded.append(True)))}
+        sn, sn_loaded = self.critic_spectral, {}
+        if sn is not None:
+            # the raw weights, u, v and sigma of every normalised kernel travel with every checkpoint (and only with the flag: without it
+            # the files are what they were); the variable itself is saved as the normalised weights every other reader expects
+            extra = dict(extra or {})
+            for n in sn.names:
+                for key in sn.keys(n):
+                    extra[key] = ((lambda key=key: sn.state_tensor(key).numpy()), (lambda a, key=key: sn_loaded.__setitem__(key, a)))
         saver = Saver(self.store, var_list=self.get_variables_up_to_stage(self.stage), max_to_keep=2, shadows=shadows, extra=extra)
         if side_effects and self.stage != 1:
             src = Saver(self.store, var_list=self.get_variables_up_to_stage(self.stage - 1), shadows=shadows, extra=extra) if self.trans else saver
@@ -562,6 +587,16 @@ class PGGAN(object):
             if not could_load:
                 raise RuntimeError('Could not load previous stage during transition' if self.trans else 'Could not load current stage')
             self.restored = (self.check_dir_read, step, list(src.var_list))
+            if sn is not None:
+                # a kernel that was restored and whose four keys the file holds is restored verbatim; every other one starts from the
+                # weights it has now (a checkpoint trained without the flag, a variable new at this stage)
+                whole = [n for n in sn.names if src._is_selected(n) and all(k in sn_loaded for k in sn.keys(n))]
+                sn.load_state_dict({k: sn_loaded[k] for n in whole for k in sn.keys(n)})
+                synced = [n for n in sn.names if n not in set(whole)]
+                sn.sync(synced)
+                self.spectral_synced = len(synced)
+                log('spectral normalisation: %d of %d kernels restored with their state, %d synced from their weights' % (
+                    len(whole), len(sn.names), len(synced)))
             if self.aug_sampler is not None and not words_loaded:
                 log('the checkpoint in %s carries no augmentation state: p stays %.6f, call counter %d' % (
                     self.check_dir_read, self.aug_sampler.p, self.aug_sampler.counter))

@@ -104,6 +104,9 @@ def main(argv=None):
                     help="the paper's equalized learning rate: kernels drawn from N(0, 2 / fan_in) and stepped by Adam as c * w-hat with "
                          "w-hat ~ N(0, 1), c = sqrt(2 / fan_in), through per-slot multipliers in the Adam launch (default: the reference's "
                          "He initialisation and plain Adam)")
+    ap.add_argument('--critic-sn', action='store_true',
+                    help="spectral normalisation of the critic's conv and dense kernels (Miyato et al. 2018): one power iteration per "
+                         "critic step next to the Adam launch; checkpoints carry the raw weights, u, v and sigma (default: none)")
     ap.add_argument('--diffaug', default=None, metavar='POLICY',
                     help="differentiable augmentation of every image the critic sees (Zhao et al. 2020): a comma-separated subset of "
                          "color,translation,cutout (default: none)")
@@ -186,6 +189,7 @@ def main(argv=None):
                       log_dir=logs_dir, stage=STAGE[i], trans=t, device=dev, critic_norm=args.critic_norm,
                       critic_mbstd=args.critic_mbstd, **({} if args.g_ema is None else {'g_ema': args.g_ema}),
                       **({'equalized_lr': True} if args.equalized_lr else {}), **({} if args.lr is None else {'adam_lr': args.lr}),
+                      **({'critic_sn': True} if args.critic_sn else {}),
                       **({} if args.diffaug is None else {'diffaug': args.diffaug}),
                       **({} if aug_sampler is None else {'diffaug_sampler': aug_sampler, 'diffaug_adapt': args.diffaug_adapt}))
         if args.bench:

@@ -120,6 +120,142 @@ class Arena(object):
         return self.grad[o:o + k].view(self.vars[name].shape)
 
 
+class SpectralNorm(object):
+    """Spectral normalisation of named variables of an arena (Miyato et al., ICLR 2018).  A variable of shape
+    [..., C] is the matrix M [R, C], C its last dimension.  The object owns `raw` (the weights the optimizer steps; a clone of
+    arena.flat), per variable u [C], v [R] and sigma, and the slot table of csrc/t2i_spectral.hip; arena.flat holds W = raw / sigma
+    for the named variables and raw for the others, so every reader of the arena sees normalised weights.
+    u is drawn N(0, 1) from `seed` on the CPU and normalised — the same on every data-parallel rank (no rank offset).  Construction
+    runs `warmup` power iterations, rewrites arena.flat and drops the cached filter images.
+    normalize(iterations) and grad_() wrap the two entries; AdamTF(spectral=...) calls them around its launch.  sync(names) is for a
+    restore behind the optimizer's back: raw <- flat for those slots, then `warmup` iterations from the u it has."""
+
+    SUFFIXES = ('raw', 'u', 'v', 'sigma')
+
+    def __init__(self, arena, names, seed=0, warmup=15):
+        names = list(names)
+        for n in names:
+            if n not in arena.offsets:
+                raise KeyError('SpectralNorm names %r, which is not a variable of this arena' % (n,))
+            if arena.vars[n].dim() < 2:
+                raise ValueError('SpectralNorm: %r has shape %s; a normalised variable has at least 2 dimensions' % (n, tuple(arena.vars[n].shape)))
+        if len(set(names)) != len(names):
+            raise ValueError('SpectralNorm: a variable is named twice')
+        if not names:
+            raise ValueError('SpectralNorm: no variable named')
+        if isinstance(warmup, bool) or not isinstance(warmup, int) or warmup < 0:
+            raise ValueError('SpectralNorm: warmup must be an integer >= 0, got %r' % (warmup,))
+        self.arena, self.warmup, self.seed = arena, warmup, seed
+        self.names = [n for n in arena.names if n in set(names)]          # arena order: the table ascends
+        slots = []
+        for n in self.names:
+            o, k = arena.offsets[n]
+            C = int(arena.vars[n].shape[-1])
+            slots.append((o, k, k // max(C, 1), C))
+        dev = arena.flat.device
+        self.table = K.spectral_table(slots, arena.numel, dev)
+        self.index = {n: i for i, n in enumerate(self.names)}
+        gen = torch.Generator().manual_seed(int(seed))
+        u = torch.zeros(self.table.nu, dtype=torch.float32)
+        for row in self.table.host:
+            C, uo = int(row[2]), int(row[3])
+            d = torch.randn(C, generator=gen, dtype=torch.float32)
+            u[uo:uo + C] = d / max(float(d.norm()), 1e-12)
+        self.u = u.to(dev)
+        self.v = torch.zeros(self.table.nv, dtype=torch.float32, device=dev)
+        self.sigma = torch.ones(self.table.n_slots, dtype=torch.float32, device=dev)
+        self.ws = torch.zeros(self.table.ws_floats, dtype=torch.float32, device=dev)
+        self.raw = arena.flat.detach().clone()
+        self.normalize(warmup)
+        K.filter_cache_invalidate()
+
+    def normalize(self, iterations=1, table=None):
+        """`iterations` power iterations on raw, then arena.flat = raw / sigma (named slots) | raw (the others)."""
+        if isinstance(iterations, bool) or not isinstance(iterations, int) or iterations < 0:
+            raise ValueError('SpectralNorm.normalize: iterations must be an integer >= 0, got %r' % (iterations,))
+        table = self.table if table is None else table
+        while True:
+            k = min(iterations, K.SPECTRAL_MAX_ITERATIONS)
+            K.spectral_normalize(self.arena.flat, self.raw, table, self.u, self.v, self.sigma, self.ws, iterations=k)
+            iterations -= k
+            if iterations == 0:
+                return
+
+    def grad_(self):
+        """arena.grad, in place: dL/dW -> dL/draw inside the named slots, with the u, v, sigma that produced the current arena.flat."""
+        K.spectral_grad_(self.arena.grad, self.arena.flat, self.table, self.u, self.v, self.sigma, self.ws)
+
+    def sync(self, names=None):
+        """After the arena's variables were written behind the optimizer's back (a restore): raw <- flat for the named slots (None:
+        all of them) and for every variable that is not normalised (raw is all the state those have), then `warmup` iterations on the
+        named slots from the u they have.  The other normalised slots keep raw, u, v and sigma bit for bit.  With a slot named,
+        arena.flat is rewritten and the cached filter images are dropped."""
+        names = list(self.names if names is None else names)
+        for n in names:
+            if n not in self.index:
+                raise KeyError('SpectralNorm.sync names %r, which is not normalised here' % (n,))
+        with torch.no_grad():
+            for n in [n for n in self.arena.names if n not in self.index] + names:
+                o, k = self.arena.offsets[n]
+                self.raw[o:o + k].copy_(self.arena.flat[o:o + k])
+            for n in names:
+                self.sigma[self.index[n]] = 1.0
+        if not names:
+            return
+        self.normalize(self.warmup, table=self.table.only([self.index[n] for n in names]))
+        K.filter_cache_invalidate()
+
+    def _views(self, n):
+        i = self.index[n]
+        o, k = self.arena.offsets[n]
+        _, R, C, uo, vo = (int(x) for x in self.table.host[i][:5])
+        return self.raw[o:o + k].view(self.arena.vars[n].shape), self.u[uo:uo + C], self.v[vo:vo + R], self.sigma[i:i + 1]
+
+    @classmethod
+    def keys(cls, name):
+        """The four state keys of a variable: `<variable>/spectral_raw`, `_u`, `_v`, `_sigma`."""
+        return tuple('%s/spectral_%s' % (name, s) for s in cls.SUFFIXES)
+
+    def state_tensor(self, key):
+        """One tensor of state_dict(), copied to the CPU on its own."""
+        var, _, tail = key.rpartition('/spectral_')
+        if var not in self.index or tail not in self.SUFFIXES:
+            raise KeyError('SpectralNorm.state_tensor: %r is not a state key of a variable normalised here' % (key,))
+        return self._views(var)[self.SUFFIXES.index(tail)].detach().cpu().clone()
+
+    def state_dict(self):
+        """key -> CPU tensor, for every normalised variable its raw weights, u, v and sigma ([1])."""
+        out = OrderedDict()
+        for n in self.names:
+            for key, t in zip(self.keys(n), self._views(n)):
+                out[key] = t.detach().cpu().clone()
+        return out
+
+    def load_state_dict(self, state):
+        """Verbatim: the four tensors of every variable `state` holds are copied in; nothing is launched that changes them, and
+        arena.flat is not touched (a checkpoint carries the normalised weights as the variable itself).  A variable with some of its
+        four keys missing, or a key of a variable not normalised here, is a KeyError; a wrong shape a ValueError."""
+        state = dict(state)
+        named = set()
+        for key in state:
+            var, _, tail = key.rpartition('/spectral_')
+            if var not in self.index or tail not in self.SUFFIXES:
+                raise KeyError('SpectralNorm.load_state_dict: %r is not a state key of a variable normalised here' % (key,))
+            named.add(var)
+        with torch.no_grad():
+            for n in self.names:
+                if n not in named:
+                    continue
+                for key, t in zip(self.keys(n), self._views(n)):
+                    if key not in state:
+                        raise KeyError('SpectralNorm.load_state_dict: %s is missing (a variable is restored from all four of its keys)' % key)
+                    src = torch.as_tensor(state[key]).to(torch.float32)
+                    if src.numel() != t.numel() or (src.dim() > 1 and tuple(src.shape) != tuple(t.shape)):
+                        raise ValueError('SpectralNorm.load_state_dict: %s has shape %s, expected %s' % (key, tuple(src.shape), tuple(t.shape)))
+                for key, t in zip(self.keys(n), self._views(n)):
+                    t.copy_(torch.as_tensor(state[key]).to(torch.float32).reshape(t.shape).to(t.device))
+
+
 class AdamTF(object):
     """lr_t = lr*sqrt(1-b2^t)/(1-b1^t); m,v updates; w -= lr_t*m/(sqrt(v)+eps) — epsilon OUTSIDE the bias correction
     (SURVEY.md §8a M5).  With beta1=0, t=1 this is ~lr*sign(g).
@@ -130,12 +266,26 @@ class AdamTF(object):
     slot_scales (default None: the plain launches, nothing allocated): a mapping variable name -> c or -> (grad_mult, lr_mult); the
     variable then steps with its gradient times grad_mult and its step size times lr_mult, in one launch over the arena
     (t2i_adam_tf_slots).  Variables not named keep (1, 1).  c for both is the equalized learning rate: Adam on
-    w-hat ~ N(0, 1) used as w = c * w-hat, restated on w itself; (1, k) is a per-layer learning-rate multiplier."""
+    w-hat ~ N(0, 1) used as w = c * w-hat, restated on w itself; (1, k) is a per-layer learning-rate multiplier.
+    spectral (default None: today's code path and launches): a SpectralNorm over this arena.  apply() then (1) turns the gradients of
+    the normalised slots into gradients of the raw weights, in place in arena.grad, (2) runs the same Adam launch on spectral.raw in
+    place of arena.flat, (3) advances the power iteration by one step on the new raw and (4) rewrites arena.flat: six launches
+    beyond Adam's.  AFTER apply() arena.grad HOLDS THE TRANSFORMED GRADIENT, so the on-demand first moment of
+    beta1 == 0 is the moment of raw, the one the step used.  slot_scales combine with it (the multipliers act on the step of raw);
+    ema_decay does not (ValueError: critic only)."""
 
     ema = None
     slot_end = slot_mult = slot_scales = None
 
-    def __init__(self, arena, beta1=0.9, beta2=0.999, eps=1e-8, ema_decay=None, slot_scales=None):
+    spectral = None
+
+    def __init__(self, arena, beta1=0.9, beta2=0.999, eps=1e-8, ema_decay=None, slot_scales=None, spectral=None):
+        if spectral is not None:
+            if not isinstance(spectral, SpectralNorm) or spectral.arena is not arena:
+                raise ValueError('spectral must be None or a SpectralNorm over this optimizer\'s arena, got %r' % (spectral,))
+            if ema_decay is not None:
+                raise ValueError('spectral and ema_decay do not combine: the moving average is the generator\'s, spectral normalisation the critic\'s')
+            self.spectral = spectral
         if ema_decay is not None:
             if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 < ema_decay < 1.0:
                 raise ValueError('ema_decay must be None or a number in (0, 1), got %r' % (ema_decay,))
@@ -262,7 +412,13 @@ class AdamTF(object):
         if self.slot_end is not None:
             kw.update(slot_end=self.slot_end, slot_mult=self.slot_mult)
         launch = K.adam_tf_slots if self.slot_end is not None else K.adam_tf if self.ema is None else K.adam_tf_ema
-        launch(self.arena.flat, self.arena.grad, None if self.skip_m else self._m, self.v, **kw)
+        if self.spectral is not None:
+            # dL/dW -> dL/draw in the gradient arena, Adam on the raw weights, one power iteration on the new raw, arena.flat rewritten
+            self.spectral.grad_()
+            launch(self.spectral.raw, self.arena.grad, None if self.skip_m else self._m, self.v, **kw)
+            self.spectral.normalize(1)
+        else:
+            launch(self.arena.flat, self.arena.grad, None if self.skip_m else self._m, self.v, **kw)
         if self.skip_m:
             self._last_scale = float(grad_scale)
             self._m_stale = True             # (an eager zero_grad between prepare() and here has formed the PREVIOUS step's moment)

@@ -3,7 +3,7 @@
 gn, the double backward of pixel_norm and layer_norm, the minibatch standard deviation) at PGGAN-sized tensors, and the Adam launch with and
 without the weight EMA (`--only adam_ema`) and with per-slot multipliers (`--only adam_slots`) at the sizes of two generator arenas, and the
 differentiable augmentation of csrc/t2i_augment.hip at the PGGAN trainer's shapes next to the same policy from tensor-library calls
-(`--only diff_augment`): one JSON line per kernel with the time per call, the bytes the algorithm moves (reads + writes, from the
+(`--only diff_augment`), and the critic's optimizer step with and without spectral normalisation (`--only spectral_norm`): one JSON line per kernel with the time per call, the bytes the algorithm moves (reads + writes, from the
 shapes), bytes per second, and the ratio of that rate to a device-to-device copy that moves the SAME number of bytes (half read, half
 written), timed in the same process.  Per measurement: 10 warm-up launches, then REPS rounds of 100 back-to-back launches between
 device events, kernel and copy rounds alternating; the median round is reported.  Read the ratio, not the absolute rate, as the share
@@ -229,6 +229,31 @@ def main():
             s = ops.DiffAugmentSampler('color,translation,cutout', p=1.0, device='cuda')
             measure('diff_augment_draw color,translation,cutout p=1 (w)', (rows, 9), 36 * rows, lambda: s.draw(rows, size, size, out=out),
                     a.reps, a.iters, lambda: ops.diff_augment_params(rows, size, size, out=out))
+
+    # spectral normalisation in the critic's optimizer step at the critic arenas of PGGAN stages 3 and 7:
+    # AdamTF.apply() as it is (one launch, 3r + 2w), with spectral= (the gradient transform, Adam on raw, one power iteration and the
+    # rewrite of the arena: seven launches) and the six extra launches alone.  Bytes, per element of a normalised slot (nearly the whole
+    # arena): the dot pass reads G and W, the correction reads and writes G, the row pass reads raw (its second pass over an item is served
+    # from cache), the rewrite reads raw and writes the arena: 7 more streams, 28 bytes.  The filter cache is left out (refresh=False).
+    # The gradient arena is transformed in place call after call, so its values drift towards 0: no kernel here takes a value-dependent path.
+    if a.only and a.only in 'spectral_norm':
+        from t2i_amd import optim
+        from t2i_amd.models.pggan.pggan import PGGAN
+        for stage, batch in ((3, 16), (7, 8)):
+            pg = PGGAN(batch, 100, None, None, None, None, None, stage, False, device=torch.device('cuda'))
+            arena = pg.d_arena
+            names = pg.kernel_names(pg.d_vars)
+            sn = optim.SpectralNorm(arena, names)
+            plain, spec = optim.AdamTF(arena, 0.0, 0.99), optim.AdamTF(arena, 0.0, 0.99, spectral=sn)
+            arena.grad.normal_()
+            for o in (plain, spec):
+                o.prepare(2e-6)
+            n = arena.numel
+            tag = 'pggan stage %d d_arena, %d of %d variables normalised' % (stage, len(names), len(arena.names))
+            m('spectral_norm: AdamTF.apply(), %s (3r + 2w)' % tag, (n,), 20 * n, lambda: plain.apply(refresh=False))
+            m('spectral_norm: AdamTF(spectral=).apply(), 7 launches, %s (8r + 4w)' % tag, (n,), 48 * n, lambda: spec.apply(refresh=False))
+            m('spectral_norm: grad_() + normalize(1) alone, 6 launches, %s (5r + 2w)' % tag, (n,), 28 * n, lambda: (sn.grad_(), sn.normalize(1)))
+            del pg, arena, sn, plain, spec
 
 
 if __name__ == '__main__':
