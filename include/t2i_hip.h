@@ -929,6 +929,33 @@ int t2i_spectral_normalize(float* flat, const float* raw, int64_t n, const int64
                            int32_t max_col_blocks, float* u, int64_t nu, float* v, int64_t nv, float* sigma, int32_t iterations,
                            int64_t part_floats, void* ws, size_t ws_bytes, t2i_stream_t stream);
 
+/* ---- anti-aliased resampling: upsample by zero insertion, pad or crop, FIR filter, decimate (the upfirdn2d of Karras et al., "A
+ * Style-Based Generator Architecture for Generative Adversarial Networks", CVPR 2019, with the taps of Zhang, "Making Convolutional
+ * Networks Shift-Invariant Again", ICML 2019).  Added within ABI v13: no existing argument list changed. ---------------------------------
+ * x [B,H,W,C] -> y [B,Ho,Wo,C], contiguous NHWC fp32.  taps: n floats in HOST memory, 1 <= n <= T2I_UPFIRDN_MAX_TAPS, read during the
+ * call and used on both axes; u, d in {1, 2}; the pads p0 (front) and p1 (back) may be negative, which crops.  Per axis, with
+ * z[j] = x[j / u] where 0 <= j < H u and u divides j, else 0:
+ *   Ho = floor((H u + p0 + p1 - n) / d) + 1 = t2i_upfirdn2d_extent(H, u, d, p0, p1, n)        (0 for a refused shape)
+ *   y[o] = sum_{t = 0}^{n - 1} g[n - 1 - t] z[o d + t - p0],     g = taps, or taps reversed when flip != 0
+ * a true convolution.  The adjoint for an input of extent H and output extent Ho is the same entry on [B,Ho,Wo,C] with
+ *   u' = d, d' = u, p0' = n - 1 - p0, p1' = H u - Ho d + p0 - u + 1, flip' = !flip
+ * and returns extent H exactly.  One launch; both axes in it, the input window of a T2I_UPFIRDN_TILE x T2I_UPFIRDN_TILE output tile staged
+ * once in LDS; with u = 2 only the taps that meet a stored sample are read (the inserted zeros exist nowhere).  A 16-byte form when
+ * C % 4 == 0 and x, y are 16-byte aligned, a scalar form otherwise.  An output is sum_t w_t (sum_s w_s x), both sums by fma in
+ * ascending tap order: no atomics, calls repeat bit for bit, a sample's bits do not depend on its batch.  The taps travel as kernel
+ * arguments: graph-capturable, no device table, no allocation, no synchronisation.  Refused with T2I_ERR_INVALID before any launch: a
+ * NULL pointer; a size < 1; n outside 1..8; u or d outside {1, 2}; |p0| or |p1| above 32768; an extent < 1; x or y of 2^31 elements or
+ * more; x and y overlapping; a tap that is not finite. */
+#define T2I_UPFIRDN_TILE 8
+#define T2I_UPFIRDN_MAX_TAPS 8
+int32_t t2i_upfirdn2d_extent(int32_t H, int32_t u, int32_t d, int32_t p0, int32_t p1, int32_t n);
+int t2i_upfirdn2d(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, const float* taps, int32_t n, int32_t u, int32_t d,
+                  int32_t p0, int32_t p1, int32_t flip, float* y, t2i_stream_t stream);
+/* The same with a back pad per axis, p1_h along H and p1_w along W (t2i_upfirdn2d passes p1 for both): where d = 2 and H and W leave
+ * different remainders, the adjoint's p1' differs between the axes by one. */
+int t2i_upfirdn2d_axes(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, const float* taps, int32_t n, int32_t u, int32_t d,
+                       int32_t p0, int32_t p1_h, int32_t p1_w, int32_t flip, float* y, t2i_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

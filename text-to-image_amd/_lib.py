@@ -176,6 +176,9 @@ SIGNATURES = {
     't2i_spectral_workspace_bytes': (_sz, [_i64]),
     't2i_spectral_grad': (ctypes.c_int, [_p, _p, _i64, _p, _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p, _sz, _p]),
     't2i_spectral_normalize': (ctypes.c_int, [_p, _p, _i64, _p, _i32, _i32, _i32, _p, _i64, _p, _i64, _p, _i32, _i64, _p, _sz, _p]),
+    't2i_upfirdn2d_extent': (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    't2i_upfirdn2d': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p]),
+    't2i_upfirdn2d_axes': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p]),
 }
 
 if not os.path.exists(LIB_PATH):

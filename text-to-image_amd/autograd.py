@@ -902,6 +902,29 @@ class DiffAugmentAdjFn(Function):
         return DiffAugmentFn.apply(gg, P, ctx.policy, False), None, None
 
 
+class UpFirDn2dFn(Function):
+    """Anti-aliased resampling: zero insertion by u, pads (p0, p1), FIR filter with the host floats `taps`
+    (reversed when flip), decimation by d, along H and W of [B,H,W,C].  Linear, and its adjoint is the same operator with
+    K.upfirdn2d_adjoint's parameters: the backward applies this Function itself, so it is differentiable to any order with one kernel
+    family (usable under the gradient penalty).  p1 is a pair (along H, along W).  No gradient flows to the taps."""
+
+    @staticmethod
+    def forward(ctx, x, taps, u, d, p0, p1, flip):
+        ctx.args = (taps, u, d, p0, flip)
+        ctx.hw = (x.shape[1], x.shape[2])
+        ctx.set_materialize_grads(False)
+        return K.upfirdn2d(_c(x), taps, u, d, p0, p1, flip)
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None, None, None, None
+        taps, u, d, p0, flip = ctx.args
+        ua, da, p0a, p1h, fa = K.upfirdn2d_adjoint(ctx.hw[0], g.shape[1], len(taps), u, d, p0, flip)
+        p1w = K.upfirdn2d_adjoint(ctx.hw[1], g.shape[2], len(taps), u, d, p0, flip)[3]
+        return UpFirDn2dFn.apply(g, taps, ua, da, p0a, (p1h, p1w), fa), None, None, None, None, None, None
+
+
 class PoolAvgFn(Function):
     """tf.nn.pool AVG, window = stride = s, SAME, any extents (the mean of the taps inside the image).  Linear; adjoint: PoolAvgAdjFn."""
 

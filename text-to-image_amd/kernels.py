@@ -2127,6 +2127,71 @@ def mul(a, b):
     return y
 
 
+# anti-aliased resampling (csrc/t2i_resample.hip)
+UPFIRDN_TILE, UPFIRDN_MAX_TAPS, UPFIRDN_MAX_PAD = 8, 8, 32768          # T2I_UPFIRDN_TILE / _MAX_TAPS (include/t2i_hip.h): outputs per tile and axis
+
+
+def upfirdn2d_extent(H, u, d, p0, p1, n):
+    """floor((H u + p0 + p1 - n) / d) + 1, the output extent of upfirdn2d along an axis of extent H; 0 for anything the entry refuses."""
+    args = (H, u, d, p0, p1, n)
+    if any(isinstance(a, bool) or int(a) != a or abs(int(a)) >= 1 << 31 for a in args):
+        return 0
+    return int(lib.t2i_upfirdn2d_extent(*(int(a) for a in args)))
+
+
+def upfirdn2d_adjoint(H, Ho, n, u, d, p0, flip):
+    """(u', d', p0', p1', flip') of the adjoint of an upfirdn2d that took extent H to Ho: the same operator, returning H exactly."""
+    return d, u, n - 1 - p0, H * u - Ho * d + p0 - u + 1, not flip
+
+
+def upfirdn2d(x, taps, u, d, p0, p1, flip, out=None):
+    """x [B,H,W,C] -> y [B,Ho,Wo,C]: insert u - 1 zeros after every sample, pad by p0 in front and p1 behind (negative: crop), convolve
+    with `taps` (n host floats, reversed first when flip) and keep every d-th sample, along H and W (include/t2i_hip.h,
+    t2i_upfirdn2d).  p1 is an integer or a pair (along H, along W): the adjoint of a decimation needs one per axis when H and W leave
+    different remainders.  One launch; `out` ([B,Ho,Wo,C] float32, not overlapping x) is written in place when given."""
+    op = 'upfirdn2d'
+    _chk(x, 'x', f32=True)
+    if x.dim() != 4 or min(x.shape) < 1:
+        raise ValueError('%s: x must be [B,H,W,C] with every size at least 1, got %s' % (op, tuple(x.shape)))
+    try:
+        taps = [float(t) for t in taps]
+    except (TypeError, ValueError):
+        raise ValueError('%s: taps must be a sequence of numbers, got %r' % (op, taps))
+    n = len(taps)
+    if not 1 <= n <= UPFIRDN_MAX_TAPS:
+        raise ValueError('%s: %d taps, the kernel takes 1..%d' % (op, n, UPFIRDN_MAX_TAPS))
+    w = np.asarray(taps, dtype=np.float32)
+    if not np.isfinite(w).all():
+        raise ValueError('%s: the taps must be finite in float32, got %r' % (op, taps))
+    p1h, p1w = (p1, p1) if not isinstance(p1, (tuple, list)) else p1
+    for label, v in (('u', u), ('d', d), ('p0', p0), ('p1', p1h), ('p1', p1w)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError('%s: %s must be an integer, got %r' % (op, label, v))
+    if u not in (1, 2) or d not in (1, 2):
+        raise ValueError('%s: the factors must be 1 or 2, got up %d and down %d' % (op, u, d))
+    if max(abs(p0), abs(p1h), abs(p1w)) > UPFIRDN_MAX_PAD:
+        raise ValueError('%s: pads (%d, %d / %d) exceed %d in magnitude' % (op, p0, p1h, p1w, UPFIRDN_MAX_PAD))
+    B, H, W, C = x.shape
+    Ho, Wo = upfirdn2d_extent(H, u, d, p0, p1h, n), upfirdn2d_extent(W, u, d, p0, p1w, n)
+    if Ho < 1 or Wo < 1:
+        raise ValueError('%s: a %dx%d map with up %d, down %d, pads (%d, %d / %d) and %d taps has no output' % (op, H, W, u, d, p0, p1h, p1w, n))
+    if x.numel() >= 1 << 31 or B * Ho * Wo * C >= 1 << 31:
+        raise ValueError('%s: x %s or y %s has 2^31 elements or more' % (op, tuple(x.shape), (B, Ho, Wo, C)))
+    if out is None:
+        out = torch.empty((B, Ho, Wo, C), dtype=torch.float32, device=x.device)
+    else:
+        _chk(out, 'out', f32=True)
+        if tuple(out.shape) != (B, Ho, Wo, C) or out.device != x.device:
+            raise ValueError('%s: out must be %s on %s, got %s on %s' % (op, (B, Ho, Wo, C), x.device, tuple(out.shape), out.device))
+        x0, y0 = x.data_ptr(), out.data_ptr()
+        if x0 < y0 + out.numel() * 4 and y0 < x0 + x.numel() * 4:
+            raise ValueError('%s: out overlaps x' % op)
+    if _live(x):
+        check(lib.t2i_upfirdn2d_axes(_ptr(x), B, H, W, C, w.ctypes.data_as(ctypes.c_void_p), n, int(u), int(d), int(p0), int(p1h), int(p1w),
+                                     1 if flip else 0, _ptr(out), _stream()), 't2i_upfirdn2d')
+    return out
+
+
 # ---- sliced Wasserstein distance (csrc/t2i_swd.hip; evaluation/swd.py is the caller) -----------------------------------------
 def _f32_nd(t, name, dim):
     if t.dtype != torch.float32 or t.dim() != dim or not t.is_contiguous():

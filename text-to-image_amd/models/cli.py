@@ -96,6 +96,28 @@ def subsets_of(args):
     return (args.mmd_subsets, args.mmd_subset_size)
 
 
+def add_resample_filter_argument(ap, reader=True):
+    ap.add_argument('--resample-filter', default=None, metavar='TAPS',
+                    help="low-pass filtered resampling in both networks (Karras et al. 2019, Zhang 2019): comma-separated taps, 2..8 of "
+                         "them, finite, with a positive sum, e.g. 1,3,3,1; they replace the generator's nearest x2 upscale and the critic's "
+                         "2x2 average pool%s (default: the reference's resampling)"
+                         % (' - give the taps the checkpoint was trained with: a mismatch is refused' if reader else
+                            '; checkpoints carry the taps and the evaluators and visualisers must be given the same'))
+
+
+def resample_filter_of(ap, args):
+    """--resample-filter as a tuple of floats (None when absent); anything but 2..8 finite taps with a positive sum is an argument error."""
+    if args.resample_filter is None:
+        return None
+    try:
+        taps = tuple(float(t) for t in args.resample_filter.split(','))
+    except ValueError:
+        taps = ()
+    if not 2 <= len(taps) <= 8 or any(t != t or t in (float('inf'), float('-inf')) for t in taps) or not sum(taps) > 0.0:
+        ap.error('--resample-filter takes 2..8 comma-separated finite taps with a positive sum, e.g. 1,3,3,1 (got %r)' % args.resample_filter)
+    return taps
+
+
 def check_mode(args, cfg, visualiser):
     """The mode errors, raised before any device work and before a directory is created."""
     if args.incep_batch is not None and (not args.eval or args.incep_batch <= 0):

@@ -50,13 +50,15 @@ from t2i_amd.models import cli  # noqa: E402
 from t2i_amd.utils.saver import restore_scopes  # noqa: E402
 
 
-def stage_model(cfg, stage, batch_size, dataset, device, **widths):
+def stage_model(cfg, stage, batch_size, dataset, device, resample_filter=None, **widths):
     """The stage's PGGAN without its training graph (build_model=False), g_net created by a launch-free pass.  `widths`
-    (fmap_base, fmap_max, z_dim, embed_dim, compr_embed_dim) default to the reference's."""
+    (fmap_base, fmap_max, z_dim, embed_dim, compr_embed_dim) default to the reference's.  resample_filter: PGGAN's, the taps the
+    checkpoint was trained with (`train_pggan.py --resample-filter`); restore_generator refuses a checkpoint whose taps differ."""
     from t2i_amd.models.pggan.pggan import PGGAN
     from t2i_amd.scope import trainable_variables
     m = PGGAN(batch_size=batch_size, steps=None, check_dir_write='', check_dir_read=os.path.join(cfg.CHECKPOINT_DIR, 'stage%d/' % stage),
-              dataset=dataset, sample_path=None, log_dir=None, stage=stage, trans=False, build_model=False, device=device, **widths)
+              dataset=dataset, sample_path=None, log_dir=None, stage=stage, trans=False, build_model=False, device=device,
+              **dict(widths, **({} if resample_filter is None else {'resample_filter': resample_filter})))
     if not trainable_variables('g_net'):
         with K.dry_run(), torch.no_grad():
             m.generator(torch.empty(batch_size, m.z_dim, device=m.device), torch.empty(batch_size, m.embed_dim, device=m.device),
@@ -65,9 +67,18 @@ def stage_model(cfg, stage, batch_size, dataset, device, **widths):
 
 
 def restore_generator(m, ema=False):
-    """ema=True: the moving average of the weights that `train_pggan.py --g-ema` keeps in the checkpoint, as the weights."""
+    """ema=True: the moving average of the weights that `train_pggan.py --g-ema` keeps in the checkpoint, as the weights.
+    The checkpoint's resampling taps (`g_net/resample_filter`, written by `train_pggan.py --resample-filter`) must be the model's:
+    a difference — the key present in a model without taps and the taps given for a checkpoint without the key included — raises
+    RuntimeError naming both sides, because the weights would otherwise be sampled through another generator."""
+    from t2i_amd.models.pggan.pggan import RESAMPLE_KEY, describe_taps, same_taps
+    found = []
     restore_scopes(m.store, [('g_net', m.check_dir_read)], error=lambda scope: RuntimeError('Could not load stage %d' % m.stage), verbose=False,
-                   ema=ema)
+                   ema=ema, extra={RESAMPLE_KEY: ((lambda: None), found.append)})
+    ckpt = found[-1] if found else None
+    if not same_taps(ckpt, m.resample_taps):
+        raise RuntimeError('the checkpoint in %s was trained with %s, but this model resamples with %s: pass the same --resample-filter '
+                           '(resample_filter=) the trainer was given' % (m.check_dir_read, describe_taps(ckpt), describe_taps(m.resample_taps)))
 
 
 def generate(m, z, cond, cond_noise=True):
@@ -119,7 +130,9 @@ def main(argv=None, **widths):
     ap.add_argument('--batch', type=int, default=64, help='images generated (and scored) per batch [64]')
     ap.add_argument('--incep-batch', type=int, default=None, help='Inception batch (default: --batch)')
     ap.add_argument('--ema', action='store_true', help="score the moving average of the generator's weights (a checkpoint of train_pggan.py --g-ema)")
+    cli.add_resample_filter_argument(ap)
     args = ap.parse_args(argv)
+    taps = cli.resample_filter_of(ap, args)
     if not 1 <= args.stage <= 8:
         ap.error('--stage must be in 1..8')
     if args.batch < 1 or (args.incep_batch is not None and args.incep_batch < 1):
@@ -138,7 +151,7 @@ def main(argv=None, **widths):
         raise ValueError('EVAL.SIZE %d is smaller than --batch %d' % (cfg.EVAL.SIZE, args.batch))
     dev = torch.device('cuda')
     dataset = load_stage_dataset(cfg, args.stage, dev)
-    m = stage_model(cfg, args.stage, args.batch, dataset, dev, **widths)
+    m = stage_model(cfg, args.stage, args.batch, dataset, dev, resample_filter=taps, **widths)
     ev = PGGANEval(None, m, dataset, cfg, incep_batch_size=args.incep_batch)
     ev.ema = args.ema
     out = cli.run_eval(ev, args.eval, args.msssim_pairs, args.prdc_k, cli.subsets_of(args))

@@ -25,7 +25,12 @@ sampler's (utils.ops.DiffAugmentSampler: `diffaug_sampler`, or the model's own),
 `Dx_logit`, `Dg_logit` and `aug_p`, all on the device.  `critic_sn=True` (default False) divides every conv2d / fc kernel of the critic by an estimate
 of its largest singular value (Miyato et al. 2018): `self.critic_spectral`, an optim.SpectralNorm, keeps the raw weights the critic's Adam steps
 and advances one power iteration per step, inside D_optimizer.apply(); the variables, and so the checkpoints and every reader, hold the
-normalised weights, and checkpoints also carry `<variable>/spectral_raw`, `_u`, `_v`, `_sigma`.  `adam_lr=L` sets Adam's step size (default None: the reference's 2e-6).  Reference specifics kept: penalty
+normalised weights, and checkpoints also carry `<variable>/spectral_raw`, `_u`, `_v`, `_sigma`.
+`resample_filter=(1, 3, 3, 1)` (or any 2..8 finite taps with a positive sum; default None = the reference's resampling) replaces the
+generator's nearest x2 `upscale` by utils.ops.upsample_2d and the critic's 2x2 `pool` by utils.ops.downsample_2d with those taps, in the
+blocks and in both fade-in branches (Karras et al. 2019, Zhang 2019): one launch of csrc/t2i_resample.hip each,
+differentiable to any order.  This changes the generator's function, so checkpoints carry the normalised taps as `g_net/resample_filter`
+and the readers (eval_pggan.restore_generator) refuse a checkpoint whose taps differ from the model's.  `adam_lr=L` sets Adam's step size (default None: the reference's 2e-6).  Reference specifics kept: penalty
 coefficient 200, no kt term, G = -D_fake + 5 KL, Adam(2e-6, beta1=0, beta2=0.99) hard-coded (pggan.py:104-110; the
 `learning_rate` placeholder is fed but unused), eps of x_hat drawn in-graph (pggan.py:68 overrides the placeholder),
 `to_rgb` = k2 s1 SAME 9-channel relu conv + 1x1, every kernel He-initialised by utils/ops.py's defaults.
@@ -36,6 +41,7 @@ whether the critic step's own forward sees the new or the previous value is a TF
 from `iter` BEFORE the critic step and kept for the generator step and the sampler — the assign-first order."""
 import contextlib
 import math
+import os
 import sys
 import time
 
@@ -45,15 +51,56 @@ from ... import autograd as A
 from ... import kernels as K
 from ... import optim
 from ... import scope as S
-from ...utils.ops import (DiffAugmentSampler, concat_tile, conv2d, diff_augment, diff_augment_params, diff_augment_policy, fc, layer_norm,
-                          lerp, lrelu_act, minibatch_stddev_stat, pixel_norm, pool, relu, upscale)
+from ...utils.ops import (DiffAugmentSampler, concat_tile, conv2d, diff_augment, diff_augment_params, diff_augment_policy, downsample_2d, fc,
+                          layer_norm, lerp, lrelu_act, minibatch_stddev_stat, pixel_norm, pool, relu, upsample_2d, upscale)
+
+RESAMPLE_KEY = 'g_net/resample_filter'          # the checkpoint entry of PGGAN(resample_filter=...): the taps divided by their sum, float32
+
+
+def normalised_taps(resample_filter):
+    """None -> None; a sequence of 2..8 finite taps with a positive sum -> (the taps as floats, taps / sum as a float32 array: what a
+    checkpoint carries); anything else is a ValueError."""
+    import numpy as np
+    if resample_filter is None:
+        return None
+    try:
+        k = tuple(float(t) for t in resample_filter)
+    except (TypeError, ValueError):
+        k = ()
+    if isinstance(resample_filter, str) or not 2 <= len(k) <= 8 or not all(math.isfinite(t) for t in k) or not math.fsum(k) > 0.0:
+        raise ValueError('resample_filter must be None or a sequence of 2..8 finite taps with a positive sum (the low-pass filter of the '
+                         'up- and downsampling, e.g. (1, 3, 3, 1)), got %r' % (resample_filter,))
+    norm = (np.asarray(k, dtype=np.float64) / math.fsum(k)).astype(np.float32)
+    if not np.isfinite(norm).all():
+        raise ValueError('resample_filter %r does not normalise to finite float32 taps' % (resample_filter,))
+    return k, norm
+
+
+def same_taps(a, b):
+    """Whether two normalised tap arrays (or None: no filter) describe the same resampling."""
+    import numpy as np
+    if a is None or b is None:
+        return a is None and b is None
+    a, b = np.asarray(a, dtype=np.float32).reshape(-1), np.asarray(b, dtype=np.float32).reshape(-1)
+    return a.shape == b.shape and bool((a == b).all())
+
+
+def describe_taps(norm):
+    """The taps of a message: 'no filter (nearest x2, 2x2 mean)' or the normalised values."""
+    if norm is None:
+        return 'no filter (nearest x2 upscale, 2x2 mean pool)'
+    return 'the normalised taps (%s)' % ', '.join('%.6g' % float(t) for t in norm)
 
 
 class PGGAN(object):
     def __init__(self, batch_size, steps, check_dir_write, check_dir_read, dataset, sample_path, log_dir, stage, trans,
                  build_model=True, device=None, seed=0, store=None, fmap_base=1024, fmap_max=512, z_dim=128, embed_dim=1024,
                  compr_embed_dim=128, dp=None, critic_norm=None, critic_mbstd=None, g_ema=None, equalized_lr=False, adam_lr=None,
-                 diffaug=None, diffaug_p=None, diffaug_adapt=False, diffaug_sampler=None, critic_sn=False):
+                 diffaug=None, diffaug_p=None, diffaug_adapt=False, diffaug_sampler=None, critic_sn=False, resample_filter=None):
+        taps = normalised_taps(resample_filter)
+        self.resample_filter = None if taps is None else taps[0]          # the taps as given; None: nearest x2 and the 2x2 mean
+        self.resample_taps = None if taps is None else taps[1]            # ... divided by their sum, float32: what checkpoints carry
+        self.resample_restored = None                                     # train(): the taps of the checkpoint the last restore read (None: it had none)
         if not isinstance(critic_sn, bool):
             raise ValueError('critic_sn must be True or False, got %r' % (critic_sn,))
         self.critic_sn = critic_sn
@@ -411,13 +458,13 @@ class PGGAN(object):
         with S.variable_scope('d_net', reuse=reuse):
             x_iden = None
             if t:
-                x_iden = self.from_rgb(pool(inp, 2), stages - 2)
+                x_iden = self.from_rgb(self._down(inp), stages - 2)
             x = self.from_rgb(inp, stages - 1)
             for i in range(stages - 1, 0, -1):
                 with S.variable_scope(self.get_conv_scope_name(i), reuse=reuse):
                     x = self._d_conv(x, self.get_dnf(i), (3, 3), 'SAME', act)
                     x = self._d_conv(x, self.get_dnf(i - 1), (3, 3), 'SAME', act)
-                    x = pool(x, 2)
+                    x = self._down(x)
                 if i == stages - 1 and t:
                     x = lerp(x_iden, x, alpha_trans)              # alpha * x + (1 - alpha) * x_iden
             with S.variable_scope(self.get_conv_scope_name(0), reuse=reuse):
@@ -429,6 +476,14 @@ class PGGAN(object):
                 x_b1 = self._d_conv(x_b1, self.get_dnf(0), (4, 4), 'VALID', act)
                 output_b1 = self._fc(x_b1.reshape(x_b1.shape[0], -1), units=1)      # dense on the [B,1,1,C] map
             return output_b1.reshape(-1)
+
+    def _up(self, x):
+        """x2: the reference's nearest-neighbour upscale, or with resample_filter the low-pass filtered upsample_2d."""
+        return upscale(x, 2) if self.resample_filter is None else upsample_2d(x, self.resample_filter)
+
+    def _down(self, x):
+        """/2: the reference's 2x2 average pool, or with resample_filter the low-pass filtered downsample_2d."""
+        return pool(x, 2) if self.resample_filter is None else downsample_2d(x, self.resample_filter)
 
     def _d_conv(self, x, f, ks, padding, act):
         """A 3x3 / 4x4 convolution of the critic.  critic_norm = None: conv + lrelu (the reference).  'layer' / 'pixel': the conv
@@ -458,9 +513,9 @@ class PGGAN(object):
             for i in range(1, stages):
                 if (i == stages - 1) and t:
                     x_iden = self.to_rgb(x, stages - 2)
-                    x_iden = upscale(x_iden, 2)
+                    x_iden = self._up(x_iden)
                 with S.variable_scope(self.get_conv_scope_name(i), reuse=reuse):
-                    x = upscale(x, 2)
+                    x = self._up(x)
                     x = self._conv2d(x, f=self.get_nf(i), ks=(3, 3), s=(1, 1))
                     x = layer_norm(x, act=relu)
                     x = self._conv2d(x, f=self.get_nf(i), ks=(3, 3), s=(1, 1))
@@ -580,6 +635,12 @@ class PGGAN(object):
             for n in sn.names:
                 for key in sn.keys(n):
                     extra[key] = ((lambda key=key: sn.state_tensor(key).numpy()), (lambda a, key=key: sn_loaded.__setitem__(key, a)))
+        taps_loaded = []
+        if self.resample_filter is not None:
+            # the normalised taps travel with every checkpoint (and only with the flag: without it the files are what they were), so that
+            # a reader built with other taps, or none, can refuse the generator instead of sampling another function from its weights
+            extra = dict(extra or {})
+            extra[RESAMPLE_KEY] = ((lambda: self.resample_taps), taps_loaded.append)
         saver = Saver(self.store, var_list=self.get_variables_up_to_stage(self.stage), max_to_keep=2, shadows=shadows, extra=extra)
         if side_effects and self.stage != 1:
             src = Saver(self.store, var_list=self.get_variables_up_to_stage(self.stage - 1), shadows=shadows, extra=extra) if self.trans else saver
@@ -587,6 +648,16 @@ class PGGAN(object):
             if not could_load:
                 raise RuntimeError('Could not load previous stage during transition' if self.trans else 'Could not load current stage')
             self.restored = (self.check_dir_read, step, list(src.var_list))
+            if self.resample_filter is None:          # no entry of ours to be handed the key: look into the file that was read
+                import numpy as np
+                with np.load(os.path.join(self.check_dir_read, 'model-%d.npz' % step)) as z:
+                    if RESAMPLE_KEY in z.files:
+                        taps_loaded.append(z[RESAMPLE_KEY])
+            self.resample_restored = taps_loaded[-1] if taps_loaded else None
+            if not same_taps(self.resample_restored, self.resample_taps):
+                # the trainer goes on (a stage may be grown with another filter on purpose); the readers refuse (eval_pggan.restore_generator)
+                log('resample filter: the checkpoint in %s was trained with %s, this model resamples with %s' % (
+                    self.check_dir_read, describe_taps(self.resample_restored), describe_taps(self.resample_taps)))
             if sn is not None:
                 # a kernel that was restored and whose four keys the file holds is restored verbatim; every other one starts from the
                 # weights it has now (a checkpoint trained without the flag, a variable new at this stage)

@@ -21,6 +21,7 @@ import torch  # noqa: E402
 import t2i_amd  # noqa: E402,F401
 from t2i_amd import kernels as K  # noqa: E402
 from t2i_amd.data import SyntheticTextDataset  # noqa: E402
+from t2i_amd.models import cli  # noqa: E402
 from t2i_amd.models.pggan.pggan import PGGAN  # noqa: E402
 from t2i_amd.utils.config import AttrDict  # noqa: E402
 
@@ -107,6 +108,7 @@ def main(argv=None):
     ap.add_argument('--critic-sn', action='store_true',
                     help="spectral normalisation of the critic's conv and dense kernels (Miyato et al. 2018): one power iteration per "
                          "critic step next to the Adam launch; checkpoints carry the raw weights, u, v and sigma (default: none)")
+    cli.add_resample_filter_argument(ap, reader=False)
     ap.add_argument('--diffaug', default=None, metavar='POLICY',
                     help="differentiable augmentation of every image the critic sees (Zhao et al. 2020): a comma-separated subset of "
                          "color,translation,cutout (default: none)")
@@ -124,6 +126,7 @@ def main(argv=None):
     ap.add_argument('--eager', action='store_true', help='--bench: keep eager launches instead of hipGraph replay')
     ap.add_argument('--bench', action='store_true', help='time `--iters` iterations of each entry instead of training with side effects')
     args = ap.parse_args(argv)
+    taps = cli.resample_filter_of(ap, args)
     if not 0 <= args.first <= args.last < len(STAGE):
         ap.error('--first %d / --last %d: need 0 <= first <= last <= %d' % (args.first, args.last, len(STAGE) - 1))
     if args.iters is not None and args.iters < 1:
@@ -189,7 +192,7 @@ def main(argv=None):
                       log_dir=logs_dir, stage=STAGE[i], trans=t, device=dev, critic_norm=args.critic_norm,
                       critic_mbstd=args.critic_mbstd, **({} if args.g_ema is None else {'g_ema': args.g_ema}),
                       **({'equalized_lr': True} if args.equalized_lr else {}), **({} if args.lr is None else {'adam_lr': args.lr}),
-                      **({'critic_sn': True} if args.critic_sn else {}),
+                      **({'critic_sn': True} if args.critic_sn else {}), **({} if taps is None else {'resample_filter': taps}),
                       **({} if args.diffaug is None else {'diffaug': args.diffaug}),
                       **({} if aug_sampler is None else {'diffaug_sampler': aug_sampler, 'diffaug_adapt': args.diffaug_adapt}))
         if args.bench:

@@ -23,6 +23,7 @@ section 4.35) take fp32 tensors only, with the same refusals, and are differenti
 4.39) draws those tables on the device with a probability ``p`` per transform and can steer ``p`` from a critic's outputs.
 """
 import math
+import struct
 
 import torch
 
@@ -630,6 +631,99 @@ def upscale(x, s=2):
         return A.Upscale2Fn.apply(x, 1.0)
     _fp32_plain(x, 'upscale')
     return A.ResizeNearestFn.apply(x, int(x.shape[1]) * int(s), int(x.shape[2]) * int(s))
+
+
+def _fir_taps(f, scale, op):
+    """The taps of a resampling filter as float32-exact Python floats: f * scale, refused unless 1..8 finite numbers."""
+    try:
+        f = [float(t) for t in f]
+    except (TypeError, ValueError):
+        raise ValueError('%s: the filter must be a sequence of numbers, got %r' % (op, f))
+    if not 1 <= len(f) <= K.UPFIRDN_MAX_TAPS:
+        raise ValueError('%s: the filter has %d taps, 1..%d are supported' % (op, len(f), K.UPFIRDN_MAX_TAPS))
+    taps = tuple(_f32(t * scale) for t in f)
+    if not all(math.isfinite(t) for t in taps):
+        raise ValueError('%s: the taps must be finite in float32, got %r (times %r)' % (op, f, scale))
+    return taps
+
+
+def _f32(v):
+    """v rounded to float32, as a Python float (inf where it overflows)"""
+    try:
+        return struct.unpack('f', struct.pack('f', v))[0]
+    except OverflowError:
+        return math.copysign(math.inf, v)
+
+
+def upfirdn2d(x, f, up=1, down=1, pad=(0, 0), flip=False, gain=1.0):
+    """Anti-aliased resampling (not in the reference: the `upfirdn2d` of Karras et al. 2019).  x [B,H,W,C]
+    (contiguous NHWC, fp32) -> [B,Ho,Wo,C]; along H and along W alike: insert up - 1 zeros after every sample, pad by pad[0] in front
+    and pad[1] behind (a negative pad crops), convolve with the taps f (a sequence of 1..8 numbers, used on both axes, reversed first
+    when flip; true convolution), keep every down-th sample: Ho = (H up + pad[0] + pad[1] - len(f)) // down + 1.  gain scales the result;
+    it is folded into the taps as sqrt(gain) per axis (gain >= 0).  up and down are 1 or 2: other factors are refused, as are bf16
+    tensors, a stacked pass, non-finite taps, pads beyond 32768 in magnitude, an empty output and tensors of 2^31 elements or more,
+    all with ValueError (NotImplementedError for the stacked pass) before any launch.  One launch of csrc/t2i_resample.hip; the taps
+    are host values (no gradient flows to them) and travel as kernel arguments, so the call can be captured.  Differentiable in x to any
+    order: the backward is the same kernel with the adjoint's parameters.  A sample's result does not depend on its batch, bit for bit."""
+    op = 'upfirdn2d'
+    _fp32_plain(x, op)
+    if not x.is_contiguous():
+        raise ValueError('%s works on physically NHWC data; got a non-contiguous tensor (shape %s, strides %s) - convert a logical NCHW '
+                         'view with to_nhwc first' % (op, tuple(x.shape), x.stride()))
+    for label, v in (('up', up), ('down', down)):
+        if isinstance(v, bool) or not isinstance(v, int) or v not in (1, 2):
+            raise ValueError('%s: %s must be 1 or 2, got %r' % (op, label, v))
+    if not isinstance(pad, (tuple, list)) or len(pad) != 2 or any(isinstance(p, bool) or not isinstance(p, int) for p in pad):
+        raise ValueError('%s: pad must be a pair of integers (front, back), got %r' % (op, pad))
+    if isinstance(gain, bool) or not isinstance(gain, (int, float)) or not (math.isfinite(gain) and gain >= 0.0):
+        raise ValueError('%s: gain must be a finite number >= 0, got %r' % (op, gain))
+    taps = _fir_taps(f, math.sqrt(float(gain)), op)
+    p0, p1 = int(pad[0]), int(pad[1])
+    if max(abs(p0), abs(p1)) > K.UPFIRDN_MAX_PAD:
+        raise ValueError('%s: pads %r exceed %d in magnitude' % (op, tuple(pad), K.UPFIRDN_MAX_PAD))
+    B, H, W, C = (int(s) for s in x.shape)
+    if min(B, H, W, C) < 1:
+        raise ValueError('%s: every size of x must be at least 1, got %s' % (op, tuple(x.shape)))
+    Ho, Wo = K.upfirdn2d_extent(H, up, down, p0, p1, len(taps)), K.upfirdn2d_extent(W, up, down, p0, p1, len(taps))
+    if Ho < 1 or Wo < 1:
+        raise ValueError('%s: a %dx%d map with up %d, down %d, pads %r and %d taps has no output' % (op, H, W, up, down, tuple(pad), len(taps)))
+    if x.numel() >= 1 << 31 or B * Ho * Wo * C >= 1 << 31:
+        raise ValueError('%s: x %s or the output %s has 2^31 elements or more' % (op, tuple(x.shape), (B, Ho, Wo, C)))
+    return A.UpFirDn2dFn.apply(x, taps, up, down, p0, (p1, p1), bool(flip))
+
+
+def _resample_helper(x, k, factor, gain, op, up):
+    if isinstance(factor, bool) or not isinstance(factor, int) or factor not in (1, 2):
+        raise ValueError('%s: factor must be 1 or 2, got %r' % (op, factor))
+    try:
+        total = math.fsum(float(t) for t in k)
+    except (TypeError, ValueError):
+        raise ValueError('%s: the filter must be a sequence of numbers, got %r' % (op, k))
+    if not (math.isfinite(total) and total != 0.0):
+        raise ValueError('%s: the taps %r must have a finite, non-zero sum (they are normalised by it)' % (op, k))
+    n = len(k)
+    p = n - factor
+    scale = (factor if up else 1.0) / total                      # per axis: DC gain 1 after the zero insertion
+    k = _fir_taps(k, scale, op)
+    if up:
+        return upfirdn2d(x, k, up=factor, pad=((p + 1) // 2 + factor - 1, p // 2), gain=gain)
+    return upfirdn2d(x, k, down=factor, pad=((p + 1) // 2, p // 2), gain=gain)
+
+
+def upsample_2d(x, k=(1, 3, 3, 1), factor=2, gain=1.0):
+    """Low-pass filtered upsampling (Karras et al. 2019, `upsample_2d`; not in the reference): upfirdn2d with up = factor, the taps
+    factor * k / sum(k) per axis (DC gain 1) and the publication's pads ((p + 1) // 2 + factor - 1, p // 2), p = len(k) - factor:
+    [B,H,W,C] -> [B,factor H,factor W,C].  k = (1, 1) is the nearest-neighbour `upscale(x, 2)` exactly.  factor is 1 or 2 (others are
+    refused), fp32 only (bf16 is refused); the other refusals, the launch and the derivatives are upfirdn2d's."""
+    return _resample_helper(x, k, factor, gain, 'upsample_2d', True)
+
+
+def downsample_2d(x, k=(1, 3, 3, 1), factor=2, gain=1.0):
+    """Low-pass filtered downsampling (Karras et al. 2019, `downsample_2d`; Zhang 2019's blur pool; not in the reference): upfirdn2d
+    with down = factor, the taps k / sum(k) per axis (DC gain 1) and the publication's pads ((p + 1) // 2, p // 2), p = len(k) - factor:
+    [B,H,W,C] -> [B,H / factor,W / factor,C] on even extents.  k = (1, 1) is the 2x2 mean `pool(x, 2)` to rounding.  factor is 1 or 2
+    (others are refused), fp32 only (bf16 is refused); the other refusals, the launch and the derivatives are upfirdn2d's."""
+    return _resample_helper(x, k, factor, gain, 'downsample_2d', False)
 
 
 def downscale(x, s=2):

@@ -178,18 +178,20 @@ def load(saver, sess, checkpoint_dir, ema=False):
     return False, 0
 
 
-def restore_scopes(store, pairs, create=None, error=RuntimeError, verbose=True, ema=False):
+def restore_scopes(store, pairs, create=None, error=RuntimeError, verbose=True, ema=False, extra=None):
     """Restores each (scope, directory) of `pairs` in order: tf.train.Saver(tf.global_variables(scope)) + load in the reference.
     When the last scope has no trainable variables yet, `create()` builds the generators once, launch-free (K.dry_run, no gradient).
     The first directory without a checkpoint ends it: ` [!] Load failed...` and `raise error(scope)` (the caller's exception); a
     restored one prints ` [*] Load SUCCESS`.  verbose=False drops those two lines (load's own remain).  ema=True loads every variable
-    from its `<variable>/ExponentialMovingAverage` key (KeyError for a checkpoint trained without EMA)."""
+    from its `<variable>/ExponentialMovingAverage` key (KeyError for a checkpoint trained without EMA).  extra: Saver's `extra`
+    ({key: (getter, setter)}), handed to every scope's Saver: a setter is called with the entry of each checkpoint that has its key
+    (default None: no entry is read)."""
     if create is not None and not store.trainable_variables(pairs[-1][0]):
         from .. import kernels as K
         with K.dry_run(), torch.no_grad():
             create()
     for scope, directory in pairs:
-        could_load, _ = load(Saver(store, var_list=[scope]), None, directory, ema=ema)
+        could_load, _ = load(Saver(store, var_list=[scope], extra=extra), None, directory, ema=ema)
         if not could_load:
             if verbose:
                 print(' [!] Load failed...')

@@ -3,7 +3,8 @@
 gn, the double backward of pixel_norm and layer_norm, the minibatch standard deviation) at PGGAN-sized tensors, and the Adam launch with and
 without the weight EMA (`--only adam_ema`) and with per-slot multipliers (`--only adam_slots`) at the sizes of two generator arenas, and the
 differentiable augmentation of csrc/t2i_augment.hip at the PGGAN trainer's shapes next to the same policy from tensor-library calls
-(`--only diff_augment`), and the critic's optimizer step with and without spectral normalisation (`--only spectral_norm`): one JSON line per kernel with the time per call, the bytes the algorithm moves (reads + writes, from the
+(`--only diff_augment`), and the critic's optimizer step with and without spectral normalisation (`--only spectral_norm`), and the
+anti-aliased resampling of csrc/t2i_resample.hip at the PGGAN trainer's full widths (`--only upfirdn`): one JSON line per kernel with the time per call, the bytes the algorithm moves (reads + writes, from the
 shapes), bytes per second, and the ratio of that rate to a device-to-device copy that moves the SAME number of bytes (half read, half
 written), timed in the same process.  Per measurement: 10 warm-up launches, then REPS rounds of 100 back-to-back launches between
 device events, kernel and copy rounds alternating; the median round is reported.  Read the ratio, not the absolute rate, as the share
@@ -40,8 +41,9 @@ def _round(fn, iters):
     return s.elapsed_time(e) / iters * 1e-3
 
 
-def measure(name, shape, nbytes, fn, reps, iters, composed=None):
-    """composed: the same operation as tensor-library calls, timed in the same alternating rounds ('composed_us', 'ratio_to_composed')"""
+def measure(name, shape, nbytes, fn, reps, iters, composed=None, others=None):
+    """composed: the same operation as tensor-library calls, timed in the same alternating rounds ('composed_us', 'ratio_to_composed');
+    others: {label: fn} of further launches on the same tensors, timed in the same rounds ('<label>_us')"""
     src = torch.empty(nbytes // 8, dtype=torch.float32, device='cuda').normal_()
     dst = torch.empty_like(src)
     copy = lambda: dst.copy_(src)          # moves nbytes: nbytes / 2 read + nbytes / 2 written
@@ -49,13 +51,17 @@ def measure(name, shape, nbytes, fn, reps, iters, composed=None):
         fn(); copy()
         if composed is not None:
             composed()
+        for other in (others or {}).values():
+            other()
     torch.cuda.synchronize()
-    tk, tc, tl = [], [], []
+    tk, tc, tl, to = [], [], [], {k: [] for k in (others or {})}
     for _ in range(reps):
         tk.append(_round(fn, iters))
         tc.append(_round(copy, iters))
         if composed is not None:
             tl.append(_round(composed, iters))
+        for k, other in (others or {}).items():
+            to[k].append(_round(other, iters))
     t, c = statistics.median(tk), statistics.median(tc)
     line = {'kernel': name, 'shape': list(shape), 'us_per_call': round(t * 1e6, 2), 'bytes': nbytes,
             'working_set_MB': round(nbytes / 1e6, 1), 'in_infinity_cache': nbytes <= INFINITY_CACHE // 2,
@@ -63,6 +69,8 @@ def measure(name, shape, nbytes, fn, reps, iters, composed=None):
             'ratio_to_copy': round(c / t, 3), 'spread_us': [round(min(tk) * 1e6, 2), round(max(tk) * 1e6, 2)]}
     if composed is not None:
         line.update(composed_us=round(statistics.median(tl) * 1e6, 2), ratio_to_composed=round(statistics.median(tl) / t, 2))
+    for k, ts in to.items():
+        line['%s_us' % k] = round(statistics.median(ts) * 1e6, 2)
     print(json.dumps(line), flush=True)
 
 
@@ -83,6 +91,22 @@ def composed_diff_augment(x, P):
     yy, xx = ar(H, (1, H, 1)), ar(W, (1, 1, W))
     inside = (yy >= P[:, 5].view(B, 1, 1)) & (yy < P[:, 6].view(B, 1, 1)) & (xx >= P[:, 7].view(B, 1, 1)) & (xx < P[:, 8].view(B, 1, 1))
     return u * (~inside).unsqueeze(3).to(u.dtype)
+
+
+def composed_upfirdn(x, taps, u, d, p0, p1):
+    """utils.ops.upfirdn2d from tensor-library calls, the way the publication's reference code builds it: zero-stuff, F.pad, a depthwise
+    F.conv2d with the outer product of the reversed taps, a strided slice.  x: a channels-last NCHW view of the kernel's NHWC tensor."""
+    B, C, H, W = x.shape
+    if u == 2:
+        z = x.new_zeros((B, C, 2 * H, 2 * W)).contiguous(memory_format=torch.channels_last)
+        z[:, :, ::2, ::2] = x
+    else:
+        z = x
+    z = torch.nn.functional.pad(z, [p0, p1, p0, p1])
+    g = torch.tensor(taps, dtype=torch.float32, device=x.device).flip(0)
+    w = (g[:, None] * g[None, :])[None, None].repeat(C, 1, 1, 1)
+    y = torch.nn.functional.conv2d(z, w, groups=C)
+    return y[:, :, ::d, ::d] if d == 2 else y
 
 
 def main():
@@ -254,6 +278,32 @@ def main():
             m('spectral_norm: AdamTF(spectral=).apply(), 7 launches, %s (8r + 4w)' % tag, (n,), 48 * n, lambda: spec.apply(refresh=False))
             m('spectral_norm: grad_() + normalize(1) alone, 6 launches, %s (5r + 2w)' % tag, (n,), 28 * n, lambda: (sn.grad_(), sn.normalize(1)))
             del pg, arena, sn, plain, spec
+
+    # anti-aliased resampling with the taps (1, 3, 3, 1) at fp32 and the trainer's full widths: the generator's
+    # upsample at stages 3, 5, 7 ([B, S/2, S/2, nf], B = 16 / 16 / 8), the critic's downsample at the same stages with its 3B rows, and the
+    # C = 3 pair of the fade-in branches at stage 7.  Bytes: |x| + |y|.  Next to each line: t2i_upscale2 / t2i_pool2_sum on the same
+    # tensors (what the option replaces) and the tensor-library composition on channels-last views, checked against the kernel first.
+    if a.only and a.only in 'upfirdn':
+        from t2i_amd.utils import ops
+        k = (1.0, 3.0, 3.0, 1.0)
+        up_taps, down_taps = tuple(2.0 * t / 8.0 for t in k), tuple(t / 8.0 for t in k)
+        rows = [('upsample_2d', 'generator stage %d' % s, shape) for s, shape in ((3, (16, 8, 8, 512)), (5, (16, 32, 32, 512)), (7, (8, 128, 128, 128)))]
+        rows += [('downsample_2d', 'critic stage %d, 3B rows' % s, shape) for s, shape in ((3, (48, 16, 16, 512)), (5, (48, 64, 64, 256)), (7, (24, 256, 256, 64)))]
+        rows += [('upsample_2d', 'generator fade-in, stage 7', (8, 128, 128, 3)), ('downsample_2d', 'critic fade-in, stage 7, 3B rows', (24, 256, 256, 3))]
+        with torch.no_grad():
+            for kind, where, shape in rows:
+                x = torch.randn(shape, device='cuda')
+                xc = x.permute(0, 3, 1, 2)                       # the same memory as a channels-last NCHW tensor
+                if kind == 'upsample_2d':
+                    fn, base, comp = (lambda: K.upfirdn2d(x, up_taps, 2, 1, 2, 1, False)), (lambda: K.upscale2(x, 1.0)), (lambda: composed_upfirdn(xc, up_taps, 2, 1, 2, 1))
+                    label, out = 'upscale2', 4 * x.numel()
+                else:
+                    fn, base, comp = (lambda: K.upfirdn2d(x, down_taps, 1, 2, 1, 1, False)), (lambda: K.pool2_sum(x, 0.25)), (lambda: composed_upfirdn(xc, down_taps, 1, 2, 1, 1))
+                    label, out = 'pool2_sum', x.numel() // 4
+                err = float((fn().permute(0, 3, 1, 2) - comp()).abs().max())
+                assert err <= 1e-4 and torch.equal(fn(), getattr(ops, kind)(x, k)), (kind, shape, err)      # the helper's launch, called as upscale2 / pool2_sum are
+                measure('upfirdn: %s (1,3,3,1), %s (r + w)' % (kind, where), shape, 4 * (x.numel() + out), fn, a.reps, a.iters, comp, {label: base})
+                del x, xc
 
 
 if __name__ == '__main__':
