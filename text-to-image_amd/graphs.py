@@ -5,9 +5,14 @@ Adam launch with its step size in device memory, tensor-library scalar math) —
 that survives the call, no host-side random draws.  `StepGraphs` keeps one set of static input buffers, captures each
 body once and replays it: at the reference's batch sizes (8 or 16) a GAN iteration is ~1000 launches of a few
 microseconds each and is bound by the host's launch rate, not by the GPU.  Replay is bit-identical to the eager
-launches (same kernels, same order)."""
+launches (same kernels, same order).  `DGSchedule` is the D-then-G iteration those bodies make up, eager or replayed."""
+import collections
+import inspect
+import weakref
+
 import torch
 
+from . import autograd as A
 from . import kernels as K
 
 
@@ -64,3 +69,92 @@ class StepGraphs(object):
         self.graphs[name].replay()
         K.filter_cache_invalidate()                  # a replayed optimizer step rewrote filters behind the host's back
         return self.outs[name]
+
+
+Half = collections.namedtuple('Half', 'losses arena optim')
+
+
+def _unowned(f):
+    """f, with a bound method held through a weak reference to its object.  The model owns its schedule; a strong reference back
+    would close a cycle, and the model, its arenas and its captured graphs would then be freed by the cyclic collector at some
+    later allocation instead of with their last reference — for instance inside another model's capture, where destroying a
+    graph is an error that aborts the process."""
+    if not inspect.ismethod(f):
+        return f
+    ref = weakref.WeakMethod(f)
+    return lambda *a, **kw: ref()(*a, **kw)
+
+
+class DGSchedule(object):
+    """The step schedule of models/gancls, models/stackgan and models/pggan (models/wgancls keeps its own: kt, the cut backward):
+
+        D half:  losses(feed) -> zero_grad -> [dp.arm] -> backward -> side_join | exchange | Adam
+        G half:  the same on the generator's arena
+
+    eager (step), captured whole, or — under data parallelism — captured and cut at the exchange: graphs 'd' | all-reduce of the
+    gradient arena, issued eagerly | 'd_upd', then 'g' | all-reduce | 'g_upd': no collective is ever captured.  The model's
+    losses(feed) end in self.backward(...); what a model draws or sets before a step is the model's business, before run()."""
+
+    def __init__(self, dp, d_losses, d_arena, d_optim, g_losses, g_arena, g_optim):
+        self.dp = dp                                 # a dp.DataParallel or None
+        self.d, self.g = Half(_unowned(d_losses), d_arena, d_optim), Half(_unowned(g_losses), g_arena, g_optim)
+        self.capturing = False                       # inside capture(): the exchanges are issued between the segments, not by armed hooks
+
+    def backward(self, arena, roots, seeds, variables):
+        """Gradients of `roots` (seeded by `seeds`, or None for scalar roots) with respect to `variables` -> arena."""
+        arena.zero_grad()
+        if self.dp is not None and not self.capturing:
+            self.dp.arm(arena)                       # the bucketed all-reduce overlaps the rest of this backward
+        torch.autograd.backward(roots, seeds, inputs=list(variables))
+        A.side_join()
+
+    def step(self, half, feed, refresh=None, **kw):
+        """One eager half (self.d or self.g), graph-capturable without dp: Adam reads its step size from device memory."""
+        out = half.losses(feed, **kw)
+        scale = self.dp.allreduce_arena(half.arena) if self.dp is not None else 1.0
+        half.optim.apply(grad_scale=scale, refresh=refresh)
+        return out
+
+    def capture(self, graphs, joint=None):
+        """Capture the iteration into `graphs` (a StepGraphs; call after one eager iteration).  Single process: 'dg' from `joint`, a
+        body of both halves, if one is given, else 'd' and 'g'.  Data parallelism: the four cut segments, in thread-local capture
+        mode because the process group's watchdog thread polls events meanwhile; the update segments run no convolution."""
+        if self.dp is None:
+            if joint is not None:
+                graphs.capture('dg', joint)
+            else:
+                graphs.capture('d', lambda f: self.step(self.d, f))
+                graphs.capture('g', lambda f: self.step(self.g, f))
+            return
+        scale = 1.0 / self.dp.world
+        self.capturing = True
+        try:
+            graphs.capture('d', self.d.losses, capture_error_mode='thread_local')
+            graphs.capture('d_upd', lambda f: self.d.optim.apply(grad_scale=scale), capture_error_mode='thread_local', refresh=False)
+            graphs.capture('g', self.g.losses, capture_error_mode='thread_local')
+            graphs.capture('g_upd', lambda f: self.g.optim.apply(grad_scale=scale), capture_error_mode='thread_local', refresh=False)
+        finally:
+            self.capturing = False
+
+    def run(self, feed, lr_d, lr_g, graphs=None, joint=None):
+        """One iteration -> {'d': ..., 'g': ...}: replayed from `graphs` if given, else eager (from `joint` if given).  prepare(lr)
+        publishes each step size on the host, outside any graph: both up front for a one-body iteration, else before its half."""
+        if graphs is not None:
+            graphs.load(feed)
+        one_body = 'dg' in graphs.graphs if graphs is not None else joint is not None
+        if one_body:
+            self.d.optim.prepare(lr_d)
+            self.g.optim.prepare(lr_g)
+            d, g = joint(feed) if graphs is None else graphs.replay('dg')
+            return {'d': d, 'g': g}
+        out = {}
+        for name, half, lr in (('d', self.d, lr_d), ('g', self.g, lr_g)):
+            half.optim.prepare(lr)
+            if graphs is None:
+                out[name] = self.step(half, feed)
+                continue
+            out[name] = graphs.replay(name)
+            if self.dp is not None:
+                self.dp.allreduce_arena(half.arena)
+                graphs.replay(name + '_upd')
+        return out

@@ -29,6 +29,7 @@ class GanCls(object):
         self.store = S.set_default_store(S.VariableStore(device=device, seed=seed))
         self.device = self.store.device
         self.dp = dp
+        self.g_scope, self.d_scope = 'g_net', 'd_net'              # (as models/stackgan: what the shared trainer base freezes)
         if build_model:
             self.build_model()
 

@@ -6,19 +6,15 @@ import time
 
 import torch
 
-from ... import autograd as A
-from ... import stacked as ST
-from ... import kernels as K
-from ... import optim
+from ...graphs import StepGraphs
 from ...utils.ops import update_ops
+from ..cgan_trainer import CGanTrainer
 
 
-class GanClsTrainer(object):
-    batched = True      # the critic's passes of one sess.run are one stacked batch (always: the unstacked forms are gone)
+class GanClsTrainer(CGanTrainer):
+    REAL_LABEL = 0.9    # one-sided smoothing (trainer.py:24)
 
     def __init__(self, sess, model, dataset, cfg):
-        self.sess, self.model, self.dataset, self.cfg = sess, model, dataset, cfg     # sess unused (no TF session)
-        self.gen = torch.Generator(device=model.device).manual_seed(1234)
         # The D run and the G run of one iteration evaluate the generator on the SAME feed (trainer.py:115-134: same z, same phi), the generator
         # has no noise input (model.py:111-192) and D_optim does not touch its variables: the two evaluations are the same numbers.  iteration()
         # therefore evaluates it ONCE (with the autograd graph the G run needs), hands the critic step a detached view, and lets the batch norms'
@@ -26,165 +22,56 @@ class GanClsTrainer(object):
         # data parallelism the two halves live in separately captured graph segments.  share_g = False: evaluate twice.
         self.share_g = True
         self._shared_G = None
-        self.define_losses()
-
-    def define_losses(self):
-        t = self.cfg.TRAIN
-        self.alpha = float(t.COEFF.ALPHA_MISMATCH_LOSS)
-        self.D_optim = optim.AdamTF(self.model.d_arena, float(t.D_BETA_DECAY), 0.999)
-        self.G_optim = optim.AdamTF(self.model.g_arena, float(t.G_BETA_DECAY), 0.999)
+        super().__init__(sess, model, dataset, cfg)
 
     def d_losses(self, feed, keep_g=False):
-        """What sess.run([D_optim, ...]) evaluates before the update (trainer.py:20-34,115-123).  Gradients -> d_arena.
+        """What sess.run([D_optim, ...]) evaluates before the update (trainer.py:20-34,115-123; the critic passes: model.py:48-51).
+        Gradients -> d_arena.
         keep_g (iteration() only): the generator is evaluated with its autograd graph and its moving averages move twice; the result is kept
         for g_losses(G=...) of the same iteration (see __init__)."""
         m = self.model
-        x, xw, phi, z = feed['inputs'], feed['wrong_inputs'], feed['phi_inputs'], feed['z']
         if keep_g:
             with update_ops(times=2):
-                self._shared_G = m.generator(z, phi, reuse=True)
+                self._shared_G = m.generator(feed['z'], feed['phi_inputs'], reuse=True)
             G = self._shared_G.detach()
-        with update_ops():      # D_optim is built under control_dependencies(UPDATE_OPS): every BN moving average moves
-            if not keep_g:
-                with torch.no_grad():
-                    G = m.generator(z, phi, reuse=True)
-            # the critic's three passes (fake / match / mismatch, model.py:48-51) as ONE stacked batch: per-sample layers run once on 3B
-            # samples, every batch norm keeps its statistics per pass (discriminator(groups=3))
-            _, logits = m.discriminator(torch.cat([G, x, xw], 0), torch.cat([phi, phi, phi], 0), reuse=True, _prob=False, groups=3)
-            B = x.shape[0]
-            lv = logits.detach().reshape(3, B)
-            seed = torch.empty(3 * B, dtype=torch.float32, device=logits.device)
-        # the three heads of trainer.py:20-34 in ONE launch (labels 0 / 0.9 one-sided smoothing / 0; D_loss = match + alpha mismatch +
-        # (1 - alpha) fake): the loss scalars, d D_loss / d logits as the seeds of the backward pass, and the sigmoid outputs
-        losses, _, probs = K.sigmoid_ce_head(list(lv), [0.0, 0.9, 0.0], [1.0 - self.alpha, 1.0, self.alpha], seeds_into=seed)
-        m.d_arena.zero_grad()
-        if m.dp is not None and not getattr(self, '_capturing', False):
-            m.dp.arm(m.d_arena)
-        torch.autograd.backward([logits], [seed.view_as(logits)], inputs=list(m.d_vars.values()))
-        A.side_join()
-        shape = (x.shape[0], 1, 1, 1)
-        return dict(D_loss=losses[0], D_real_match_loss=losses[2], D_real_mismatch_loss=losses[3], D_synthetic_loss=losses[1], G=G,
-                    D_synthetic=probs[0].view(shape), D_real_match=probs[1].view(shape), D_real_mismatch=probs[2].view(shape))
+        else:
+            with update_ops(), torch.no_grad():
+                G = m.generator(feed['z'], feed['phi_inputs'], reuse=True)
+        d, _, probs = self.critic_step(feed, G, want_prob=True)
+        shape = (G.shape[0], 1, 1, 1)
+        d.update(D_synthetic=probs[0].view(shape), D_real_match=probs[1].view(shape), D_real_mismatch=probs[2].view(shape))
+        return d
 
     def g_losses(self, feed, G=None):
         """G: the generator output d_losses(keep_g=True) evaluated for this iteration (with its autograd graph), or None: evaluate it here."""
-        m = self.model
-        x, xw, phi, z = feed['inputs'], feed['wrong_inputs'], feed['phi_inputs'], feed['z']
-        with update_ops():
-            if G is None:
-                G = m.generator(z, phi, reuse=True)
-            # G_optim also sits under ALL update ops of the graph: the match / mismatch critic passes run in this
-            # sess.run too, only to move their batch-norm moving averages (trainer.py:46-51)
-            if x.is_cuda:
-                # round 6: fake | match | mismatch as ONE stacked pass of three evaluations (stacked.py): every conv once on 3B rows, per-evaluation
-                # batch-norm statistics, the moving averages move once per evaluation in this order (as the three calls did); only the fake rows
-                # carry a gradient, so the backward runs on B rows as before
-                with m.store.frozen('d_net'):
-                    _, ls = m.discriminator(ST.Stacked(G, torch.cat([x, xw], 0)), ST.Stacked(phi, torch.cat([phi, phi], 0)), reuse=True, _prob=False,
-                                            groups=3)
-                l_fake = ls.main
-            else:
-                with m.store.frozen('d_net'):
-                    _, l_fake = m.discriminator(G, phi, reuse=True, _prob=False)
-                with torch.no_grad():
-                    m.discriminator(torch.cat([x, xw], 0), torch.cat([phi, phi], 0), reuse=True, _prob=False, groups=2)
-        losses, seeds, _ = K.sigmoid_ce_head([l_fake.detach().reshape(-1)], [1.0], [1.0], want_prob=False)      # G_loss: label 1 (trainer.py:36)
-        m.g_arena.zero_grad()
-        if m.dp is not None and not getattr(self, '_capturing', False):
-            m.dp.arm(m.g_arena)
-        torch.autograd.backward([l_fake], [seeds[0].view_as(l_fake)], inputs=list(m.g_vars.values()))
-        A.side_join()
+        if G is None:
+            with update_ops():
+                G = self.model.generator(feed['z'], feed['phi_inputs'], reuse=True)
+        losses = self.generator_step(feed, G)                     # G_loss: label 1 (trainer.py:36,46-51)
         return dict(G_loss=losses[0], G=G.detach())
-
-    # ---- device-only halves of an iteration (graph-capturable) ------------------------------------------------------------
-    def _d_body(self, feed, keep_g=False, refresh=None):
-        m = self.model
-        d = self.d_losses(feed, keep_g=keep_g)
-        scale = m.dp.allreduce_arena(m.d_arena) if m.dp is not None else 1.0
-        self.D_optim.apply(grad_scale=scale, refresh=refresh)
-        return d
-
-    def _g_body(self, feed, G=None):
-        m = self.model
-        g = self.g_losses(feed, G=G)
-        scale = m.dp.allreduce_arena(m.g_arena) if m.dp is not None else 1.0
-        self.G_optim.apply(grad_scale=scale)
-        return g
 
     def _dg_body(self, feed):
         """Both halves with ONE generator evaluation (see __init__); the critic's cached filter images are regenerated behind its Adam step,
         because the generator half of the same capture reads the updated filters."""
-        d = self._d_body(feed, keep_g=True, refresh=True)
+        s = self.schedule
+        d = s.step(s.d, feed, keep_g=True, refresh=True)
         G, self._shared_G = self._shared_G, None
-        return d, self._g_body(feed, G=G)
+        return d, s.step(s.g, feed, G=G)
+
+    def _joint(self):
+        """The one-body iteration, where it applies: single process only (under data parallelism the halves are separate segments)."""
+        return self._dg_body if self.share_g and self.model.dp is None else None
 
     def enable_graphs(self, feed):
         """Capture the iteration into hipGraphs and replay it from then on (call after one eager iteration): one graph for both halves when
-        the generator evaluation is shared (single process), else one per half.  With data parallelism each half is cut at its exchange step —
-        [losses + backward] | all-reduce of the gradient arena, issued eagerly | [Adam] — as in models/wgancls and models/stackgan: no
-        collective is ever captured."""
-        from ...graphs import StepGraphs
+        the generator evaluation is shared (single process), else one per half, cut at the exchange under data parallelism
+        (graphs.DGSchedule.capture)."""
         m = self.model
         self._graphs = StepGraphs(feed, ('inputs', 'wrong_inputs', 'phi_inputs', 'z'), filters=(m.d_arena.flat, m.g_arena.flat))
-        if m.dp is None:
-            if self.share_g:
-                self._graphs.capture('dg', self._dg_body)
-            else:
-                self._graphs.capture('d', self._d_body)
-                self._graphs.capture('g', self._g_body)
-            return
-        scale = 1.0 / m.dp.world
-        self._capturing = True
-        try:
-            self._graphs.capture('d', self.d_losses, capture_error_mode='thread_local')
-            self._graphs.capture('d_upd', lambda f: self.D_optim.apply(grad_scale=scale), capture_error_mode='thread_local', refresh=False)
-            self._graphs.capture('g', self.g_losses, capture_error_mode='thread_local')
-            self._graphs.capture('g_upd', lambda f: self.G_optim.apply(grad_scale=scale), capture_error_mode='thread_local', refresh=False)
-        finally:
-            self._capturing = False
+        self.schedule.capture(self._graphs, joint=self._joint())
 
     def iteration(self, feed):
-        lr_d, lr_g = float(self.cfg.TRAIN.D_LR), float(self.cfg.TRAIN.G_LR)
-        graphs = getattr(self, '_graphs', None)
-        dp = self.model.dp
-        if graphs is not None:
-            graphs.load(feed)
-            if 'dg' in graphs.graphs:
-                self.D_optim.prepare(lr_d)
-                self.G_optim.prepare(lr_g)
-                d, g = graphs.replay('dg')
-                return {'d': d, 'g': g}
-            self.D_optim.prepare(lr_d)
-            d = graphs.replay('d')
-            if dp is not None:
-                dp.allreduce_arena(self.model.d_arena)
-                graphs.replay('d_upd')
-            self.G_optim.prepare(lr_g)
-            g = graphs.replay('g')
-            if dp is not None:
-                dp.allreduce_arena(self.model.g_arena)
-                graphs.replay('g_upd')
-            return {'d': d, 'g': g}
-        if self.share_g and dp is None:
-            self.D_optim.prepare(lr_d)
-            self.G_optim.prepare(lr_g)
-            d, g = self._dg_body(feed)
-            return {'d': d, 'g': g}
-        self.D_optim.prepare(lr_d)
-        d = self._d_body(feed)
-        self.G_optim.prepare(lr_g)
-        return {'d': d, 'g': self._g_body(feed)}
-
-    def make_feed(self):
-        m = self.model
-        images, wrong_images, embed, _, _ = self.dataset.train.next_batch(m.batch_size, 4, embeddings=True, wrong_img=True)
-        return {'inputs': images, 'wrong_inputs': wrong_images, 'phi_inputs': embed,
-                'z': torch.randn((m.batch_size, m.z_dim), generator=self.gen, device=m.device)}
-
-    def define_summaries(self):
-        """reference trainer.py:53-75: the FileWriter on cfg.LOGS_DIR (utils/summary.py: TensorBoard event files without TensorFlow)."""
-        from ...utils.summary import FileWriter
-        self.writer = FileWriter(self.cfg.LOGS_DIR)
+        return self.schedule.run(feed, float(self.cfg.TRAIN.D_LR), float(self.cfg.TRAIN.G_LR), graphs=self._graphs, joint=self._joint())
 
     def write_summaries(self, counter, feed, out):
         """The two merged summaries the reference adds per update (trainer.py:66-72,115-134) — D: histograms of the three critic
@@ -254,7 +141,7 @@ class GanClsTrainer(object):
             for idx in range(updates_per_epoch):
                 feed = self.make_feed()
                 out = self.iteration(feed)
-                if graphs and getattr(self, '_graphs', None) is None:
+                if graphs and self._graphs is None:
                     self.enable_graphs(feed)
                 if getattr(self, 'writer', None) is not None:
                     self.write_summaries(counter, feed, out)

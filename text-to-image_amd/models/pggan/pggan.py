@@ -51,6 +51,7 @@ from ... import autograd as A
 from ... import kernels as K
 from ... import optim
 from ... import scope as S
+from ...graphs import DGSchedule, StepGraphs
 from ...utils.ops import (DiffAugmentSampler, concat_tile, conv2d, diff_augment, diff_augment_params, diff_augment_policy, downsample_2d, fc,
                           layer_norm, lerp, lrelu_act, minibatch_stddev_stat, pixel_norm, pool, relu, upsample_2d, upscale)
 
@@ -169,7 +170,6 @@ class PGGAN(object):
         # at local batch `batch_size`, critic and generator gradients all-reduced over RCCL, bucketed and overlapped with the
         # backward when eager, exchanged between captured graph segments under replay (same contract as models/wgancls)
         self.dp = dp
-        self._capturing = False
         if self.aug_sampler is None and (diffaug_p is not None or diffaug_adapt):
             # device tables with probability p; adapting alone starts from p = 0 like the publication; under
             # data parallelism each rank draws its own stream and steers its own p, as each rank draws its own table without this
@@ -217,6 +217,7 @@ class PGGAN(object):
                                         **({} if self.critic_spectral is None else {'spectral': self.critic_spectral}))
         self.G_optimizer = optim.AdamTF(self.g_arena, 0.0, 0.99, ema_decay=self.g_ema,       # (None: no shadow, the plain launch)
                                         slot_scales=self.kernel_scales(self.g_vars))
+        self.schedule = DGSchedule(self.dp, self.d_losses, self.d_arena, self.D_optimizer, self.g_losses, self.g_arena, self.G_optimizer)
 
     @staticmethod
     def kernel_names(variables):
@@ -296,11 +297,7 @@ class PGGAN(object):
         D_loss_real, D_loss_fake, D_loss_mismatch = Dx_logit.mean(), Dg_logit.mean(), Dxmi_logit.mean()
         wdist, wdist2 = D_loss_real - D_loss_fake, D_loss_real - D_loss_mismatch
         D_loss = -wdist - wdist2 + self.gp_coeff * (real_gp + real_gp2)
-        self.d_arena.zero_grad()
-        if self.dp is not None and not self._capturing:
-            self.dp.arm(self.d_arena)           # bucketed all-reduce overlaps the rest of this backward
-        D_loss.backward(inputs=list(self.d_vars.values()))
-        A.side_join()
+        self.schedule.backward(self.d_arena, [D_loss], None, self.d_vars.values())
         out = dict(D_loss=D_loss.detach(), wdist=wdist.detach(), wdist2=wdist2.detach(), real_gp=real_gp.detach(),
                    real_gp2=real_gp2.detach(), reg_loss=(Dxmi_logit.detach() ** 2).mean(), G=G, Dx_hat_logit=Dx_hat_logit.detach(),
                    D_loss_real=D_loss_real.detach(), D_loss_fake=D_loss_fake.detach(), D_loss_mismatch=D_loss_mismatch.detach())
@@ -326,11 +323,7 @@ class PGGAN(object):
             Dg_logit = self.discriminator(G_seen, cond, reuse=True, stages=self.stage, t=self.trans)
         G_kl_loss = self.kl_std_normal_loss(mean, log_sigma)
         G_loss = -Dg_logit.mean() + self.kl_coeff * G_kl_loss
-        self.g_arena.zero_grad()
-        if self.dp is not None and not self._capturing:
-            self.dp.arm(self.g_arena)
-        G_loss.backward(inputs=list(self.g_vars.values()))
-        A.side_join()
+        self.schedule.backward(self.g_arena, [G_loss], None, self.g_vars.values())
         return dict(G_loss=G_loss.detach(), G_kl_loss=G_kl_loss.detach(), G=G.detach(), D_loss_fake=Dg_logit.detach().mean())
 
     def set_alpha(self, value):
@@ -338,22 +331,15 @@ class PGGAN(object):
         self._alpha_dev.fill_(self.alpha_tra)
 
     def _d_body(self, feed):
-        d = self.d_losses(feed)
-        scale = self.dp.allreduce_arena(self.d_arena) if self.dp is not None else 1.0
-        self.D_optimizer.apply(grad_scale=scale)
-        return d
+        return self.schedule.step(self.schedule.d, feed)
 
     def _g_body(self, feed):
-        g = self.g_losses(feed)
-        scale = self.dp.allreduce_arena(self.g_arena) if self.dp is not None else 1.0
-        self.G_optimizer.apply(grad_scale=scale)
-        return g
+        return self.schedule.step(self.schedule.g, feed)
 
     def enable_graphs(self, feed):
-        """Capture the two halves of the iteration into hipGraphs (call after one eager iteration).  alpha then lives in
-        device memory, and the in-graph random draws of the reference (eps of x_hat, the conditioning noise) become static
-        buffers that are re-drawn before every replay."""
-        from ...graphs import StepGraphs
+        """Capture the two halves of the iteration into hipGraphs (call after one eager iteration), cut at the exchange under data
+        parallelism (graphs.DGSchedule.capture).  alpha then lives in device memory, and the in-graph random draws of the reference
+        (eps of x_hat, the conditioning noise) become static buffers that are re-drawn before every replay."""
         B, dev = feed['x'].shape[0], self.device
         feed = dict(feed)
         drawn = (('eps_graph', (B,)), ('ca_noise_d', (B, self.compr_embed_dim)), ('ca_noise_g', (B, self.compr_embed_dim)))
@@ -368,21 +354,7 @@ class PGGAN(object):
                                   filters=(self.d_arena.flat, self.g_arena.flat))
         self._redraw(feed)
         self._graphs.load(feed)
-        if self.dp is None:
-            self._graphs.capture('d', self._d_body)
-            self._graphs.capture('g', self._g_body)
-            return
-        # data parallelism: each half is cut at its exchange step — [losses + backward] | all-reduce (eager, never captured)
-        # | [Adam]; thread-local capture mode because the process group's watchdog thread polls events meanwhile
-        scale = 1.0 / self.dp.world
-        self._capturing = True
-        try:
-            self._graphs.capture('d', self.d_losses, capture_error_mode='thread_local')
-            self._graphs.capture('d_upd', lambda f: self.D_optimizer.apply(grad_scale=scale), capture_error_mode='thread_local', refresh=False)
-            self._graphs.capture('g', self.g_losses, capture_error_mode='thread_local')
-            self._graphs.capture('g_upd', lambda f: self.G_optimizer.apply(grad_scale=scale), capture_error_mode='thread_local', refresh=False)
-        finally:
-            self._capturing = False
+        self.schedule.capture(self._graphs)
 
     def _redraw(self, feed):
         st = self._graphs.static
@@ -404,22 +376,7 @@ class PGGAN(object):
             if self.aug_sampler is not None and any(feed.get(k) is not None and k not in self._graphs.static for k in ('aug_d', 'aug_g')):
                 raise ValueError('a parameter table is fed, but the graphs were captured drawing it: feed aug_d / aug_g to enable_graphs too')
             self._redraw(feed)
-            self._graphs.load(feed)
-            self.D_optimizer.prepare(self.adam_lr)
-            d = self._graphs.replay('d')
-            if self.dp is not None:
-                self.dp.allreduce_arena(self.d_arena)
-                self._graphs.replay('d_upd')
-            self.G_optimizer.prepare(self.adam_lr)
-            g = self._graphs.replay('g')
-            if self.dp is not None:
-                self.dp.allreduce_arena(self.g_arena)
-                self._graphs.replay('g_upd')
-            return {'d': d, 'g': g}
-        self.D_optimizer.prepare(self.adam_lr)
-        d = self._d_body(feed)
-        self.G_optimizer.prepare(self.adam_lr)
-        return {'d': d, 'g': self._g_body(feed)}
+        return self.schedule.run(feed, self.adam_lr, self.adam_lr, graphs=self._graphs)
 
     @contextlib.contextmanager
     def ema_weights(self):

@@ -6,28 +6,19 @@ import time
 
 import torch
 
-from .... import autograd as A
-from .... import stacked as ST
 from .... import kernels as K
-from .... import optim
+from ....graphs import StepGraphs
 from ....utils.ops import update_ops
+from ...cgan_trainer import CGanTrainer
 
 
-class ConditionalGanTrainer(object):
+class ConditionalGanTrainer(CGanTrainer):
     REAL_LABEL = 0.9                     # trainer.py:26 (Stage-II overrides with 0.95)
-    batched = True                       # the critic's passes of one sess.run are one stacked batch (always, as in models/gancls)
 
     def __init__(self, sess, model, dataset, cfg):
-        self.sess, self.model, self.dataset, self.cfg = sess, model, dataset, cfg     # sess unused (no TF session)
         self.lr = float(cfg.TRAIN.D_LR)
-        self.gen = torch.Generator(device=model.device).manual_seed(1234)
-        self.define_losses()
-
-    def define_losses(self):
-        t = self.cfg.TRAIN
-        self.alpha, self.kl_coeff = float(t.COEFF.ALPHA_MISMATCH_LOSS), float(t.COEFF.KL)
-        self.D_optim = optim.AdamTF(self.model.d_arena, float(t.D_BETA_DECAY), 0.999)
-        self.G_optim = optim.AdamTF(self.model.g_arena, float(t.G_BETA_DECAY), 0.999)
+        self.kl_coeff = float(cfg.TRAIN.COEFF.KL)
+        super().__init__(sess, model, dataset, cfg)
 
     @staticmethod
     def kl_loss(mean, log_sigma):
@@ -40,84 +31,29 @@ class ConditionalGanTrainer(object):
 
     def d_losses(self, feed):
         """What sess.run([D_optim, ...]) evaluates before the update (trainer.py:19-41).  Gradients -> d_arena."""
-        m = self.model
-        x, xw, phi = feed['inputs'], feed['wrong_inputs'], feed['phi_inputs']
-        with update_ops():      # D_optim sits under control_dependencies(UPDATE_OPS): every BN moving average moves
-            with torch.no_grad():
-                G, _, _ = self._generate(feed, 'd')
-            # fake | match | mismatch stacked along the batch axis, batch-norm statistics per pass (models/gancls)
-            _, logits = m.discriminator(torch.cat([G, x, xw], 0), torch.cat([phi, phi, phi], 0), reuse=True, _prob=False, groups=3)
-            B = x.shape[0]
-            heads = list(logits.detach().reshape(3, B))
-            seed = torch.empty(3 * B, dtype=torch.float32, device=logits.device)
-        # the three heads (trainer.py:24-33) in one launch: loss scalars + d D_loss / d logits as the seeds of the backward pass
-        losses, _, _ = K.sigmoid_ce_head(heads, [0.0, self.REAL_LABEL, 0.0], [1.0 - self.alpha, 1.0, self.alpha], want_prob=False, seeds_into=seed)
-        m.d_arena.zero_grad()
-        if m.dp is not None and not getattr(self, '_capturing', False):
-            m.dp.arm(m.d_arena)
-        torch.autograd.backward([logits], [seed.view_as(logits)], inputs=list(m.d_vars.values()))
-        A.side_join()
+        with update_ops(), torch.no_grad():
+            G, _, _ = self._generate(feed, 'd')
+        d, heads, _ = self.critic_step(feed, G, want_prob=False)      # the three heads: trainer.py:24-33
         # the three critic outputs (fake, match, mismatch logits) ride along for the D summary's histograms (trainer.py:59-61)
-        return dict(D_loss=losses[0], D_real_match_loss=losses[2], D_real_mismatch_loss=losses[3], D_synthetic_loss=losses[1], G=G,
-                    D_logits=heads)
-
-    def g_losses(self, feed):
-        m = self.model
-        x, xw, phi = feed['inputs'], feed['wrong_inputs'], feed['phi_inputs']
-        with update_ops():
-            G, mean, log_sigma = self._generate(feed, 'g')
-            # G_optim also sits under ALL update ops of the graph: the match / mismatch critic passes run in this
-            # sess.run too, only to move their batch-norm moving averages (trainer.py:50-55)
-            if x.is_cuda:
-                # round 6: fake | match | mismatch as ONE stacked pass of three evaluations (stacked.py): every conv once on 3B rows, per-evaluation
-                # batch-norm statistics, the moving averages move once per evaluation in this order (as the three calls did); only the fake rows
-                # carry a gradient, so the backward runs on B rows as before
-                with m.store.frozen(m.d_scope):
-                    _, ls = m.discriminator(ST.Stacked(G, torch.cat([x, xw], 0)), ST.Stacked(phi, torch.cat([phi, phi], 0)), reuse=True, _prob=False,
-                                            groups=3)
-                l_fake = ls.main
-            else:
-                with m.store.frozen(m.d_scope):
-                    _, l_fake = m.discriminator(G, phi, reuse=True, _prob=False)
-                with torch.no_grad():
-                    m.discriminator(torch.cat([x, xw], 0), torch.cat([phi, phi], 0), reuse=True, _prob=False, groups=2)
-        # G_loss = CE(fake, 1) + kl_coeff * KL (trainer.py:35-41): the CE head gives its value and d/d logits; the KL term stays a
-        # differentiable tensor expression, so the two are seeded together
-        losses, seeds, _ = K.sigmoid_ce_head([l_fake.detach().reshape(-1)], [1.0], [1.0], want_prob=False)
-        G_gan_loss = losses[1]
-        G_kl_loss = self.kl_loss(mean, log_sigma)
-        m.g_arena.zero_grad()
-        if m.dp is not None and not getattr(self, '_capturing', False):
-            m.dp.arm(m.g_arena)
-        torch.autograd.backward([l_fake, G_kl_loss], [seeds[0].view_as(l_fake), torch.full_like(G_kl_loss, self.kl_coeff)],
-                                inputs=list(m.g_vars.values()))
-        A.side_join()
-        G_loss = G_gan_loss + self.kl_coeff * G_kl_loss.detach()
-        return dict(G_loss=G_loss, G_gan_loss=G_gan_loss, G_kl_loss=G_kl_loss.detach(), G=G.detach())
-
-    # ---- device-only halves of an iteration (graph-capturable: Adam reads its step size from device memory) -----------------
-    def _d_body(self, feed):
-        m = self.model
-        d = self.d_losses(feed)
-        scale = m.dp.allreduce_arena(m.d_arena) if m.dp is not None else 1.0
-        self.D_optim.apply(grad_scale=scale)
+        d['D_logits'] = heads
         return d
 
-    def _g_body(self, feed):
-        m = self.model
-        g = self.g_losses(feed)
-        scale = m.dp.allreduce_arena(m.g_arena) if m.dp is not None else 1.0
-        self.G_optim.apply(grad_scale=scale)
-        return g
+    def g_losses(self, feed):
+        with update_ops():
+            G, mean, log_sigma = self._generate(feed, 'g')
+        # G_loss = CE(fake, 1) + kl_coeff * KL (trainer.py:35-41,50-55): the KL term stays a differentiable tensor expression, seeded with
+        # kl_coeff next to the CE head's d/d logits
+        G_kl_loss = self.kl_loss(mean, log_sigma)
+        G_gan_loss = self.generator_step(feed, G, [G_kl_loss], [torch.full_like(G_kl_loss, self.kl_coeff)])[1]
+        G_loss = G_gan_loss + self.kl_coeff * G_kl_loss.detach()
+        return dict(G_loss=G_loss, G_gan_loss=G_gan_loss, G_kl_loss=G_kl_loss.detach(), G=G.detach())
 
     NOISE_KEYS = ('ca_noise_d', 'ca_noise_g')
 
     def enable_graphs(self, feed):
-        """Capture the two halves into hipGraphs and replay them from then on.  Call after at least one eager iteration with
-        the same shapes.  The conditioning-augmentation noise lives in static buffers that are re-drawn before every replay
-        (the reference draws it inside the graph on every run).  With data parallelism each half is cut at its exchange
-        step — [losses + backward] | all-reduce of the gradient arena, issued eagerly | [Adam] — as in models/wgancls."""
-        from ....graphs import StepGraphs
+        """Capture the two halves into hipGraphs and replay them from then on, cut at the exchange under data parallelism
+        (graphs.DGSchedule.capture).  Call after at least one eager iteration with the same shapes.  The conditioning-augmentation
+        noise lives in static buffers that are re-drawn before every replay (the reference draws it inside the graph on every run)."""
         m = self.model
         feed = dict(feed)
         for k in self.NOISE_KEYS:
@@ -127,19 +63,7 @@ class ConditionalGanTrainer(object):
                                   filters=(m.d_arena.flat, m.g_arena.flat))
         self._draw_noise(feed)
         self._graphs.load(feed)
-        if m.dp is None:
-            self._graphs.capture('d', self._d_body)
-            self._graphs.capture('g', self._g_body)
-            return
-        scale = 1.0 / m.dp.world
-        self._capturing = True
-        try:
-            self._graphs.capture('d', self.d_losses, capture_error_mode='thread_local')
-            self._graphs.capture('d_upd', lambda f: self.D_optim.apply(grad_scale=scale), capture_error_mode='thread_local', refresh=False)
-            self._graphs.capture('g', self.g_losses, capture_error_mode='thread_local')
-            self._graphs.capture('g_upd', lambda f: self.G_optim.apply(grad_scale=scale), capture_error_mode='thread_local', refresh=False)
-        finally:
-            self._capturing = False
+        self.schedule.capture(self._graphs)
 
     def _noise_dim(self, key):
         return self.model.compressed_embed_dim
@@ -151,38 +75,9 @@ class ConditionalGanTrainer(object):
 
     def iteration(self, feed, epoch=0):
         lr = self.lr * (0.5 ** (epoch // 100))                       # trainer.py:119,127
-        graphs = getattr(self, '_graphs', None)
-        if graphs is not None:
+        if self._graphs is not None:
             self._draw_noise(feed)
-            graphs.load(feed)
-            dp = self.model.dp
-            self.D_optim.prepare(lr)
-            d = graphs.replay('d')
-            if dp is not None:
-                dp.allreduce_arena(self.model.d_arena)
-                graphs.replay('d_upd')
-            self.G_optim.prepare(lr)
-            g = graphs.replay('g')
-            if dp is not None:
-                dp.allreduce_arena(self.model.g_arena)
-                graphs.replay('g_upd')
-            return {'d': d, 'g': g}
-        self.D_optim.prepare(lr)
-        d = self._d_body(feed)
-        self.G_optim.prepare(lr)
-        g = self._g_body(feed)
-        return {'d': d, 'g': g}
-
-    def make_feed(self):
-        m = self.model
-        images, wrong_images, embed, _, _ = self.dataset.train.next_batch(m.batch_size, 4, embeddings=True, wrong_img=True)
-        return {'inputs': images, 'wrong_inputs': wrong_images, 'phi_inputs': embed,
-                'z': torch.randn((m.batch_size, m.z_dim), generator=self.gen, device=m.device)}
-
-    def define_summaries(self):
-        """reference trainer.py:58-87: the FileWriter on cfg.LOGS_DIR (utils/summary.py: TensorBoard event files without TensorFlow)."""
-        from ....utils.summary import FileWriter
-        self.writer = FileWriter(self.cfg.LOGS_DIR)
+        return self.schedule.run(feed, lr, lr, graphs=self._graphs)
 
     def write_summaries(self, counter, out):
         """The two merged summaries the reference adds per update (trainer.py:72-85,134-141).  D: histograms of the three critic
@@ -260,7 +155,7 @@ class ConditionalGanTrainer(object):
             for idx in range(updates_per_epoch):
                 feed = self.make_feed()
                 out = self.iteration(feed, epoch)
-                if graphs and getattr(self, '_graphs', None) is None:
+                if graphs and self._graphs is None:
                     self.enable_graphs(feed)
                 if getattr(self, 'writer', None) is not None:
                     self.write_summaries(counter, out)
