@@ -956,6 +956,42 @@ int t2i_upfirdn2d(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, co
 int t2i_upfirdn2d_axes(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, const float* taps, int32_t n, int32_t u, int32_t d,
                        int32_t p0, int32_t p1_h, int32_t p1_w, int32_t flip, float* y, t2i_stream_t stream);
 
+/* ---- the style-based generator's layer epilogue: per-pixel noise, activation, instance norm and the style's affine map (AdaIN; Karras
+ * et al., CVPR 2019).  csrc/t2i_style.hip, DESIGN.md section 4.42.  Added within ABI v13: no existing argument list changed. ------------
+ * x [B,R,C] (R = H W, contiguous NHWC fp32), noise [B,R] and strength [C] (both or neither: NULL), ys and yb [B,C] whose rows lie
+ * style_stride >= C floats apart (the two halves of one dense layer's [B,2C] output need no copy):
+ *   u = act(x + strength[c] noise[b,r])     act: T2I_ACT_NONE, T2I_ACT_RELU or T2I_ACT_LRELU with alpha >= 0; without noise u = act(x)
+ *   mean[b,c], var[b,c] = the biased moments of u over r,    rstd = rsqrt(var + eps)
+ *   y = (u - mean) rstd (1 + ys[b,c]) + yb[b,c]
+ * _stats  (2 launches) per-chunk (mean, M2) by Welford's update for each (b, chunk of T2I_ADAIN_CHUNK_ROWS rows, c) into the workspace, then
+ *         their merge in ascending chunk order by Chan's update -> mean [B,C], rstd [B,C]; never E[u^2] - mean^2.
+ * _apply  (1 launch) recomputes u and writes y; no plane of u or of the normalised u is ever stored.
+ * _bwd_sums (2 launches) for the cotangent g of y: dyb [B,C] = sum_r g, dys [B,C] = sum_r g uh, uh = (u - mean) rstd recomputed.
+ * _bwd_apply (1 launch, 2 with dstrength) dx = act'(u) rstd (1 + ys) (g - dyb / R - uh dys / R), act' from the sign of the recomputed
+ *         pre-activation; dstrength [C] (or NULL; needs noise) = sum_{b,r} dx noise, per-item partials summed in a fixed order.  noise gets
+ *         no gradient.
+ * A 16-byte form when C % 4 == 0 and the [B,R,C] tensors of the call are 16-byte aligned, a scalar form otherwise.  A grid of at most 65535
+ * workgroups walks the items with a stride.  No atomics; the split depends on R and C alone: mean, rstd, y, dx, dys and dyb of a sample do
+ * not depend on its batch, and calls repeat bit for bit.  Graph-capturable: no allocation, no synchronisation, nothing read back.
+ * Refused with T2I_ERR_INVALID before any launch: a NULL pointer (noise, strength and dstrength apart); a size < 1; 2^31 elements or more;
+ * another activation or a negative slope; noise without strength or the reverse; dstrength without noise; style_stride < C; eps negative or
+ * not finite; an output overlapping x or g.  A workspace that is NULL, not 16-byte aligned or smaller than t2i_adain_workspace_bytes
+ * (0 for a refused shape) returns T2I_ERR_WORKSPACE (_bwd_apply reads it only with dstrength). */
+#define T2I_ADAIN_CHUNK_ROWS 64
+int32_t t2i_adain_chunk_rows(void);
+size_t t2i_adain_workspace_bytes(int32_t B, int64_t R, int32_t C);
+int t2i_adain_stats(const float* x, const float* noise, const float* strength, int32_t B, int64_t R, int32_t C, int act, float alpha,
+                    float eps, float* mean, float* rstd, void* ws, size_t ws_bytes, t2i_stream_t stream);
+int t2i_adain_apply(const float* x, const float* noise, const float* strength, const float* mean, const float* rstd, const float* ys,
+                    const float* yb, int32_t style_stride, int32_t B, int64_t R, int32_t C, int act, float alpha, float* y,
+                    t2i_stream_t stream);
+int t2i_adain_bwd_sums(const float* g, const float* x, const float* noise, const float* strength, const float* mean, const float* rstd,
+                       int32_t B, int64_t R, int32_t C, int act, float alpha, float* dys, float* dyb, void* ws, size_t ws_bytes,
+                       t2i_stream_t stream);
+int t2i_adain_bwd_apply(const float* g, const float* x, const float* noise, const float* strength, const float* mean, const float* rstd,
+                        const float* ys, int32_t style_stride, const float* dys, const float* dyb, int32_t B, int64_t R, int32_t C,
+                        int act, float alpha, float* dx, float* dstrength, void* ws, size_t ws_bytes, t2i_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

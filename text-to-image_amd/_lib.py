@@ -179,6 +179,12 @@ SIGNATURES = {
     't2i_upfirdn2d_extent': (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
     't2i_upfirdn2d': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p]),
     't2i_upfirdn2d_axes': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p]),
+    't2i_adain_chunk_rows': (_i32, []),
+    't2i_adain_workspace_bytes': (_sz, [_i32, _i64, _i32]),
+    't2i_adain_stats': (ctypes.c_int, [_p, _p, _p, _i32, _i64, _i32, ctypes.c_int, _f, _f, _p, _p, _p, _sz, _p]),
+    't2i_adain_apply': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, ctypes.c_int, _f, _p, _p]),
+    't2i_adain_bwd_sums': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i64, _i32, ctypes.c_int, _f, _p, _p, _p, _sz, _p]),
+    't2i_adain_bwd_apply': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _i32, _i64, _i32, ctypes.c_int, _f, _p, _p, _p, _sz, _p]),
 }
 
 if not os.path.exists(LIB_PATH):

@@ -1073,3 +1073,43 @@ class BatchRenormTrainFn(Function):
         dx, g_xhat, dbeta = K.bn_bwd(gy, x, mean, rstd, (gamma * r).contiguous(), sum_dy, sum_dy_x)      # g_xhat = sum g * xhat
         dgamma = r * g_xhat + d * dbeta
         return (dx, dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None) + (None,) * 6
+
+
+class AdaINFn(Function):
+    """The style-based generator's layer epilogue (Karras et al. 2019; not in the reference):
+    u = act(x + strength[c] noise[b,h,w]) (u = act(x) without noise), instance norm over (h, w), y = uhat (1 + ys) + yb.  Saves x, noise,
+    strength, ys, mean and rstd only: the backward recomputes u.  noise gets no gradient.  First order: the generator is never under
+    the gradient penalty, so the backward of the backward (AdaINBwdFn.backward) raises NotImplementedError."""
+
+    @staticmethod
+    def forward(ctx, x, ys, yb, noise, strength, act, alpha, eps):
+        y, mean, rstd = K.adain_fwd(x, ys, yb, noise, strength, act, alpha, eps)
+        ctx.save_for_backward(x, ys, noise, strength, mean, rstd)
+        ctx.act, ctx.alpha = act, alpha
+        ctx.set_materialize_grads(False)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        if gy is None:
+            return (None,) * 8
+        x, ys, noise, strength, mean, rstd = ctx.saved_tensors
+        want_strength = strength is not None and ctx.needs_input_grad[4] and not _INPUTS_ONLY[0]
+        dx, dstrength, dys, dyb = AdaINBwdFn.apply(gy, x, ys, noise, strength, mean, rstd, ctx.act, ctx.alpha, want_strength)
+        return dx, dys, dyb, None, dstrength, None, None, None
+
+
+class AdaINBwdFn(Function):
+    """(dx, dstrength, dys, dyb) of AdaINFn from gy: three launches, four with dstrength (want_strength = False under
+    input_grads_only: its reduction is not launched and None is returned).  Not differentiable."""
+
+    @staticmethod
+    def forward(ctx, gy, x, ys, noise, strength, mean, rstd, act, alpha, want_strength):
+        ctx.set_materialize_grads(False)
+        return K.adain_bwd(_c(gy), x, ys, mean, rstd, noise, strength, act, alpha, want_strength)
+
+    @staticmethod
+    def backward(ctx, *v):
+        raise NotImplementedError('adain: a second differentiation is not implemented - the layer belongs to the generator, which no '
+                                  'gradient penalty differentiates (the penalty is a gradient of the critic with respect to images); '
+                                  'a critic that needs a twice-differentiable norm has layer_norm and pixel_norm')

@@ -2192,6 +2192,71 @@ def upfirdn2d(x, taps, u, d, p0, p1, flip, out=None):
     return out
 
 
+# ---- the style-based generator's layer epilogue: noise, activation, instance norm, style (csrc/t2i_style.hip) ----
+ADAIN_CHUNK_ROWS = int(lib.t2i_adain_chunk_rows())      # rows of a sample per work item (include/t2i_hip.h T2I_ADAIN_CHUNK_ROWS)
+
+
+def _style_rows(t, name, B, C):
+    """ys / yb: float32 [B,C] with unit stride along C and rows any stride >= C apart (the halves of a dense layer's [B,2C] output)."""
+    if t.dtype != torch.float32 or tuple(t.shape) != (B, C) or t.stride(1) != 1 or (B > 1 and t.stride(0) < C):
+        raise ValueError('adain: %s must be a float32 [%d, %d] with unit stride along the channels, got %s %s strides %s' % (
+            name, B, C, t.dtype, tuple(t.shape), t.stride()))
+    return t.stride(0) if B > 1 else C
+
+
+def _adain_args(x, noise, strength):
+    _chk(x, 'x', f32=True)
+    if x.dim() != 4 or min(x.shape) < 1 or x.numel() >= 1 << 31:
+        raise ValueError('adain: x must be [B,H,W,C] with every size at least 1 and fewer than 2^31 elements, got %s' % (tuple(x.shape),))
+    B, H, W, C = x.shape
+    if (noise is None) != (strength is None):
+        raise ValueError('adain: noise and strength come together or not at all')
+    if noise is not None:
+        _chk(noise, 'noise', f32=True); _chk(strength, 'strength', f32=True)
+        if tuple(noise.shape) != (B, H, W) or tuple(strength.shape) != (C,):
+            raise ValueError('adain: noise must be [%d, %d, %d] and strength [%d], got %s and %s' % (B, H, W, C, tuple(noise.shape), tuple(strength.shape)))
+    return B, H * W, C
+
+
+def adain_fwd(x, ys, yb, noise=None, strength=None, act=ACT_NONE, alpha=0.2, eps=1e-8):
+    """x [B,H,W,C] -> (y, mean [B,C], rstd [B,C]) with u = act(x + strength[c] noise[b,h,w]) (u = act(x) without noise), the biased
+    moments of u over (h, w) and y = (u - mean) rstd (1 + ys) + yb.  Three launches: chunk moments, their merge, apply."""
+    B, R, C = _adain_args(x, noise, strength)
+    sstride = _style_rows(ys, 'ys', B, C)
+    if _style_rows(yb, 'yb', B, C) != sstride:
+        raise ValueError('adain: ys and yb must have the same row stride, got %d and %d' % (ys.stride(0), yb.stride(0)))
+    y = torch.empty_like(x)
+    mean = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    if _live(x):
+        wsp, wsn = _ws_args(x, int(lib.t2i_adain_workspace_bytes(B, R, C)))
+        check(lib.t2i_adain_stats(_ptr(x), _ptr(noise), _ptr(strength), B, R, C, act, alpha, float(eps), _ptr(mean), _ptr(rstd), wsp, wsn,
+                                  _stream()), 't2i_adain_stats')
+        check(lib.t2i_adain_apply(_ptr(x), _ptr(noise), _ptr(strength), _ptr(mean), _ptr(rstd), _ptr(ys), _ptr(yb), sstride, B, R, C, act, alpha,
+                                  _ptr(y), _stream()), 't2i_adain_apply')
+    return y, mean, rstd
+
+
+def adain_bwd(g, x, ys, mean, rstd, noise=None, strength=None, act=ACT_NONE, alpha=0.2, want_strength=True):
+    """The first-order backward of adain_fwd for the cotangent g of y -> (dx, dstrength [C] or None, dys [B,C], dyb [B,C]); u is
+    recomputed from x.  Three launches, four with dstrength (only with noise, and only when wanted)."""
+    B, R, C = _adain_args(x, noise, strength)
+    _chk(g, 'g', f32=True); _chk(mean, 'mean', f32=True); _chk(rstd, 'rstd', f32=True)
+    assert g.shape == x.shape and tuple(mean.shape) == (B, C) and tuple(rstd.shape) == (B, C)
+    sstride = _style_rows(ys, 'ys', B, C)
+    dx = torch.empty_like(x)
+    dys = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    dyb = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    dstrength = torch.empty((C,), dtype=torch.float32, device=x.device) if (noise is not None and want_strength) else None
+    if _live(x):
+        wsp, wsn = _ws_args(x, int(lib.t2i_adain_workspace_bytes(B, R, C)))
+        check(lib.t2i_adain_bwd_sums(_ptr(g), _ptr(x), _ptr(noise), _ptr(strength), _ptr(mean), _ptr(rstd), B, R, C, act, alpha, _ptr(dys),
+                                     _ptr(dyb), wsp, wsn, _stream()), 't2i_adain_bwd_sums')
+        check(lib.t2i_adain_bwd_apply(_ptr(g), _ptr(x), _ptr(noise), _ptr(strength), _ptr(mean), _ptr(rstd), _ptr(ys), sstride, _ptr(dys),
+                                      _ptr(dyb), B, R, C, act, alpha, _ptr(dx), _ptr(dstrength), wsp, wsn, _stream()), 't2i_adain_bwd_apply')
+    return dx, dstrength, dys, dyb
+
+
 # ---- sliced Wasserstein distance (csrc/t2i_swd.hip; evaluation/swd.py is the caller) -----------------------------------------
 def _f32_nd(t, name, dim):
     if t.dtype != torch.float32 or t.dim() != dim or not t.is_contiguous():

@@ -2,6 +2,7 @@
 
     python text-to-image_amd/models/pggan/eval_pggan.py --cfg models/pggan/cfg/flowers.yml --eval is|fid|swd|msssim|prdc|mmd [--stage 7] [--batch 64]
                                                         [--msssim-pairs random|caption] [--prdc-k K] [--mmd-subsets S] [--mmd-subset-size M]
+                                                        [--style-dim D [--mapping-layers N] [--no-style-noise] [--truncation-psi PSI]]
 
 The generator's variables (`g_net`) are restored from CHECKPOINT_DIR/stage%d/; a failed load raises with the reference's
 message.  The dataset is `TextDataset(DATASET_DIR, MODEL.SIZES[stage - 1])` (256 at stage 7, as the reference reads).  Per batch
@@ -70,8 +71,18 @@ def restore_generator(m, ema=False):
     """ema=True: the moving average of the weights that `train_pggan.py --g-ema` keeps in the checkpoint, as the weights.
     The checkpoint's resampling taps (`g_net/resample_filter`, written by `train_pggan.py --resample-filter`) must be the model's:
     a difference — the key present in a model without taps and the taps given for a checkpoint without the key included — raises
-    RuntimeError naming both sides, because the weights would otherwise be sampled through another generator."""
-    from t2i_amd.models.pggan.pggan import RESAMPLE_KEY, describe_taps, same_taps
+    RuntimeError naming both sides, because the weights would otherwise be sampled through another generator.  Likewise the style-based
+    generator (`train_pggan.py --style-dim`): a checkpoint whose generator was built with another --style-dim, --mapping-layers or
+    --no-style-noise than the model raises RuntimeError naming the flags, before any variable is read."""
+    from t2i_amd.models.pggan.pggan import RESAMPLE_KEY, describe_style, describe_taps, same_taps, style_of_names
+    names = checkpoint_names(m.check_dir_read)
+    if names is not None:
+        ckpt_style, model_style = style_of_names(names), (m.style_dim, m.mapping_layers if m.style_dim is not None else None,
+                                                          m.style_noise if m.style_dim is not None else None)
+        if ckpt_style != model_style:
+            raise RuntimeError('the checkpoint in %s holds %s, but this model was built with %s: pass the same --style-dim / --mapping-layers / '
+                               '--no-style-noise (style_dim=, mapping_layers=, style_noise=) the trainer was given' % (
+                                   m.check_dir_read, describe_style(ckpt_style), describe_style(model_style)))
     found = []
     restore_scopes(m.store, [('g_net', m.check_dir_read)], error=lambda scope: RuntimeError('Could not load stage %d' % m.stage), verbose=False,
                    ema=ema, extra={RESAMPLE_KEY: ((lambda: None), found.append)})
@@ -81,10 +92,26 @@ def restore_generator(m, ema=False):
                            '(resample_filter=) the trainer was given' % (m.check_dir_read, describe_taps(ckpt), describe_taps(m.resample_taps)))
 
 
+def checkpoint_names(directory):
+    """{variable name: shape} of the generator's mapping-network and style-block entries in the newest checkpoint of `directory` (what
+    utils/saver.load would read); None when there is no checkpoint."""
+    import re
+    import numpy as np
+    state = os.path.join(directory, 'checkpoint')
+    if not os.path.isfile(state):
+        return None
+    found = re.search(r'model_checkpoint_path: "([^"]+)"', open(state).read())
+    if not found or not os.path.isfile(os.path.join(directory, os.path.basename(found.group(1)))):
+        return None
+    with np.load(os.path.join(directory, os.path.basename(found.group(1)))) as z:
+        return {k: tuple(z[k].shape) for k in z.files if k.startswith('g_net/mapping/') or '/StyleMod' in k}
+
+
 def generate(m, z, cond, cond_noise=True):
     """The stage generator on device tensors (fresh truncated-normal conditioning noise when cond_noise), clipped to [-1, 1]."""
     with torch.no_grad():
         m._ca = None
+        m._sn = None                   # (style_dim: fresh style noise; the constructor's truncation_psi applies)
         img, _, _ = m.generator(z, cond, stages=m.stage, t=False, reuse=True, cond_noise=cond_noise)
         return torch.clamp(img.float(), -1.0, 1.0).contiguous()
 
@@ -131,8 +158,10 @@ def main(argv=None, **widths):
     ap.add_argument('--incep-batch', type=int, default=None, help='Inception batch (default: --batch)')
     ap.add_argument('--ema', action='store_true', help="score the moving average of the generator's weights (a checkpoint of train_pggan.py --g-ema)")
     cli.add_resample_filter_argument(ap)
+    cli.add_style_arguments(ap)
     args = ap.parse_args(argv)
     taps = cli.resample_filter_of(ap, args)
+    widths = dict(widths, **cli.style_kwargs_of(ap, args))
     if not 1 <= args.stage <= 8:
         ap.error('--stage must be in 1..8')
     if args.batch < 1 or (args.incep_batch is not None and args.incep_batch < 1):

@@ -30,7 +30,13 @@ normalised weights, and checkpoints also carry `<variable>/spectral_raw`, `_u`, 
 generator's nearest x2 `upscale` by utils.ops.upsample_2d and the critic's 2x2 `pool` by utils.ops.downsample_2d with those taps, in the
 blocks and in both fade-in branches (Karras et al. 2019, Zhang 2019): one launch of csrc/t2i_resample.hip each,
 differentiable to any order.  This changes the generator's function, so checkpoints carry the normalised taps as `g_net/resample_filter`
-and the readers (eval_pggan.restore_generator) refuse a checkpoint whose taps differ from the model's.  `adam_lr=L` sets Adam's step size (default None: the reference's 2e-6).  Reference specifics kept: penalty
+and the readers (eval_pggan.restore_generator) refuse a checkpoint whose taps differ from the model's.
+`style_dim=D` (default None = the reference's generator: today's variables, launches and checkpoint files) builds the style-based generator
+of Karras et al. 2019 (`_style_generator`): a mapping network `g_net/mapping` turns [z, c] into a style vector w,
+and every conv -> layer_norm(relu) pair of the generator becomes conv -> utils.ops.style_block (per-pixel noise, relu, instance norm, an
+affine map of w: csrc/t2i_style.hip); `mapping_layers`, `style_noise` and `truncation_psi` configure it, `feed['style_noise_{d,g}_<k>']`
+carry the noise images (drawn when missing), and the readers refuse a checkpoint built otherwise.  Style mixing, a learned constant input,
+bf16 tensors and modulated convolutions are out of scope.  `adam_lr=L` sets Adam's step size (default None: the reference's 2e-6).  Reference specifics kept: penalty
 coefficient 200, no kt term, G = -D_fake + 5 KL, Adam(2e-6, beta1=0, beta2=0.99) hard-coded (pggan.py:104-110; the
 `learning_rate` placeholder is fed but unused), eps of x_hat drawn in-graph (pggan.py:68 overrides the placeholder),
 `to_rgb` = k2 s1 SAME 9-channel relu conv + 1x1, every kernel He-initialised by utils/ops.py's defaults.
@@ -53,8 +59,11 @@ from ... import optim
 from ... import scope as S
 from ...graphs import DGSchedule, StepGraphs
 from ...utils.ops import (DiffAugmentSampler, concat_tile, conv2d, diff_augment, diff_augment_params, diff_augment_policy, downsample_2d, fc,
-                          layer_norm, lerp, lrelu_act, minibatch_stddev_stat, pixel_norm, pool, relu, upsample_2d, upscale)
+                          layer_norm, lerp, lrelu_act, minibatch_stddev_stat, pixel_norm, pool, relu, style_block, upsample_2d, upscale)
 
+W_AVG = 'g_net/mapping/w_avg'                   # PGGAN(style_dim=D): the running mean of the style vector, [D], not trainable
+W_AVG_DECAY = 0.995
+STYLE_NOISE_CUT = 6.0                           # the style noise is kernels.trunc_normal_'s inverse-CDF draw cut at +-6 sigma: a standard normal to 24 bits
 RESAMPLE_KEY = 'g_net/resample_filter'          # the checkpoint entry of PGGAN(resample_filter=...): the taps divided by their sum, float32
 
 
@@ -93,11 +102,42 @@ def describe_taps(norm):
     return 'the normalised taps (%s)' % ', '.join('%.6g' % float(t) for t in norm)
 
 
+def style_of_names(names):
+    """(style_dim, mapping_layers, style_noise) of the generator whose variables are `names` ({name: shape}); (None, None, None) for the
+    reference's generator."""
+    import re
+    if W_AVG not in names:
+        return (None, None, None)
+    layers = sum(1 for n in names if re.match(r'^g_net/mapping/dense(_\d+)?/kernel$', n))
+    return (int(names[W_AVG][0]), layers, any(n.endswith('/noise_strength') for n in names))
+
+
+def describe_style(sig):
+    """A (style_dim, mapping_layers, style_noise) triple in the flags' words."""
+    if sig[0] is None:
+        return "the reference's generator (no --style-dim)"
+    return 'a style-based generator (--style-dim %d --mapping-layers %d%s)' % (sig[0], sig[1], '' if sig[2] else ' --no-style-noise')
+
+
 class PGGAN(object):
     def __init__(self, batch_size, steps, check_dir_write, check_dir_read, dataset, sample_path, log_dir, stage, trans,
                  build_model=True, device=None, seed=0, store=None, fmap_base=1024, fmap_max=512, z_dim=128, embed_dim=1024,
                  compr_embed_dim=128, dp=None, critic_norm=None, critic_mbstd=None, g_ema=None, equalized_lr=False, adam_lr=None,
-                 diffaug=None, diffaug_p=None, diffaug_adapt=False, diffaug_sampler=None, critic_sn=False, resample_filter=None):
+                 diffaug=None, diffaug_p=None, diffaug_adapt=False, diffaug_sampler=None, critic_sn=False, resample_filter=None,
+                 style_dim=None, mapping_layers=4, style_noise=True, truncation_psi=None):
+        if style_dim is not None and (isinstance(style_dim, bool) or not isinstance(style_dim, int) or style_dim < 1):
+            raise ValueError('style_dim must be None (the reference\'s generator) or an integer >= 1 (the width of the style vector w), got %r' % (style_dim,))
+        if isinstance(mapping_layers, bool) or not isinstance(mapping_layers, int) or mapping_layers < 1:
+            raise ValueError('mapping_layers must be an integer >= 1 (the dense layers of the mapping network), got %r' % (mapping_layers,))
+        if not isinstance(style_noise, bool):
+            raise ValueError('style_noise must be True or False, got %r' % (style_noise,))
+        if truncation_psi is not None and (isinstance(truncation_psi, bool) or not isinstance(truncation_psi, (int, float)) or not math.isfinite(truncation_psi)):
+            raise ValueError('truncation_psi must be None or a finite number (the sampler uses w_avg + psi (w - w_avg)), got %r' % (truncation_psi,))
+        if style_dim is None and truncation_psi is not None:
+            raise ValueError('truncation_psi needs style_dim (the style-based generator whose w it truncates), which is None')
+        self.style_dim, self.mapping_layers, self.style_noise = style_dim, mapping_layers, style_noise
+        self.truncation_psi = None if truncation_psi is None else float(truncation_psi)
+        self._sn = None                           # where the style blocks take their noise from: (feed, 'd' | 'g'), a list of images, or None (drawn)
         taps = normalised_taps(resample_filter)
         self.resample_filter = None if taps is None else taps[0]          # the taps as given; None: nearest x2 and the 2x2 mean
         self.resample_taps = None if taps is None else taps[1]            # ... divided by their sum, float32: what checkpoints carry
@@ -235,6 +275,8 @@ class PGGAN(object):
                 scales[n] = math.sqrt(2.0 / (v.shape[0] * v.shape[1] * v.shape[2]))
             elif n.endswith('/kernel') and v.dim() == 2:
                 scales[n] = math.sqrt(2.0 / v.shape[0])
+                if n.startswith('g_net/mapping/'):          # the mapping network's learning-rate multiplier (Karras et al. 2019)
+                    scales[n] = (scales[n], 0.01)
         return scales
 
     def _init(self, fan_in):
@@ -273,6 +315,7 @@ class PGGAN(object):
             eps = torch.rand(B, device=x.device)
         with torch.no_grad():
             self._ca = self._noise(feed, 'ca_noise_d', cond[:, :self.compr_embed_dim])
+            self._sn = (feed, 'd')
             G, _, _ = self.generator(z, cond, stages=st, t=t, reuse=True)
             x_hat = K.interp(eps.reshape(B, 1, 1, 1).contiguous(), G, x)
         # D(G), D(x), D(x_mismatch) as one pass over 3B samples: without critic_mbstd the critic has no batch coupling; with it the
@@ -315,7 +358,11 @@ class PGGAN(object):
         if self.aug_sampler is not None:          # the first launch, as in d_losses: call k + 1
             aug = self._aug_table(feed, 'aug_g', z.shape[0], (self.out_size, self.out_size))
         self._ca = self._noise(feed, 'ca_noise_g', cond[:, :self.compr_embed_dim])
+        self._sn = (feed, 'g')
         G, mean, log_sigma = self.generator(z, cond, stages=self.stage, t=self.trans, reuse=True)
+        if self.style_dim is not None:            # the truncation's centre follows the batch mean of w: in place, no host value, capturable
+            with torch.no_grad():
+                self.store.vars[W_AVG].lerp_(self._w.detach().mean(0), 1.0 - W_AVG_DECAY)
         if self.diffaug is not None and aug is None:
             aug = self._aug_table(feed, 'aug_g', G.shape[0], G.shape[1:3])
         G_seen = G if self.diffaug is None else diff_augment(G, aug, self.diffaug)
@@ -345,6 +392,7 @@ class PGGAN(object):
         drawn = (('eps_graph', (B,)), ('ca_noise_d', (B, self.compr_embed_dim)), ('ca_noise_g', (B, self.compr_embed_dim)))
         if self.diffaug is not None and self.aug_sampler is None:      # the two parameter tables of the augmentation: static buffers, re-drawn like eps_graph
             drawn += (('aug_d', (4 * B, 9)), ('aug_g', (B, 9)))
+        drawn += tuple((k, (B, size, size)) for k, size in self.style_noise_keys())      # one image per style block and step, re-drawn like ca_noise_*
         for k, shape in drawn:
             if feed.get(k) is None:
                 feed[k] = torch.empty(shape, device=dev)
@@ -363,6 +411,9 @@ class PGGAN(object):
         for k in ('ca_noise_d', 'ca_noise_g'):
             if feed.get(k) is None or feed[k] is st[k]:
                 K.trunc_normal_(st[k])
+        for k, _ in self.style_noise_keys():
+            if feed.get(k) is None or feed[k] is st[k]:
+                K.trunc_normal_(st[k], a=-STYLE_NOISE_CUT, b=STYLE_NOISE_CUT)
         if self.diffaug is not None and self.aug_sampler is None:
             size = st['x'].shape[1:3]
             for k in ('aug_d', 'aug_g'):
@@ -402,10 +453,26 @@ class PGGAN(object):
         finally:
             exchange()
 
-    def sampler(self, z_sample, cond_sample):
+    def sampler(self, z_sample, cond_sample, noise=None, truncation_psi=None):
+        """noise (style_dim only): one [B,S,S] image per style block, in order (style_noise_keys gives the sizes); None draws fresh
+        ones.  truncation_psi (style_dim only; default: the constructor's): w_avg + psi (w - w_avg) in place of w."""
+        if self.style_dim is None and (noise is not None or truncation_psi is not None):
+            raise ValueError('noise and truncation_psi belong to the style-based generator (style_dim), which this model does not have')
         with torch.no_grad():
             self._ca = None
-            return self.generator(z_sample, cond_sample, reuse=True, stages=self.stage, t=self.trans)[0]
+            self._sn = None if noise is None else list(noise)
+            try:
+                return self.generator(z_sample, cond_sample, reuse=True, stages=self.stage, t=self.trans, truncation_psi=truncation_psi)[0]
+            finally:
+                self._sn = None
+
+    def style_noise_keys(self):
+        """[(feed key, map extent)] of the style-noise images of one iteration: `style_noise_d_<k>` and `style_noise_g_<k>` for block k
+        (two per conv stage, 4 x 4 upwards); empty without style_dim or with style_noise=False."""
+        if self.style_dim is None or not self.style_noise:
+            return []
+        sizes = [4 * 2 ** i for i in range(self.stage) for _ in range(2)]
+        return [('style_noise_%s_%d' % (tag, k), size) for tag in ('d', 'g') for k, size in enumerate(sizes)]
 
     # ---- networks ------------------------------------------------------------------------------------------------------
     def discriminator(self, inp, cond, stages, t, reuse=False):
@@ -451,8 +518,10 @@ class PGGAN(object):
         x = self._conv2d(x, f=f, ks=ks, s=(1, 1), padding=padding, act=None)
         return layer_norm(x, act=act) if self.critic_norm == 'layer' else pixel_norm(x, act=act)
 
-    def generator(self, z_var, cond_inp, stages, t, reuse=False, cond_noise=True):
+    def generator(self, z_var, cond_inp, stages, t, reuse=False, cond_noise=True, truncation_psi=None):
         """-> (image NHWC, mean, log_sigma)  (pggan.py:283-316)"""
+        if self.style_dim is not None:
+            return self._style_generator(z_var, cond_inp, stages, t, reuse, cond_noise, truncation_psi)
         alpha_trans = self._alpha_dev
         with S.variable_scope('g_net', reuse=reuse):
             with S.variable_scope(self.get_conv_scope_name(0), reuse=reuse):
@@ -481,6 +550,77 @@ class PGGAN(object):
             if t:
                 x = lerp(x_iden, x, alpha_trans)                  # (1 - alpha) * x_iden + alpha * x
             return x, mean_lr, log_sigma_lr
+
+    def _style_generator(self, z_var, cond_inp, stages, t, reuse, cond_noise, truncation_psi):
+        """The style-based generator (style_dim=D; Karras et al. 2019).  The dense 4x4 trunk from [z, c] stays
+        (no learned constant); a mapping network (scope g_net/mapping: pixel norm of [z, c], then mapping_layers dense + lrelu layers)
+        gives w [B,D]; every conv -> layer_norm(relu) pair becomes conv -> style_block(x, w, noise, relu): per-pixel noise scaled per
+        channel, relu, instance norm, the style's affine map.  to_rgb, the fade-in and _up are the reference's.  g_net/mapping/w_avg [D]
+        (not trainable) follows the batch mean of w with decay 0.995 in g_losses; under data parallelism it is rank-local — every rank
+        averages its own batches — and rank 0's is the one a checkpoint holds.  truncation_psi (None: the constructor's) replaces w by
+        w_avg + psi (w - w_avg); training never truncates (g_losses and d_losses pass None with the constructor's None)."""
+        alpha_trans = self._alpha_dev
+        psi = self.truncation_psi if truncation_psi is None else float(truncation_psi)
+        B = z_var.shape[0]
+        block = [0]
+
+        def styled(x, f):
+            x = self._conv2d(x, f=f, ks=(3, 3), s=(1, 1))
+            k = block[0]
+            block[0] += 1
+            return style_block(x, w, noise=self._style_noise_image(k, x), act=relu, init=self._init(self.style_dim))
+
+        with S.variable_scope('g_net', reuse=reuse):
+            with S.variable_scope(self.get_conv_scope_name(0), reuse=reuse):
+                mean_lr, log_sigma_lr = self.generate_conditionals(cond_inp)
+                cond = self.sample_normal_conditional(mean_lr, log_sigma_lr, cond_noise)
+                zc = torch.cat([z_var, cond], 1)
+                x = self._fc(zc, units=4 * 4 * self.get_nf(0))
+                x = layer_norm(x)
+                x = x.reshape(-1, 4, 4, self.get_nf(0))
+            with S.variable_scope('mapping', reuse=reuse):
+                w = pixel_norm(zc.reshape(B, 1, 1, zc.shape[1])).reshape(B, zc.shape[1])
+                for _ in range(self.mapping_layers):
+                    w = self._fc(w, units=self.style_dim, act=lrelu_act())
+                w_avg = self.store.get_variable('w_avg', (self.style_dim,), S.constant_init(0.0), trainable=False)
+            self._w = w
+            if psi is not None:
+                w = torch.lerp(w_avg.expand_as(w), w, psi)                # psi = 1: w, psi = 0: w_avg, both exactly
+            self._w_used = w                                              # (what the style blocks see: w, or its truncation)
+            with S.variable_scope(self.get_conv_scope_name(0), reuse=reuse):      # (re-entered: only Conv and StyleMod layers follow)
+                x = styled(x, self.get_nf(0))
+                x = styled(x, self.get_nf(0))
+            x_iden = None
+            for i in range(1, stages):
+                if (i == stages - 1) and t:
+                    x_iden = self.to_rgb(x, stages - 2)
+                    x_iden = self._up(x_iden)
+                with S.variable_scope(self.get_conv_scope_name(i), reuse=reuse):
+                    x = self._up(x)
+                    x = styled(x, self.get_nf(i))
+                    x = styled(x, self.get_nf(i))
+            x = self.to_rgb(x, stages - 1)
+            if t:
+                x = lerp(x_iden, x, alpha_trans)                  # (1 - alpha) * x_iden + alpha * x
+            return x, mean_lr, log_sigma_lr
+
+    def _style_noise_image(self, k, x):
+        """The noise image [B,H,W] of style block k: the feed's `style_noise_{d,g}_<k>`, the k-th of the sampler's list, or a fresh draw."""
+        if not self.style_noise:
+            return None
+        src = self._sn
+        n = None
+        if isinstance(src, tuple):
+            n = src[0].get('style_noise_%s_%d' % (src[1], k))
+        elif src is not None:
+            if k >= len(src):
+                raise ValueError('the sampler was given %d noise images, style block %d needs one more' % (len(src), k))
+            n = src[k]
+        if n is None:
+            n = K.trunc_normal_(torch.empty(x.shape[:3], device=x.device), a=-STYLE_NOISE_CUT, b=STYLE_NOISE_CUT)
+        if tuple(n.shape) != tuple(x.shape[:3]):
+            raise ValueError('the noise image of style block %d must be %s, got %s' % (k, tuple(x.shape[:3]), tuple(n.shape)))
+        return n
 
     @staticmethod
     def mbstd_features(channels):
@@ -536,6 +676,7 @@ class PGGAN(object):
         for stage in range(stages):
             d += list(self.store.global_variables('d_net/%s/' % self.get_conv_scope_name(stage)))
             g += list(self.store.global_variables('g_net/%s/' % self.get_conv_scope_name(stage)))
+        g += list(self.store.global_variables('g_net/mapping/'))       # (style_dim: the mapping network and w_avg, at every stage; else none)
         return d + g
 
     # ---- training loop (pggan.py:147-247) ---------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 """Stage driver of the progressive-growing schedule — reference models/pggan/train_pggan.py:17-69: stages
 1, 2t, 2, 3t, 3, ... (t = fade-in transition), batch 16 (8 from stage 6 on), 600000 images per stage, checkpoints
 written under `<CHECKPOINT_DIR>/stage<k>/` and read from the previous stage's directory.  `--iters` bounds the iterations
-per stage (the full 600000 // batch when omitted).
+per stage (the full 600000 // batch when omitted).  `--style-dim D [--mapping-layers N] [--no-style-noise]` trains the style-based
+generator (PGGAN(style_dim=D)).
 
 Without `--cfg`, synthetic data stands in for the pickled datasets and everything goes under `--out`.  With `--cfg <yml>`
 (models/pggan/cfg/flowers.yml, birds.yml) the entry runs on the real dataset as the reference does: `TextDataset(DATASET_DIR,
@@ -109,6 +110,7 @@ def main(argv=None):
                     help="spectral normalisation of the critic's conv and dense kernels (Miyato et al. 2018): one power iteration per "
                          "critic step next to the Adam launch; checkpoints carry the raw weights, u, v and sigma (default: none)")
     cli.add_resample_filter_argument(ap, reader=False)
+    cli.add_style_arguments(ap, reader=False)
     ap.add_argument('--diffaug', default=None, metavar='POLICY',
                     help="differentiable augmentation of every image the critic sees (Zhao et al. 2020): a comma-separated subset of "
                          "color,translation,cutout (default: none)")
@@ -127,6 +129,7 @@ def main(argv=None):
     ap.add_argument('--bench', action='store_true', help='time `--iters` iterations of each entry instead of training with side effects')
     args = ap.parse_args(argv)
     taps = cli.resample_filter_of(ap, args)
+    style = cli.style_kwargs_of(ap, args)
     if not 0 <= args.first <= args.last < len(STAGE):
         ap.error('--first %d / --last %d: need 0 <= first <= last <= %d' % (args.first, args.last, len(STAGE) - 1))
     if args.iters is not None and args.iters < 1:
@@ -193,7 +196,7 @@ def main(argv=None):
                       critic_mbstd=args.critic_mbstd, **({} if args.g_ema is None else {'g_ema': args.g_ema}),
                       **({'equalized_lr': True} if args.equalized_lr else {}), **({} if args.lr is None else {'adam_lr': args.lr}),
                       **({'critic_sn': True} if args.critic_sn else {}), **({} if taps is None else {'resample_filter': taps}),
-                      **({} if args.diffaug is None else {'diffaug': args.diffaug}),
+                      **({} if args.diffaug is None else {'diffaug': args.diffaug}), **style,
                       **({} if aug_sampler is None else {'diffaug_sampler': aug_sampler, 'diffaug_adapt': args.diffaug_adapt}))
         if args.bench:
             gen = torch.Generator(device=dev).manual_seed(0)

@@ -79,8 +79,10 @@ def main(argv=None, **widths):
     ap.add_argument('--cfg', required=True, help='models/pggan/cfg/flowers.yml or birds.yml')
     ap.add_argument('--ema', action='store_true', help="every stage from the moving average of its generator's weights (checkpoints of train_pggan.py --g-ema)")
     cli.add_resample_filter_argument(ap)
+    cli.add_style_arguments(ap)
     args = ap.parse_args(argv)
     taps = cli.resample_filter_of(ap, args)
+    widths = dict(widths, **cli.style_kwargs_of(ap, args))
     cfg = config_from_yaml(args.cfg)
     for stage in STAGES:
         d = os.path.join(cfg.CHECKPOINT_DIR, 'stage%d' % stage)

@@ -125,8 +125,10 @@ def main(argv=None, **widths):
     ap.add_argument('--stage', type=int, default=7, help='the stage whose generator draws the sheets [7]')
     ap.add_argument('--ema', action='store_true', help="draw from the moving average of the generator's weights (a checkpoint of train_pggan.py --g-ema)")
     cli.add_resample_filter_argument(ap)
+    cli.add_style_arguments(ap)
     args = ap.parse_args(argv)
     taps = cli.resample_filter_of(ap, args)
+    widths = dict(widths, **cli.style_kwargs_of(ap, args))
     if args.interp < 0 or not 1 <= args.stage <= 8:
         ap.error('--interp must be >= 0 and --stage in 1..8')
     cfg = config_from_yaml(args.cfg)

@@ -21,6 +21,8 @@ like ``pool``, ``resize_nearest_neighbor``, ``gn``, ``lerp``, ``add`` and the co
 ``diff_augment`` / ``diff_augment_params`` (not in the reference either: the differentiable augmentation of Zhao et al. 2020, DESIGN.md
 section 4.35) take fp32 tensors only, with the same refusals, and are differentiable to any order.  ``DiffAugmentSampler`` (DESIGN.md section
 4.39) draws those tables on the device with a probability ``p`` per transform and can steer ``p`` from a critic's outputs.
+``adain`` / ``style_block`` (not in the reference: the layer of a style-based generator) take fp32 tensors only,
+with the same refusals, and are first order: the generator is never under the gradient penalty.
 """
 import math
 import struct
@@ -359,6 +361,70 @@ def pixel_norm(x, eps=1e-8, act=None):
         raise ValueError('pixel_norm normalises over the last axis of physically NHWC data; got a non-contiguous tensor (shape %s, strides %s) '
                          '- convert a logical NCHW view with to_nhwc first' % (tuple(x.shape), x.stride()))
     return A.PixelNormFn.apply(x, float(eps), kind, alpha)
+
+
+def adain(x, ys, yb, noise=None, strength=None, act=None, eps=1e-8):
+    """The layer epilogue of a style-based generator (Karras et al. 2019; not in the reference).  x [B,H,W,C]
+    (contiguous NHWC, fp32), ys and yb [B,C], optionally noise [B,H,W] with strength [C] (both or neither):
+      u = act(x + strength[c] * noise[b,h,w])         act: None, relu or lrelu_act(slope >= 0), fused
+      mu, var = the biased moments of u over (h, w), per sample and channel (never E[u^2] - mu^2)
+      y = (u - mu) / sqrt(var + eps) * (1 + ys[b,c]) + yb[b,c]
+    Three launches forward; three backward, four with strength.  Gradients reach x, ys, yb and strength (not under
+    autograd.input_grads_only()); noise gets none and must not require one.  First order only: a second differentiation raises
+    NotImplementedError.  ys and yb may be the two halves of one [B,2C] tensor (no copy).  bf16 tensors, a stacked pass, another rank, a
+    non-contiguous x or noise, wrong shapes, noise without strength or the reverse and a negative lrelu slope are refused before any
+    launch.  A sample's result does not depend on its batch, bit for bit."""
+    op = 'adain'
+    _fp32_plain(x, op)
+    kind, alpha, post = _split_act(act)
+    if post is not None or kind == K.ACT_TANH:
+        raise ValueError('%s: act must be None, relu or an lrelu_act (it is fused between the noise and the normalisation), got %r' % (op, act))
+    if kind == K.ACT_LRELU and alpha < 0.0:
+        raise ValueError('%s: lrelu_act(%g) has a negative slope; the backward takes the derivative from the sign, which needs a slope >= 0' % (op, alpha))
+    if not x.is_contiguous():
+        raise ValueError('%s works on physically NHWC data; got a non-contiguous tensor (shape %s, strides %s) - convert a logical NCHW '
+                         'view with to_nhwc first' % (op, tuple(x.shape), x.stride()))
+    B, H, W, C = (int(s) for s in x.shape)
+    if min(B, H, W, C) < 1 or x.numel() >= 1 << 31:
+        raise ValueError('%s: every size of x must be at least 1 and x must have fewer than 2^31 elements, got %s' % (op, tuple(x.shape)))
+    for name, t in (('ys', ys), ('yb', yb)):
+        if not isinstance(t, torch.Tensor) or isinstance(t, ST.Stacked) or t.dtype != torch.float32 or tuple(t.shape) != (B, C) or t.device != x.device:
+            raise ValueError('%s: %s must be a float32 tensor of shape [%d, %d] on %s, got %s' % (
+                op, name, B, C, x.device, '%s %s on %s' % (t.dtype, tuple(t.shape), t.device) if isinstance(t, torch.Tensor) else type(t).__name__))
+    if ys.stride(1) != 1 or yb.stride(1) != 1 or (B > 1 and (ys.stride(0) != yb.stride(0) or ys.stride(0) < C)):
+        ys, yb = ys.contiguous(), yb.contiguous()
+    if (noise is None) != (strength is None):
+        raise ValueError('%s: noise and strength come together or not at all (got %s without %s)' % (
+            (op, 'noise', 'strength') if strength is None else (op, 'strength', 'noise')))
+    if noise is not None:
+        for name, t, shape in (('noise', noise, (B, H, W)), ('strength', strength, (C,))):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape or t.device != x.device:
+                raise ValueError('%s: %s must be a float32 tensor of shape %s on %s, got %s' % (
+                    op, name, list(shape), x.device, '%s %s on %s' % (t.dtype, tuple(t.shape), t.device) if isinstance(t, torch.Tensor) else type(t).__name__))
+            if not t.is_contiguous():
+                raise ValueError('%s: %s must be contiguous (strides %s)' % (op, name, t.stride()))
+        if noise.requires_grad:
+            raise ValueError('%s: noise requires a gradient, and the operator gives it none (detach it)' % op)
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not (math.isfinite(eps) and eps >= 0.0):
+        raise ValueError('%s: eps must be a finite number >= 0, got %r' % (op, eps))
+    return A.AdaINFn.apply(x, ys, yb, noise, strength, kind, alpha, float(eps))
+
+
+def style_block(x, w, noise=None, act=None, name=None, init=None):
+    """The layer a style-based generator puts behind every convolution: x [B,H,W,C] is the convolution's output
+    (bias included, no activation), w [B, w_dim] the style vector, noise [B,H,W] a standard-normal image or None.
+    Variables: <scope>/StyleMod[_k]/{noise_strength [C] zeros (only with noise), style/kernel [w_dim, 2C], style/bias [2C] zeros}: the
+    dense layer is `fc` with the caller's `init` (None: fc's He default), and its rank-2 `kernel` is what an equalized-learning-rate table
+    selects.  Its output is split into ys | yb and handed to `adain` without a copy."""
+    st = S.default_store()
+    _fp32_plain(x, 'style_block')
+    if w.dim() != 2 or w.shape[0] != x.shape[0]:
+        raise ValueError('style_block: w must be [%d, w_dim], got shape %s' % (x.shape[0], tuple(w.shape)))
+    C = int(x.shape[3])
+    with st.variable_scope(name or st.unique_op_name('StyleMod'), reuse=st.reuse()):
+        strength = st.get_variable('noise_strength', (C,), S.constant_init(0.0)) if noise is not None else None
+        s = fc(w, 2 * C, init=init, name='style')
+    return adain(x, s[:, :C], s[:, C:], noise=noise, strength=strength, act=act)
 
 
 def minibatch_stddev_stat(x, group_size=4, num_features=1, eps=1e-8):

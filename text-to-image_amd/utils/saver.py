@@ -75,7 +75,7 @@ class Saver(object):
         z = np.load(path)
         with torch.no_grad():
             for n, v in self._selected():
-                key = shadow_key(n) if ema else n
+                key = shadow_key(n) if ema and getattr(self.store, 'trainable', {}).get(n, True) else n      # (a variable no optimizer steps has no shadow: PGGAN's w_avg)
                 if key not in z.files:
                     if ema:
                         raise KeyError('checkpoint %s has no %s: it was trained without EMA (no moving average of the weights was kept)'

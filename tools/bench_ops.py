@@ -4,7 +4,8 @@ gn, the double backward of pixel_norm and layer_norm, the minibatch standard dev
 without the weight EMA (`--only adam_ema`) and with per-slot multipliers (`--only adam_slots`) at the sizes of two generator arenas, and the
 differentiable augmentation of csrc/t2i_augment.hip at the PGGAN trainer's shapes next to the same policy from tensor-library calls
 (`--only diff_augment`), and the critic's optimizer step with and without spectral normalisation (`--only spectral_norm`), and the
-anti-aliased resampling of csrc/t2i_resample.hip at the PGGAN trainer's full widths (`--only upfirdn`): one JSON line per kernel with the time per call, the bytes the algorithm moves (reads + writes, from the
+anti-aliased resampling of csrc/t2i_resample.hip at the PGGAN trainer's full widths (`--only upfirdn`), and the style layer of
+csrc/t2i_style.hip at the generator's B = 8 shapes next to layer_norm on the same tensors (`--only adain`): one JSON line per kernel with the time per call, the bytes the algorithm moves (reads + writes, from the
 shapes), bytes per second, and the ratio of that rate to a device-to-device copy that moves the SAME number of bytes (half read, half
 written), timed in the same process.  Per measurement: 10 warm-up launches, then REPS rounds of 100 back-to-back launches between
 device events, kernel and copy rounds alternating; the median round is reported.  Read the ratio, not the absolute rate, as the share
@@ -41,8 +42,8 @@ def _round(fn, iters):
     return s.elapsed_time(e) / iters * 1e-3
 
 
-def measure(name, shape, nbytes, fn, reps, iters, composed=None, others=None):
-    """composed: the same operation as tensor-library calls, timed in the same alternating rounds ('composed_us', 'ratio_to_composed');
+def measure(name, shape, nbytes, fn, reps, iters, composed=None, others=None, extra=None):
+    """extra: further fields of the line (a launch count); composed: the same operation as tensor-library calls, timed in the same alternating rounds ('composed_us', 'ratio_to_composed');
     others: {label: fn} of further launches on the same tensors, timed in the same rounds ('<label>_us')"""
     src = torch.empty(nbytes // 8, dtype=torch.float32, device='cuda').normal_()
     dst = torch.empty_like(src)
@@ -71,6 +72,7 @@ def measure(name, shape, nbytes, fn, reps, iters, composed=None, others=None):
         line.update(composed_us=round(statistics.median(tl) * 1e6, 2), ratio_to_composed=round(statistics.median(tl) / t, 2))
     for k, ts in to.items():
         line['%s_us' % k] = round(statistics.median(ts) * 1e6, 2)
+    line.update(extra or {})
     print(json.dumps(line), flush=True)
 
 
@@ -304,6 +306,49 @@ def main():
                 assert err <= 1e-4 and torch.equal(fn(), getattr(ops, kind)(x, k)), (kind, shape, err)      # the helper's launch, called as upscale2 / pool2_sum are
                 measure('upfirdn: %s (1,3,3,1), %s (r + w)' % (kind, where), shape, 4 * (x.numel() + out), fn, a.reps, a.iters, comp, {label: base})
                 del x, xc
+
+    # the style layer at the generator's B = 8 shapes, relu and noise as the model runs it: each entry alone, the
+    # forward (3 launches) and the backward (4 launches) as the autograd Function issues them, and layer_norm(act=relu) forward and
+    # backward on the same tensors (what the layer replaces) with one r + w pass standing in for a separate noise add.  Bytes: the passes
+    # over the [B,H,W,C] tensors each line makes (stats r, apply r + w, bwd_sums 2r, bwd_apply 2r + w); layer_norm's lines are charged the
+    # same bytes as the adain line they stand next to, so the two ratios compare directly.
+    if a.only and a.only in 'adain':
+        from t2i_amd import autograd as A
+        from t2i_amd._lib import check, lib
+        with torch.no_grad():
+            for shape in ((8, 4, 4, 512), (8, 16, 16, 512), (8, 64, 64, 128), (8, 256, 256, 64)):
+                B, H, W, C = shape
+                R, n = H * W, B * H * W * C
+                x, g = torch.randn(shape, device='cuda'), torch.randn(shape, device='cuda')
+                nz, st = torch.randn((B, H, W), device='cuda'), torch.rand(C, device='cuda') - 0.5
+                sty = torch.randn((B, 2 * C), device='cuda') * 0.3
+                ys, yb = sty[:, :C], sty[:, C:]
+                y, mean, rstd = K.adain_fwd(x, ys, yb, nz, st, K.ACT_RELU, 0.0)
+                dx, ds, dys, dyb = K.adain_bwd(g, x, ys, mean, rstd, nz, st, K.ACT_RELU, 0.0)
+                wsp, wsn = K._ws_args(x, int(lib.t2i_adain_workspace_bytes(B, R, C)))
+                p, sm = K._ptr, K._stream
+                one = lambda name, nbytes, fn, launches: measure('adain: ' + name, shape, nbytes, fn, a.reps, a.iters, extra={'launches': launches})
+                one('t2i_adain_stats relu + noise (r)', 4 * n, lambda: check(lib.t2i_adain_stats(p(x), p(nz), p(st), B, R, C, K.ACT_RELU, 0.0, 1e-8,
+                    p(mean), p(rstd), wsp, wsn, sm())), 2)
+                one('t2i_adain_apply relu + noise (r + w)', 8 * n, lambda: check(lib.t2i_adain_apply(p(x), p(nz), p(st), p(mean), p(rstd), p(ys), p(yb),
+                    2 * C, B, R, C, K.ACT_RELU, 0.0, p(y), sm())), 1)
+                one('forward = stats + apply (2r + w)', 12 * n, lambda: K.adain_fwd(x, ys, yb, nz, st, K.ACT_RELU, 0.0), 3)
+                one('t2i_adain_bwd_sums relu + noise (2r)', 8 * n, lambda: check(lib.t2i_adain_bwd_sums(p(g), p(x), p(nz), p(st), p(mean), p(rstd),
+                    B, R, C, K.ACT_RELU, 0.0, p(dys), p(dyb), wsp, wsn, sm())), 2)
+                one('t2i_adain_bwd_apply relu + noise + dstrength (2r + w)', 12 * n, lambda: check(lib.t2i_adain_bwd_apply(p(g), p(x), p(nz), p(st),
+                    p(mean), p(rstd), p(ys), 2 * C, p(dys), p(dyb), B, R, C, K.ACT_RELU, 0.0, p(dx), p(ds), wsp, wsn, sm())), 2)
+                one('backward = bwd_sums + bwd_apply (4r + w)', 20 * n, lambda: K.adain_bwd(g, x, ys, mean, rstd, nz, st, K.ACT_RELU, 0.0), 4)
+                gamma, beta = torch.rand(C, device='cuda') + 0.5, torch.randn(C, device='cuda') * 0.1
+                one('layer_norm relu forward, same tensors (charged 2r + w)', 12 * n, lambda: A.LayerNormFn.apply(x, gamma, beta, 1e-12, K.ACT_RELU, 0.0), 3)
+                s1, s2 = K.row_moments(x)
+                lmean = s1 / (R * C)
+                lrstd = torch.rsqrt(torch.clamp(s2 / (R * C) - lmean * lmean, min=0.0) + 1e-12)
+                xhat = K.row_fma2(x, lrstd, delta=-lmean * lrstd)
+                yl = K.bn_apply(xhat, gamma, beta, K.ACT_RELU, 0.0)
+                one('layer_norm relu backward, same tensors (charged 4r + w)', 20 * n,
+                    lambda: A.LayerNormBwdFn.apply(g, x, gamma, xhat, lrstd, yl, K.ACT_RELU, 0.0, R * C, True), 5)
+                one('a separate noise add stood in for by bn_apply (r + w)', 8 * n, lambda: K.bn_apply(x, gamma, beta, K.ACT_NONE, 0.0), 1)
+                del x, g, y, dx, xhat, yl
 
 
 if __name__ == '__main__':
