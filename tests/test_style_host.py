@@ -208,7 +208,7 @@ def test_the_style_model_and_its_restatement_name_the_same_variables(t2i):
 
 
 def test_flags_and_the_refusal_message(t2i, tmp_path):
-    from t2i_amd.models import cli
+    from t2i_amd.models.pggan import options as cli
     from t2i_amd.models.pggan import eval_pggan as E
     from t2i_amd.utils.saver import Saver, save
 

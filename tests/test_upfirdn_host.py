@@ -224,7 +224,7 @@ def _parse_error(main, argv):
 
 def test_the_scripts_parse_the_flag(capsys):
     import argparse
-    from t2i_amd.models import cli
+    from t2i_amd.models.pggan import options as cli
     from t2i_amd.models.pggan import eval_pggan, train_pggan, visualize_last_stage, visualize_pggan
     for reader in (True, False):
         ap = argparse.ArgumentParser()

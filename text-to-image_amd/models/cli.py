@@ -96,66 +96,6 @@ def subsets_of(args):
     return (args.mmd_subsets, args.mmd_subset_size)
 
 
-def add_resample_filter_argument(ap, reader=True):
-    ap.add_argument('--resample-filter', default=None, metavar='TAPS',
-                    help="low-pass filtered resampling in both networks (Karras et al. 2019, Zhang 2019): comma-separated taps, 2..8 of "
-                         "them, finite, with a positive sum, e.g. 1,3,3,1; they replace the generator's nearest x2 upscale and the critic's "
-                         "2x2 average pool%s (default: the reference's resampling)"
-                         % (' - give the taps the checkpoint was trained with: a mismatch is refused' if reader else
-                            '; checkpoints carry the taps and the evaluators and visualisers must be given the same'))
-
-
-def resample_filter_of(ap, args):
-    """--resample-filter as a tuple of floats (None when absent); anything but 2..8 finite taps with a positive sum is an argument error."""
-    if args.resample_filter is None:
-        return None
-    try:
-        taps = tuple(float(t) for t in args.resample_filter.split(','))
-    except ValueError:
-        taps = ()
-    if not 2 <= len(taps) <= 8 or any(t != t or t in (float('inf'), float('-inf')) for t in taps) or not sum(taps) > 0.0:
-        ap.error('--resample-filter takes 2..8 comma-separated finite taps with a positive sum, e.g. 1,3,3,1 (got %r)' % args.resample_filter)
-    return taps
-
-
-def add_style_arguments(ap, reader=True):
-    """PGGAN's style-based generator: --style-dim, --mapping-layers, --no-style-noise, and for the readers --truncation-psi."""
-    ap.add_argument('--style-dim', type=int, default=None, metavar='D',
-                    help="the style-based generator (Karras et al. 2019): a mapping network turns [z, c] into a style vector w of D units, and "
-                         "every generator convolution is followed by per-pixel noise, instance norm and an affine map of w%s (default: the "
-                         "reference's generator)" % (' - give what the checkpoint was trained with: a mismatch is refused' if reader else
-                                                     '; the evaluators and visualisers must be given the same'))
-    ap.add_argument('--mapping-layers', type=int, default=None, metavar='N', help='--style-dim: dense layers of the mapping network (default 4)')
-    ap.add_argument('--no-style-noise', action='store_true', help='--style-dim: build the style blocks without the per-pixel noise and its strengths')
-    if reader:
-        ap.add_argument('--truncation-psi', type=float, default=None, metavar='PSI',
-                        help='--style-dim: sample from w_avg + PSI (w - w_avg), w_avg the running mean of w the checkpoint carries (default: w itself)')
-
-
-def style_kwargs_of(ap, args):
-    """The PGGAN constructor arguments of add_style_arguments' flags ({} without --style-dim); a flag that needs --style-dim without it,
-    or a value out of range, is an argument error."""
-    psi = getattr(args, 'truncation_psi', None)
-    if args.style_dim is None:
-        if args.mapping_layers is not None or args.no_style_noise or psi is not None:
-            ap.error('--mapping-layers / --no-style-noise / --truncation-psi need --style-dim (the generator they configure)')
-        return {}
-    if args.style_dim < 1:
-        ap.error('--style-dim %r: the style vector needs at least one unit' % args.style_dim)
-    if args.mapping_layers is not None and args.mapping_layers < 1:
-        ap.error('--mapping-layers %r: the mapping network needs at least one layer' % args.mapping_layers)
-    if psi is not None and not (psi == psi and abs(psi) != float('inf')):
-        ap.error('--truncation-psi %r: a finite number' % psi)
-    kw = {'style_dim': args.style_dim}
-    if args.mapping_layers is not None:
-        kw['mapping_layers'] = args.mapping_layers
-    if args.no_style_noise:
-        kw['style_noise'] = False
-    if psi is not None:
-        kw['truncation_psi'] = psi
-    return kw
-
-
 def check_mode(args, cfg, visualiser):
     """The mode errors, raised before any device work and before a directory is created."""
     if args.incep_batch is not None and (not args.eval or args.incep_batch <= 0):

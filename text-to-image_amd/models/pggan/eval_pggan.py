@@ -48,18 +48,18 @@ import t2i_amd  # noqa: E402,F401
 from t2i_amd import kernels as K  # noqa: E402
 from t2i_amd.evaluation.evaluator import GeneratorEval  # noqa: E402
 from t2i_amd.models import cli  # noqa: E402
+from t2i_amd.models.pggan import options  # noqa: E402
+from t2i_amd.models.pggan.pggan import PGGAN  # noqa: E402
 from t2i_amd.utils.saver import restore_scopes  # noqa: E402
 
 
-def stage_model(cfg, stage, batch_size, dataset, device, resample_filter=None, **widths):
-    """The stage's PGGAN without its training graph (build_model=False), g_net created by a launch-free pass.  `widths`
-    (fmap_base, fmap_max, z_dim, embed_dim, compr_embed_dim) default to the reference's.  resample_filter: PGGAN's, the taps the
-    checkpoint was trained with (`train_pggan.py --resample-filter`); restore_generator refuses a checkpoint whose taps differ."""
-    from t2i_amd.models.pggan.pggan import PGGAN
+def stage_model(cfg, stage, batch_size, dataset, device, **kw):
+    """The stage's PGGAN without its training graph (build_model=False), g_net created by a launch-free pass.  kw: the widths (fmap_base,
+    fmap_max, z_dim, embed_dim, compr_embed_dim; default: the reference's) and the architecture the checkpoint was trained with
+    (resample_filter, style_dim, ...: options.kwargs_of); restore_generator refuses a checkpoint built otherwise."""
     from t2i_amd.scope import trainable_variables
     m = PGGAN(batch_size=batch_size, steps=None, check_dir_write='', check_dir_read=os.path.join(cfg.CHECKPOINT_DIR, 'stage%d/' % stage),
-              dataset=dataset, sample_path=None, log_dir=None, stage=stage, trans=False, build_model=False, device=device,
-              **dict(widths, **({} if resample_filter is None else {'resample_filter': resample_filter})))
+              dataset=dataset, sample_path=None, log_dir=None, stage=stage, trans=False, build_model=False, device=device, **kw)
     if not trainable_variables('g_net'):
         with K.dry_run(), torch.no_grad():
             m.generator(torch.empty(batch_size, m.z_dim, device=m.device), torch.empty(batch_size, m.embed_dim, device=m.device),
@@ -69,42 +69,31 @@ def stage_model(cfg, stage, batch_size, dataset, device, resample_filter=None, *
 
 def restore_generator(m, ema=False):
     """ema=True: the moving average of the weights that `train_pggan.py --g-ema` keeps in the checkpoint, as the weights.
-    The checkpoint's resampling taps (`g_net/resample_filter`, written by `train_pggan.py --resample-filter`) must be the model's:
-    a difference — the key present in a model without taps and the taps given for a checkpoint without the key included — raises
-    RuntimeError naming both sides, because the weights would otherwise be sampled through another generator.  Likewise the style-based
-    generator (`train_pggan.py --style-dim`): a checkpoint whose generator was built with another --style-dim, --mapping-layers or
-    --no-style-noise than the model raises RuntimeError naming the flags, before any variable is read."""
-    from t2i_amd.models.pggan.pggan import RESAMPLE_KEY, describe_style, describe_taps, same_taps, style_of_names
-    names = checkpoint_names(m.check_dir_read)
-    if names is not None:
-        ckpt_style, model_style = style_of_names(names), (m.style_dim, m.mapping_layers if m.style_dim is not None else None,
-                                                          m.style_noise if m.style_dim is not None else None)
+    The checkpoint's generator must be the model's, or its weights would be sampled through another function: a checkpoint built with
+    another --style-dim, --mapping-layers or --no-style-noise (`train_pggan.py --style-dim`), or trained with other resampling taps
+    (`g_net/resample_filter`, written by `train_pggan.py --resample-filter`; the key present in a model without taps and the taps given
+    for a checkpoint without the key included), raises RuntimeError naming both sides, before any variable is read."""
+    arch = options.checkpoint_architecture(m.check_dir_read)
+    if arch is not None:
+        ckpt_style, model_style = options.style_of_names(arch[0]), (m.style_dim, m.mapping_layers if m.style_dim is not None else None,
+                                                                    m.style_noise if m.style_dim is not None else None)
         if ckpt_style != model_style:
             raise RuntimeError('the checkpoint in %s holds %s, but this model was built with %s: pass the same --style-dim / --mapping-layers / '
                                '--no-style-noise (style_dim=, mapping_layers=, style_noise=) the trainer was given' % (
-                                   m.check_dir_read, describe_style(ckpt_style), describe_style(model_style)))
-    found = []
+                                   m.check_dir_read, options.describe_style(ckpt_style), options.describe_style(model_style)))
+        if not options.same_taps(arch[1], m.resample_taps):
+            raise RuntimeError('the checkpoint in %s was trained with %s, but this model resamples with %s: pass the same --resample-filter '
+                               '(resample_filter=) the trainer was given' % (
+                                   m.check_dir_read, options.describe_taps(arch[1]), options.describe_taps(m.resample_taps)))
     restore_scopes(m.store, [('g_net', m.check_dir_read)], error=lambda scope: RuntimeError('Could not load stage %d' % m.stage), verbose=False,
-                   ema=ema, extra={RESAMPLE_KEY: ((lambda: None), found.append)})
-    ckpt = found[-1] if found else None
-    if not same_taps(ckpt, m.resample_taps):
-        raise RuntimeError('the checkpoint in %s was trained with %s, but this model resamples with %s: pass the same --resample-filter '
-                           '(resample_filter=) the trainer was given' % (m.check_dir_read, describe_taps(ckpt), describe_taps(m.resample_taps)))
+                   ema=ema)
 
 
 def checkpoint_names(directory):
     """{variable name: shape} of the generator's mapping-network and style-block entries in the newest checkpoint of `directory` (what
     utils/saver.load would read); None when there is no checkpoint."""
-    import re
-    import numpy as np
-    state = os.path.join(directory, 'checkpoint')
-    if not os.path.isfile(state):
-        return None
-    found = re.search(r'model_checkpoint_path: "([^"]+)"', open(state).read())
-    if not found or not os.path.isfile(os.path.join(directory, os.path.basename(found.group(1)))):
-        return None
-    with np.load(os.path.join(directory, os.path.basename(found.group(1)))) as z:
-        return {k: tuple(z[k].shape) for k in z.files if k.startswith('g_net/mapping/') or '/StyleMod' in k}
+    arch = options.checkpoint_architecture(directory)
+    return None if arch is None else arch[0]
 
 
 def generate(m, z, cond, cond_noise=True):
@@ -145,6 +134,29 @@ def load_stage_dataset(cfg, stage, device):
     return dataset
 
 
+class Reader(object):
+    """What the evaluator and the two visualisers do before their own work, with room for their own checks between the steps: the
+    reader flags added to `ap`, `argv` parsed and the architecture keywords made of it (an argument error before anything else); the
+    check that a stage has a checkpoint; the (dataset, model) of a stage on the device."""
+
+    def __init__(self, ap, argv, widths):
+        options.add_reader_arguments(ap)
+        self.args = ap.parse_args(argv)
+        self.kw = dict(widths, **options.kwargs_of(ap, self.args))
+
+    @staticmethod
+    def need_checkpoint(cfg, stage):
+        d = os.path.join(cfg.CHECKPOINT_DIR, 'stage%d' % stage)
+        if not os.path.isfile(os.path.join(d, 'checkpoint')):
+            raise RuntimeError('Could not load stage %d (no checkpoint in %s)' % (stage, d))
+
+    def open(self, cfg, stage, batch):
+        """-> (the stage's dataset, its model at `batch`) on the device."""
+        dev = torch.device('cuda')
+        dataset = load_stage_dataset(cfg, stage, dev)
+        return dataset, stage_model(cfg, stage, batch, dataset, dev, **self.kw)
+
+
 def main(argv=None, **widths):
     from t2i_amd.utils.config import config_from_yaml
     ap = argparse.ArgumentParser()
@@ -157,11 +169,8 @@ def main(argv=None, **widths):
     ap.add_argument('--batch', type=int, default=64, help='images generated (and scored) per batch [64]')
     ap.add_argument('--incep-batch', type=int, default=None, help='Inception batch (default: --batch)')
     ap.add_argument('--ema', action='store_true', help="score the moving average of the generator's weights (a checkpoint of train_pggan.py --g-ema)")
-    cli.add_resample_filter_argument(ap)
-    cli.add_style_arguments(ap)
-    args = ap.parse_args(argv)
-    taps = cli.resample_filter_of(ap, args)
-    widths = dict(widths, **cli.style_kwargs_of(ap, args))
+    reader = Reader(ap, argv, widths)
+    args = reader.args
     if not 1 <= args.stage <= 8:
         ap.error('--stage must be in 1..8')
     if args.batch < 1 or (args.incep_batch is not None and args.incep_batch < 1):
@@ -174,13 +183,10 @@ def main(argv=None, **widths):
     if args.eval == 'msssim' and args.msssim_pairs != 'caption' and args.batch < 2:
         ap.error('--eval msssim pairs image i of a batch with image i + batch // 2: --batch 2 or more (or --msssim-pairs caption)')
     cfg = config_from_yaml(args.cfg)
-    if not os.path.isfile(os.path.join(cfg.CHECKPOINT_DIR, 'stage%d' % args.stage, 'checkpoint')):
-        raise RuntimeError('Could not load stage %d (no checkpoint in %s)' % (args.stage, os.path.join(cfg.CHECKPOINT_DIR, 'stage%d' % args.stage)))
+    reader.need_checkpoint(cfg, args.stage)
     if cfg.EVAL.SIZE // args.batch == 0:
         raise ValueError('EVAL.SIZE %d is smaller than --batch %d' % (cfg.EVAL.SIZE, args.batch))
-    dev = torch.device('cuda')
-    dataset = load_stage_dataset(cfg, args.stage, dev)
-    m = stage_model(cfg, args.stage, args.batch, dataset, dev, resample_filter=taps, **widths)
+    dataset, m = reader.open(cfg, args.stage, args.batch)
     ev = PGGANEval(None, m, dataset, cfg, incep_batch_size=args.incep_batch)
     ev.ema = args.ema
     out = cli.run_eval(ev, args.eval, args.msssim_pairs, args.prdc_k, cli.subsets_of(args))

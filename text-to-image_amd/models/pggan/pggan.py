@@ -6,39 +6,11 @@ schedule in train_pggan.py:17-69: output size 4 * 2^(stage-1); with `trans` the 
 alpha = iter / steps next to the up-scaled previous `to_rgb` (generator) / the pooled-input `from_rgb` (critic).
 The losses reuse the hot path's WGAN-GP machinery (gradient penalty through a double-differentiable critic); new
 here: per-sample layer norm (generator only), 2x2 average pool and nearest x2 upscale (a pair of adjoint kernels, closed
-under differentiation — the critic is differentiated twice), the fade-in mix; `critic_norm='layer' | 'pixel'` (not in the
-reference; default None = the reference's critic) normalises the critic's 3x3 / 4x4 convolutions per sample; `critic_mbstd=G` (not in the
-reference either; default None) puts the progressive-growing paper's minibatch standard deviation in front of the critic's last block
-(DESIGN.md section 4.29); `g_ema=D` (the paper's `Gs`; default None) keeps an exponential moving average of the generator's weights, formed in
-the generator's Adam launch, that checkpoints carry and `ema_weights()` / `--ema` sample from (DESIGN.md section 4.30);
-`equalized_lr=True` (the paper's equalized learning rate; default False) draws every conv2d / fc kernel from N(0, c^2), c = sqrt(2 / fan_in),
-not truncated, and gives both optimizers the per-slot multipliers (c, c) for it: Adam on w-hat ~ N(0, 1) used as c * w-hat, restated on
-w = c * w-hat itself, so the convolutions, the checkpoints and the readers see plain weights.  The gain is sqrt(2)
-for every layer: the paper's gain 1 on the last linear layers (to_rgb's 1x1, the critic's last dense) is deliberately left out.  Biases and
-the layer-norm gamma / beta keep the multiplier 1.  `diffaug='color,translation,cutout'` (or any subset; default None) sends every image
-the critic sees, real or generated, through the differentiable augmentation T of Zhao et al. (utils.ops.diff_augment, DESIGN.md section
-4.35): the generator is trained through T, both gradient penalties are gradients of D o T, and the sampler, checkpoints, evaluators and
-summaries never see it; the parameter tables are `feed['aug_d']` [4B, 9] (rows G | x | x_mismatch | x_hat) and `feed['aug_g']` [B, 9],
-drawn when missing.  `diffaug_p=P` applies each transform with probability P and `diffaug_adapt=True` steers that probability from D(x) and
-D(G) at the end of the critic step; either one moves the draw of a missing table into the step, as one launch of the
-sampler's (utils.ops.DiffAugmentSampler: `diffaug_sampler`, or the model's own), which a captured graph holds; the critic step then also returns
-`Dx_logit`, `Dg_logit` and `aug_p`, all on the device.  `critic_sn=True` (default False) divides every conv2d / fc kernel of the critic by an estimate
-of its largest singular value (Miyato et al. 2018): `self.critic_spectral`, an optim.SpectralNorm, keeps the raw weights the critic's Adam steps
-and advances one power iteration per step, inside D_optimizer.apply(); the variables, and so the checkpoints and every reader, hold the
-normalised weights, and checkpoints also carry `<variable>/spectral_raw`, `_u`, `_v`, `_sigma`.
-`resample_filter=(1, 3, 3, 1)` (or any 2..8 finite taps with a positive sum; default None = the reference's resampling) replaces the
-generator's nearest x2 `upscale` by utils.ops.upsample_2d and the critic's 2x2 `pool` by utils.ops.downsample_2d with those taps, in the
-blocks and in both fade-in branches (Karras et al. 2019, Zhang 2019): one launch of csrc/t2i_resample.hip each,
-differentiable to any order.  This changes the generator's function, so checkpoints carry the normalised taps as `g_net/resample_filter`
-and the readers (eval_pggan.restore_generator) refuse a checkpoint whose taps differ from the model's.
-`style_dim=D` (default None = the reference's generator: today's variables, launches and checkpoint files) builds the style-based generator
-of Karras et al. 2019 (`_style_generator`): a mapping network `g_net/mapping` turns [z, c] into a style vector w,
-and every conv -> layer_norm(relu) pair of the generator becomes conv -> utils.ops.style_block (per-pixel noise, relu, instance norm, an
-affine map of w: csrc/t2i_style.hip); `mapping_layers`, `style_noise` and `truncation_psi` configure it, `feed['style_noise_{d,g}_<k>']`
-carry the noise images (drawn when missing), and the readers refuse a checkpoint built otherwise.  Style mixing, a learned constant input,
-bf16 tensors and modulated convolutions are out of scope.  `adam_lr=L` sets Adam's step size (default None: the reference's 2e-6).  Reference specifics kept: penalty
-coefficient 200, no kt term, G = -D_fake + 5 KL, Adam(2e-6, beta1=0, beta2=0.99) hard-coded (pggan.py:104-110; the
-`learning_rate` placeholder is fed but unused), eps of x_hat drawn in-graph (pggan.py:68 overrides the placeholder),
+under differentiation — the critic is differentiated twice), the fade-in mix.  The keywords from `critic_norm` on are
+not in the reference; every default is the reference's model, and options.py describes each one where it checks it.
+Reference specifics kept: penalty coefficient 200, no kt term, G = -D_fake + 5 KL, Adam(2e-6, beta1=0, beta2=0.99)
+(pggan.py:104-110; `adam_lr` replaces the step size; the `learning_rate` placeholder is fed but unused), eps of x_hat
+drawn in-graph (pggan.py:68 overrides the placeholder),
 `to_rgb` = k2 s1 SAME 9-channel relu conv + 1x1, every kernel He-initialised by utils/ops.py's defaults.
 `fmap_base` / `fmap_max` / the three sizes generalise the hard-coded 1024 / 512 / 128 / 1024 / 128 (defaults = the
 reference's) so that the golden step can be tiny.
@@ -47,7 +19,6 @@ whether the critic step's own forward sees the new or the previous value is a TF
 from `iter` BEFORE the critic step and kept for the generator step and the sampler — the assign-first order."""
 import contextlib
 import math
-import os
 import sys
 import time
 
@@ -58,65 +29,14 @@ from ... import kernels as K
 from ... import optim
 from ... import scope as S
 from ...graphs import DGSchedule, StepGraphs
-from ...utils.ops import (DiffAugmentSampler, concat_tile, conv2d, diff_augment, diff_augment_params, diff_augment_policy, downsample_2d, fc,
-                          layer_norm, lerp, lrelu_act, minibatch_stddev_stat, pixel_norm, pool, relu, style_block, upsample_2d, upscale)
+from ...utils.saver import Saver, load, save
+from ...utils.ops import (DiffAugmentSampler, concat_tile, conv2d, diff_augment, diff_augment_params, downsample_2d, fc, layer_norm, lerp,
+                          lrelu_act, minibatch_stddev_stat, pixel_norm, pool, relu, style_block, upsample_2d, upscale)
+from .options import RESAMPLE_KEY, W_AVG, checkpoint_architecture, describe_taps, same_taps, validated
+from .options import normalised_taps, style_of_names  # noqa: F401  (importable from here, as before)
 
-W_AVG = 'g_net/mapping/w_avg'                   # PGGAN(style_dim=D): the running mean of the style vector, [D], not trainable
 W_AVG_DECAY = 0.995
 STYLE_NOISE_CUT = 6.0                           # the style noise is kernels.trunc_normal_'s inverse-CDF draw cut at +-6 sigma: a standard normal to 24 bits
-RESAMPLE_KEY = 'g_net/resample_filter'          # the checkpoint entry of PGGAN(resample_filter=...): the taps divided by their sum, float32
-
-
-def normalised_taps(resample_filter):
-    """None -> None; a sequence of 2..8 finite taps with a positive sum -> (the taps as floats, taps / sum as a float32 array: what a
-    checkpoint carries); anything else is a ValueError."""
-    import numpy as np
-    if resample_filter is None:
-        return None
-    try:
-        k = tuple(float(t) for t in resample_filter)
-    except (TypeError, ValueError):
-        k = ()
-    if isinstance(resample_filter, str) or not 2 <= len(k) <= 8 or not all(math.isfinite(t) for t in k) or not math.fsum(k) > 0.0:
-        raise ValueError('resample_filter must be None or a sequence of 2..8 finite taps with a positive sum (the low-pass filter of the '
-                         'up- and downsampling, e.g. (1, 3, 3, 1)), got %r' % (resample_filter,))
-    norm = (np.asarray(k, dtype=np.float64) / math.fsum(k)).astype(np.float32)
-    if not np.isfinite(norm).all():
-        raise ValueError('resample_filter %r does not normalise to finite float32 taps' % (resample_filter,))
-    return k, norm
-
-
-def same_taps(a, b):
-    """Whether two normalised tap arrays (or None: no filter) describe the same resampling."""
-    import numpy as np
-    if a is None or b is None:
-        return a is None and b is None
-    a, b = np.asarray(a, dtype=np.float32).reshape(-1), np.asarray(b, dtype=np.float32).reshape(-1)
-    return a.shape == b.shape and bool((a == b).all())
-
-
-def describe_taps(norm):
-    """The taps of a message: 'no filter (nearest x2, 2x2 mean)' or the normalised values."""
-    if norm is None:
-        return 'no filter (nearest x2 upscale, 2x2 mean pool)'
-    return 'the normalised taps (%s)' % ', '.join('%.6g' % float(t) for t in norm)
-
-
-def style_of_names(names):
-    """(style_dim, mapping_layers, style_noise) of the generator whose variables are `names` ({name: shape}); (None, None, None) for the
-    reference's generator."""
-    import re
-    if W_AVG not in names:
-        return (None, None, None)
-    layers = sum(1 for n in names if re.match(r'^g_net/mapping/dense(_\d+)?/kernel$', n))
-    return (int(names[W_AVG][0]), layers, any(n.endswith('/noise_strength') for n in names))
-
-
-def describe_style(sig):
-    """A (style_dim, mapping_layers, style_noise) triple in the flags' words."""
-    if sig[0] is None:
-        return "the reference's generator (no --style-dim)"
-    return 'a style-based generator (--style-dim %d --mapping-layers %d%s)' % (sig[0], sig[1], '' if sig[2] else ' --no-style-noise')
 
 
 class PGGAN(object):
@@ -125,70 +45,16 @@ class PGGAN(object):
                  compr_embed_dim=128, dp=None, critic_norm=None, critic_mbstd=None, g_ema=None, equalized_lr=False, adam_lr=None,
                  diffaug=None, diffaug_p=None, diffaug_adapt=False, diffaug_sampler=None, critic_sn=False, resample_filter=None,
                  style_dim=None, mapping_layers=4, style_noise=True, truncation_psi=None):
-        if style_dim is not None and (isinstance(style_dim, bool) or not isinstance(style_dim, int) or style_dim < 1):
-            raise ValueError('style_dim must be None (the reference\'s generator) or an integer >= 1 (the width of the style vector w), got %r' % (style_dim,))
-        if isinstance(mapping_layers, bool) or not isinstance(mapping_layers, int) or mapping_layers < 1:
-            raise ValueError('mapping_layers must be an integer >= 1 (the dense layers of the mapping network), got %r' % (mapping_layers,))
-        if not isinstance(style_noise, bool):
-            raise ValueError('style_noise must be True or False, got %r' % (style_noise,))
-        if truncation_psi is not None and (isinstance(truncation_psi, bool) or not isinstance(truncation_psi, (int, float)) or not math.isfinite(truncation_psi)):
-            raise ValueError('truncation_psi must be None or a finite number (the sampler uses w_avg + psi (w - w_avg)), got %r' % (truncation_psi,))
-        if style_dim is None and truncation_psi is not None:
-            raise ValueError('truncation_psi needs style_dim (the style-based generator whose w it truncates), which is None')
-        self.style_dim, self.mapping_layers, self.style_noise = style_dim, mapping_layers, style_noise
-        self.truncation_psi = None if truncation_psi is None else float(truncation_psi)
+        # style_dim, mapping_layers, style_noise, truncation_psi, resample_filter, resample_taps, critic_sn, diffaug, diffaug_p, diffaug_adapt,
+        # aug_sampler (the model's own is made below, on the store's device), adam_lr, equalized_lr, g_ema, critic_norm, critic_mbstd, mbstd_group
+        vars(self).update(validated(
+            batch_size, critic_norm=critic_norm, critic_mbstd=critic_mbstd, g_ema=g_ema, equalized_lr=equalized_lr, adam_lr=adam_lr, diffaug=diffaug,
+            diffaug_p=diffaug_p, diffaug_adapt=diffaug_adapt, diffaug_sampler=diffaug_sampler, critic_sn=critic_sn, resample_filter=resample_filter,
+            style_dim=style_dim, mapping_layers=mapping_layers, style_noise=style_noise, truncation_psi=truncation_psi))
         self._sn = None                           # where the style blocks take their noise from: (feed, 'd' | 'g'), a list of images, or None (drawn)
-        taps = normalised_taps(resample_filter)
-        self.resample_filter = None if taps is None else taps[0]          # the taps as given; None: nearest x2 and the 2x2 mean
-        self.resample_taps = None if taps is None else taps[1]            # ... divided by their sum, float32: what checkpoints carry
-        self.resample_restored = None                                     # train(): the taps of the checkpoint the last restore read (None: it had none)
-        if not isinstance(critic_sn, bool):
-            raise ValueError('critic_sn must be True or False, got %r' % (critic_sn,))
-        self.critic_sn = critic_sn
+        self.resample_restored = None             # train(): the taps of the checkpoint the last restore read (None: it had none)
         self.critic_spectral = None
         self.spectral_synced = None               # train(): how many normalised kernels the last restore had to sync from their weights
-        if diffaug is not None:
-            try:
-                diff_augment_policy(diffaug, 'diffaug')
-            except ValueError:
-                raise ValueError("diffaug must be None or a comma-separated, non-empty subset of 'color,translation,cutout' (the "
-                                 "differentiable augmentation in front of the critic), got %r" % (diffaug,))
-        self.diffaug = diffaug
-        if diffaug_p is not None and (isinstance(diffaug_p, bool) or not isinstance(diffaug_p, (int, float)) or not 0.0 <= diffaug_p <= 1.0):
-            raise ValueError('diffaug_p must be None or a probability in [0, 1] (each transform of diffaug is applied with it), got %r' % (diffaug_p,))
-        if not isinstance(diffaug_adapt, bool):
-            raise ValueError('diffaug_adapt must be True or False, got %r' % (diffaug_adapt,))
-        if diffaug_sampler is not None and not isinstance(diffaug_sampler, DiffAugmentSampler):
-            raise ValueError('diffaug_sampler must be None or a utils.ops.DiffAugmentSampler, got %r' % (diffaug_sampler,))
-        if diffaug is None and (diffaug_p is not None or diffaug_adapt or diffaug_sampler is not None):
-            raise ValueError('diffaug_p, diffaug_adapt and diffaug_sampler need diffaug (the policy they apply), which is None')
-        if diffaug_sampler is not None and diffaug_sampler.mask != diff_augment_policy(diffaug, 'diffaug'):
-            raise ValueError('diffaug_sampler draws for the policy %r, diffaug is %r' % (diffaug_sampler.policy, diffaug))
-        if diffaug_sampler is not None and diffaug_adapt and diffaug_sampler.adapt is None:
-            raise ValueError('diffaug_adapt=True, but the diffaug_sampler that was passed has adapt=None')
-        self.diffaug_p, self.diffaug_adapt = diffaug_p, diffaug_adapt
-        self.aug_sampler = diffaug_sampler        # (the model's own is made below, on the store's device)
-        if adam_lr is not None and (isinstance(adam_lr, bool) or not isinstance(adam_lr, (int, float)) or not (math.isfinite(adam_lr) and adam_lr > 0.0)):
-            raise ValueError("adam_lr must be None (the reference's 2e-6) or a finite step size > 0, got %r" % (adam_lr,))
-        self.adam_lr = 0.000002 if adam_lr is None else float(adam_lr)
-        if not isinstance(equalized_lr, bool):
-            raise ValueError('equalized_lr must be True or False, got %r' % (equalized_lr,))
-        self.equalized_lr = equalized_lr
-        if g_ema is not None and (isinstance(g_ema, bool) or not isinstance(g_ema, (int, float)) or not 0.0 < g_ema < 1.0):
-            raise ValueError("g_ema must be None or a decay in (0, 1) (the moving average of the generator's weights), got %r" % (g_ema,))
-        self.g_ema = None if g_ema is None else float(g_ema)
-        if critic_norm not in (None, 'layer', 'pixel'):
-            raise ValueError("critic_norm must be None, 'layer' or 'pixel', got %r" % (critic_norm,))
-        self.critic_norm = critic_norm
-        if critic_mbstd is not None and (isinstance(critic_mbstd, bool) or not isinstance(critic_mbstd, int) or critic_mbstd < 1):
-            raise ValueError('critic_mbstd must be None or an integer >= 1 (the group size of the minibatch standard deviation), got %r'
-                             % (critic_mbstd,))
-        if critic_mbstd is not None and (isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1):
-            raise ValueError('critic_mbstd needs an integer batch_size >= 1 to pick its group size from, got %r' % (batch_size,))
-        # the group: the largest divisor of the batch not above the argument (and the kernels' 16), so that groups of contiguous rows
-        # never straddle the B-row parts of the critic's 3B pass; per rank under data parallelism (batch_size is the local batch)
-        self.critic_mbstd = critic_mbstd
-        self.mbstd_group = None if critic_mbstd is None else max(g for g in range(1, min(critic_mbstd, 16) + 1) if batch_size % g == 0)
         self.batch_size, self.steps = batch_size, steps
         self.check_dir_write, self.check_dir_read = check_dir_write, check_dir_read
         self.dataset, self.sample_path, self.log_dir = dataset, sample_path, log_dir
@@ -519,77 +385,27 @@ class PGGAN(object):
         return layer_norm(x, act=act) if self.critic_norm == 'layer' else pixel_norm(x, act=act)
 
     def generator(self, z_var, cond_inp, stages, t, reuse=False, cond_noise=True, truncation_psi=None):
-        """-> (image NHWC, mean, log_sigma)  (pggan.py:283-316)"""
-        if self.style_dim is not None:
-            return self._style_generator(z_var, cond_inp, stages, t, reuse, cond_noise, truncation_psi)
+        """-> (image NHWC, mean, log_sigma)  (pggan.py:283-316).  With style_dim (Karras et al. 2019) the dense
+        4x4 trunk from [z, c] stays (no learned constant), the mapping network comes between it and the first convolution, and every
+        conv -> layer_norm(relu) pair is a conv -> style block (_g_conv); to_rgb, the fade-in and _up are the reference's either way.
+        truncation_psi (style_dim only; None: the constructor's) replaces w by w_avg + psi (w - w_avg); training never truncates
+        (g_losses and d_losses pass None with the constructor's None)."""
         alpha_trans = self._alpha_dev
+        stage0 = self.get_conv_scope_name(0)
         with S.variable_scope('g_net', reuse=reuse):
-            with S.variable_scope(self.get_conv_scope_name(0), reuse=reuse):
-                mean_lr, log_sigma_lr = self.generate_conditionals(cond_inp)
-                cond = self.sample_normal_conditional(mean_lr, log_sigma_lr, cond_noise)
-                x = torch.cat([z_var, cond], 1)
-                x = self._fc(x, units=4 * 4 * self.get_nf(0))
-                x = layer_norm(x)
-                x = x.reshape(-1, 4, 4, self.get_nf(0))
-                x = self._conv2d(x, f=self.get_nf(0), ks=(3, 3), s=(1, 1))
-                x = layer_norm(x, act=relu)
-                x = self._conv2d(x, f=self.get_nf(0), ks=(3, 3), s=(1, 1))
-                x = layer_norm(x, act=relu)
-            x_iden = None
-            for i in range(1, stages):
-                if (i == stages - 1) and t:
-                    x_iden = self.to_rgb(x, stages - 2)
-                    x_iden = self._up(x_iden)
-                with S.variable_scope(self.get_conv_scope_name(i), reuse=reuse):
-                    x = self._up(x)
-                    x = self._conv2d(x, f=self.get_nf(i), ks=(3, 3), s=(1, 1))
-                    x = layer_norm(x, act=relu)
-                    x = self._conv2d(x, f=self.get_nf(i), ks=(3, 3), s=(1, 1))
-                    x = layer_norm(x, act=relu)
-            x = self.to_rgb(x, stages - 1)
-            if t:
-                x = lerp(x_iden, x, alpha_trans)                  # (1 - alpha) * x_iden + alpha * x
-            return x, mean_lr, log_sigma_lr
-
-    def _style_generator(self, z_var, cond_inp, stages, t, reuse, cond_noise, truncation_psi):
-        """The style-based generator (style_dim=D; Karras et al. 2019).  The dense 4x4 trunk from [z, c] stays
-        (no learned constant); a mapping network (scope g_net/mapping: pixel norm of [z, c], then mapping_layers dense + lrelu layers)
-        gives w [B,D]; every conv -> layer_norm(relu) pair becomes conv -> style_block(x, w, noise, relu): per-pixel noise scaled per
-        channel, relu, instance norm, the style's affine map.  to_rgb, the fade-in and _up are the reference's.  g_net/mapping/w_avg [D]
-        (not trainable) follows the batch mean of w with decay 0.995 in g_losses; under data parallelism it is rank-local — every rank
-        averages its own batches — and rank 0's is the one a checkpoint holds.  truncation_psi (None: the constructor's) replaces w by
-        w_avg + psi (w - w_avg); training never truncates (g_losses and d_losses pass None with the constructor's None)."""
-        alpha_trans = self._alpha_dev
-        psi = self.truncation_psi if truncation_psi is None else float(truncation_psi)
-        B = z_var.shape[0]
-        block = [0]
-
-        def styled(x, f):
-            x = self._conv2d(x, f=f, ks=(3, 3), s=(1, 1))
-            k = block[0]
-            block[0] += 1
-            return style_block(x, w, noise=self._style_noise_image(k, x), act=relu, init=self._init(self.style_dim))
-
-        with S.variable_scope('g_net', reuse=reuse):
-            with S.variable_scope(self.get_conv_scope_name(0), reuse=reuse):
+            with S.variable_scope(stage0, reuse=reuse):
                 mean_lr, log_sigma_lr = self.generate_conditionals(cond_inp)
                 cond = self.sample_normal_conditional(mean_lr, log_sigma_lr, cond_noise)
                 zc = torch.cat([z_var, cond], 1)
                 x = self._fc(zc, units=4 * 4 * self.get_nf(0))
                 x = layer_norm(x)
                 x = x.reshape(-1, 4, 4, self.get_nf(0))
-            with S.variable_scope('mapping', reuse=reuse):
-                w = pixel_norm(zc.reshape(B, 1, 1, zc.shape[1])).reshape(B, zc.shape[1])
-                for _ in range(self.mapping_layers):
-                    w = self._fc(w, units=self.style_dim, act=lrelu_act())
-                w_avg = self.store.get_variable('w_avg', (self.style_dim,), S.constant_init(0.0), trainable=False)
-            self._w = w
-            if psi is not None:
-                w = torch.lerp(w_avg.expand_as(w), w, psi)                # psi = 1: w, psi = 0: w_avg, both exactly
-            self._w_used = w                                              # (what the style blocks see: w, or its truncation)
-            with S.variable_scope(self.get_conv_scope_name(0), reuse=reuse):      # (re-entered: only Conv and StyleMod layers follow)
-                x = styled(x, self.get_nf(0))
-                x = styled(x, self.get_nf(0))
+                if self.style_dim is None:
+                    x = self._g_conv(self._g_conv(x, self.get_nf(0)), self.get_nf(0))
+            if self.style_dim is not None:
+                self._mapping(zc, reuse, self.truncation_psi if truncation_psi is None else float(truncation_psi))
+                with S.variable_scope(stage0, reuse=reuse):                # (re-entered: only Conv and StyleMod layers follow)
+                    x = self._g_conv(self._g_conv(x, self.get_nf(0)), self.get_nf(0))
             x_iden = None
             for i in range(1, stages):
                 if (i == stages - 1) and t:
@@ -597,12 +413,35 @@ class PGGAN(object):
                     x_iden = self._up(x_iden)
                 with S.variable_scope(self.get_conv_scope_name(i), reuse=reuse):
                     x = self._up(x)
-                    x = styled(x, self.get_nf(i))
-                    x = styled(x, self.get_nf(i))
+                    x = self._g_conv(self._g_conv(x, self.get_nf(i)), self.get_nf(i))
             x = self.to_rgb(x, stages - 1)
             if t:
                 x = lerp(x_iden, x, alpha_trans)                  # (1 - alpha) * x_iden + alpha * x
             return x, mean_lr, log_sigma_lr
+
+    def _mapping(self, zc, reuse, psi):
+        """style_dim: the mapping network (scope g_net/mapping: pixel norm of [z, c], then mapping_layers dense + lrelu layers) -> self._w
+        [B,D], and self._w_used, what the style blocks of this pass see: w, or with psi its truncation.  g_net/mapping/w_avg [D] (not
+        trainable) follows the batch mean of w with decay 0.995 in g_losses; under data parallelism it is rank-local — every rank averages
+        its own batches — and rank 0's is the one a checkpoint holds."""
+        B = zc.shape[0]
+        with S.variable_scope('mapping', reuse=reuse):
+            w = pixel_norm(zc.reshape(B, 1, 1, zc.shape[1])).reshape(B, zc.shape[1])
+            for _ in range(self.mapping_layers):
+                w = self._fc(w, units=self.style_dim, act=lrelu_act())
+            w_avg = self.store.get_variable('w_avg', (self.style_dim,), S.constant_init(0.0), trainable=False)
+        self._w = w
+        self._w_used = w if psi is None else torch.lerp(w_avg.expand_as(w), w, psi)       # psi = 1: w, psi = 0: w_avg, both exactly
+        self._block = 0                                                   # the style blocks of the pass, counted by _g_conv
+
+    def _g_conv(self, x, f):
+        """A 3x3 convolution of the generator and what follows it: the reference's layer_norm(relu), or with style_dim style block k of
+        the pass: per-pixel noise scaled per channel, relu, instance norm, the style's affine map."""
+        x = self._conv2d(x, f=f, ks=(3, 3), s=(1, 1))
+        if self.style_dim is None:
+            return layer_norm(x, act=relu)
+        k, self._block = self._block, self._block + 1
+        return style_block(x, self._w_used, noise=self._style_noise_image(k, x), act=relu, init=self._init(self.style_dim))
 
     def _style_noise_image(self, k, x):
         """The noise image [B,H,W] of style block k: the feed's `style_noise_{d,g}_<k>`, the k-th of the sampler's list, or a fresh draw."""
@@ -710,65 +549,64 @@ class PGGAN(object):
         self.writer.add_summary(vals, idx)
         self.writer.flush()
 
+    def _savers(self):
+        """(the saver of this stage's checkpoints, the saver that restores: the previous stage's variables for a transition, else the
+        same one).  Each option's entries travel with every checkpoint and only with the option: without it the files are what they were."""
+        shadows = [self.G_optimizer] if self.g_ema is not None else None      # both savers: a transition restores the previous stage's shadows too
+        extra, loaded = {}, {}
+        self._loaded = loaded                     # key -> what a restore read of it, for _after_restore
+        if self.aug_sampler is not None:          # the sampler's sixteen state words; a checkpoint written without them leaves the sampler as it is
+            extra['diffaug/state'] = (self.aug_sampler.state_dict, lambda w: (loaded.__setitem__('diffaug/state', w), self.aug_sampler.load_state_dict(w)))
+        sn = self.critic_spectral
+        for key in () if sn is None else [k for n in sn.names for k in sn.keys(n)]:
+            # the raw weights, u, v and sigma of every normalised kernel; the variable itself is saved as the normalised weights every reader expects
+            extra[key] = ((lambda key=key: sn.state_tensor(key).numpy()), (lambda a, key=key: loaded.__setitem__(key, a)))
+        if self.resample_filter is not None:
+            # the normalised taps, so that a reader built with other taps, or none, can refuse the generator instead of sampling another
+            # function from its weights (what a restore found is read from the file: _after_restore)
+            extra[RESAMPLE_KEY] = ((lambda: self.resample_taps), lambda a: None)
+        saver = Saver(self.store, var_list=self.get_variables_up_to_stage(self.stage), max_to_keep=2, shadows=shadows, extra=extra)
+        if not self.trans:
+            return saver, saver
+        return saver, Saver(self.store, var_list=self.get_variables_up_to_stage(self.stage - 1), shadows=shadows, extra=extra)
+
+    def _after_restore(self, src, log):
+        """What a restore through `src` leaves to do: the taps the checkpoint was trained with, the spectral state, the sampler's words."""
+        self.resample_restored = checkpoint_architecture(self.check_dir_read)[1]
+        if not same_taps(self.resample_restored, self.resample_taps):
+            # the trainer goes on (a stage may be grown with another filter on purpose); the readers refuse (eval_pggan.restore_generator)
+            log('resample filter: the checkpoint in %s was trained with %s, this model resamples with %s' % (
+                self.check_dir_read, describe_taps(self.resample_restored), describe_taps(self.resample_taps)))
+        sn = self.critic_spectral
+        if sn is not None:
+            # a kernel that was restored and whose four keys the file holds is restored verbatim; every other one starts from the
+            # weights it has now (a checkpoint trained without the flag, a variable new at this stage)
+            whole = [n for n in sn.names if src._is_selected(n) and all(k in self._loaded for k in sn.keys(n))]
+            sn.load_state_dict({k: self._loaded[k] for n in whole for k in sn.keys(n)})
+            synced = [n for n in sn.names if n not in set(whole)]
+            sn.sync(synced)
+            self.spectral_synced = len(synced)
+            log('spectral normalisation: %d of %d kernels restored with their state, %d synced from their weights' % (
+                len(whole), len(sn.names), len(synced)))
+        if self.aug_sampler is not None and 'diffaug/state' not in self._loaded:
+            log('the checkpoint in %s carries no augmentation state: p stays %.6f, call counter %d' % (
+                self.check_dir_read, self.aug_sampler.p, self.aug_sampler.counter))
+
     def train(self, max_steps=None, log=None, side_effects=False, summaries=False, final_sample=False):
         """Stage schedule semantics of pggan.py:147-247: a transition stage restores the previous stage's variables
         (`get_variables_up_to_stage(stage - 1)`) from check_dir_read, a stabilisation stage its own; new variables keep
         their fresh initialisation; checkpoints of `get_variables_up_to_stage(stage)` go to check_dir_write.  What was
         restored is kept in `self.restored` = (directory, step, variable names), None when nothing was.  final_sample: the
         last iteration, which writes the last checkpoint, also writes a sample grid (the reference only samples every 2000)."""
-        from ...utils.saver import Saver, load, save
         from ...utils.utils import get_balanced_factorization, save_captions, save_images
         log = log or (lambda s: (sys.stdout.write(s + '\n'), sys.stdout.flush()))
-        shadows = [self.G_optimizer] if self.g_ema is not None else None      # both savers: a transition restores the previous stage's shadows too
-        # the augmentation sampler's sixteen state words travel with every checkpoint (and only with a sampler: without one the files
-        # are what they were); a checkpoint written without them leaves the sampler as it is
-        words_loaded = []
-        extra = None if self.aug_sampler is None else {
-            'diffaug/state': (self.aug_sampler.state_dict, lambda w: (self.aug_sampler.load_state_dict(w), words_loaded.append(True)))}
-        sn, sn_loaded = self.critic_spectral, {}
-        if sn is not None:
-            # the raw weights, u, v and sigma of every normalised kernel travel with every checkpoint (and only with the flag: without it
-            # the files are what they were); the variable itself is saved as the normalised weights every other reader expects
-            extra = dict(extra or {})
-            for n in sn.names:
-                for key in sn.keys(n):
-                    extra[key] = ((lambda key=key: sn.state_tensor(key).numpy()), (lambda a, key=key: sn_loaded.__setitem__(key, a)))
-        taps_loaded = []
-        if self.resample_filter is not None:
-            # the normalised taps travel with every checkpoint (and only with the flag: without it the files are what they were), so that
-            # a reader built with other taps, or none, can refuse the generator instead of sampling another function from its weights
-            extra = dict(extra or {})
-            extra[RESAMPLE_KEY] = ((lambda: self.resample_taps), taps_loaded.append)
-        saver = Saver(self.store, var_list=self.get_variables_up_to_stage(self.stage), max_to_keep=2, shadows=shadows, extra=extra)
+        saver, src = self._savers()
         if side_effects and self.stage != 1:
-            src = Saver(self.store, var_list=self.get_variables_up_to_stage(self.stage - 1), shadows=shadows, extra=extra) if self.trans else saver
             could_load, step = load(src, None, self.check_dir_read)
             if not could_load:
                 raise RuntimeError('Could not load previous stage during transition' if self.trans else 'Could not load current stage')
             self.restored = (self.check_dir_read, step, list(src.var_list))
-            if self.resample_filter is None:          # no entry of ours to be handed the key: look into the file that was read
-                import numpy as np
-                with np.load(os.path.join(self.check_dir_read, 'model-%d.npz' % step)) as z:
-                    if RESAMPLE_KEY in z.files:
-                        taps_loaded.append(z[RESAMPLE_KEY])
-            self.resample_restored = taps_loaded[-1] if taps_loaded else None
-            if not same_taps(self.resample_restored, self.resample_taps):
-                # the trainer goes on (a stage may be grown with another filter on purpose); the readers refuse (eval_pggan.restore_generator)
-                log('resample filter: the checkpoint in %s was trained with %s, this model resamples with %s' % (
-                    self.check_dir_read, describe_taps(self.resample_restored), describe_taps(self.resample_taps)))
-            if sn is not None:
-                # a kernel that was restored and whose four keys the file holds is restored verbatim; every other one starts from the
-                # weights it has now (a checkpoint trained without the flag, a variable new at this stage)
-                whole = [n for n in sn.names if src._is_selected(n) and all(k in sn_loaded for k in sn.keys(n))]
-                sn.load_state_dict({k: sn_loaded[k] for n in whole for k in sn.keys(n)})
-                synced = [n for n in sn.names if n not in set(whole)]
-                sn.sync(synced)
-                self.spectral_synced = len(synced)
-                log('spectral normalisation: %d of %d kernels restored with their state, %d synced from their weights' % (
-                    len(whole), len(sn.names), len(synced)))
-            if self.aug_sampler is not None and not words_loaded:
-                log('the checkpoint in %s carries no augmentation state: p stays %.6f, call counter %d' % (
-                    self.check_dir_read, self.aug_sampler.p, self.aug_sampler.counter))
+            self._after_restore(src, log)
         gen = torch.Generator(device=self.device).manual_seed(1234)
         if side_effects:
             sample_z = torch.randn((self.sample_num, self.z_dim), generator=gen, device=self.device)

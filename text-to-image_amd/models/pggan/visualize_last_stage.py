@@ -18,8 +18,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))))
 
 import t2i_amd  # noqa: E402,F401
-from t2i_amd.models import cli  # noqa: E402
-from t2i_amd.models.pggan.eval_pggan import generate, load_stage_dataset, restore_generator, stage_model  # noqa: E402
+from t2i_amd.models.pggan.eval_pggan import Reader, generate, load_stage_dataset, restore_generator, stage_model  # noqa: E402
 from t2i_amd.models.wgancls.visualize_wgan import WGanClsVisualizer  # noqa: E402
 from t2i_amd.utils import visualize as V  # noqa: E402
 
@@ -48,10 +47,10 @@ def stage_sample(samples, size=128):
     return out
 
 
-def visualize_last_stage(cfg, dataset, device, batch_size=64, stages=STAGES, ema=False, resample_filter=None, **widths):
+def visualize_last_stage(cfg, dataset, device, batch_size=64, stages=STAGES, ema=False, **kw):
     """-> dict(sheets: the uint8 sheets written, samples: the clipped stage outputs, resized: stage_sample's result).
-    resample_filter: the taps every stage was trained with (stage_model's; a checkpoint with other taps is refused)."""
-    z_dim = widths.get('z_dim', 128)
+    kw: stage_model's: the widths and the architecture every stage was trained with (a checkpoint built otherwise is refused)."""
+    z_dim = kw.get('z_dim', 128)
     z_sample = np.random.standard_normal((batch_size, z_dim))
     dataset_pos = np.random.randint(0, dataset.test.num_examples)
     _, conditions, _, captions = dataset.test.next_batch_test(batch_size, dataset_pos, 1)
@@ -61,7 +60,7 @@ def visualize_last_stage(cfg, dataset, device, batch_size=64, stages=STAGES, ema
     all_samples = []
     for stage in stages:
         print('Generating stage %d' % stage, flush=True)
-        m = stage_model(cfg, stage, batch_size, dataset, device, resample_filter=resample_filter, **widths)
+        m = stage_model(cfg, stage, batch_size, dataset, device, **kw)
         restore_generator(m, ema=ema)
         all_samples.append(generate(m, z, cond).cpu().numpy())
         del m
@@ -78,19 +77,13 @@ def main(argv=None, **widths):
     ap = argparse.ArgumentParser()
     ap.add_argument('--cfg', required=True, help='models/pggan/cfg/flowers.yml or birds.yml')
     ap.add_argument('--ema', action='store_true', help="every stage from the moving average of its generator's weights (checkpoints of train_pggan.py --g-ema)")
-    cli.add_resample_filter_argument(ap)
-    cli.add_style_arguments(ap)
-    args = ap.parse_args(argv)
-    taps = cli.resample_filter_of(ap, args)
-    widths = dict(widths, **cli.style_kwargs_of(ap, args))
-    cfg = config_from_yaml(args.cfg)
+    reader = Reader(ap, argv, widths)
+    cfg = config_from_yaml(reader.args.cfg)
     for stage in STAGES:
-        d = os.path.join(cfg.CHECKPOINT_DIR, 'stage%d' % stage)
-        if not os.path.isfile(os.path.join(d, 'checkpoint')):
-            raise RuntimeError('Could not load stage %d (no checkpoint in %s)' % (stage, d))
+        reader.need_checkpoint(cfg, stage)
     dev = torch.device('cuda')
     dataset = load_stage_dataset(cfg, 5, dev)         # TextDataset(datadir, 64) as the reference: only its test captions are used
-    return visualize_last_stage(cfg, dataset, dev, ema=args.ema, resample_filter=taps, **widths)
+    return visualize_last_stage(cfg, dataset, dev, ema=reader.args.ema, **reader.kw)
 
 
 if __name__ == '__main__':

@@ -27,8 +27,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))))
 
 import t2i_amd  # noqa: E402,F401
-from t2i_amd.models import cli  # noqa: E402
-from t2i_amd.models.pggan.eval_pggan import generate, load_stage_dataset, restore_generator, stage_model  # noqa: E402
+from t2i_amd.models.pggan.eval_pggan import Reader, generate, restore_generator  # noqa: E402
 from t2i_amd.models.wgancls.visualize_wgan import WGanClsVisualizer  # noqa: E402
 from t2i_amd.utils import visualize as V  # noqa: E402
 
@@ -124,21 +123,15 @@ def main(argv=None, **widths):
     ap.add_argument('--interp', type=int, default=40, help='rounds of interpolation / caption sheets [40]')
     ap.add_argument('--stage', type=int, default=7, help='the stage whose generator draws the sheets [7]')
     ap.add_argument('--ema', action='store_true', help="draw from the moving average of the generator's weights (a checkpoint of train_pggan.py --g-ema)")
-    cli.add_resample_filter_argument(ap)
-    cli.add_style_arguments(ap)
-    args = ap.parse_args(argv)
-    taps = cli.resample_filter_of(ap, args)
-    widths = dict(widths, **cli.style_kwargs_of(ap, args))
+    reader = Reader(ap, argv, widths)
+    args = reader.args
     if args.interp < 0 or not 1 <= args.stage <= 8:
         ap.error('--interp must be >= 0 and --stage in 1..8')
     cfg = config_from_yaml(args.cfg)
     if cfg.DATASET_NAME not in SPECIAL:
         raise ValueError('DATASET_NAME %r has no special positions (known: %s)' % (cfg.DATASET_NAME, sorted(SPECIAL)))
-    if not os.path.isfile(os.path.join(cfg.CHECKPOINT_DIR, 'stage%d' % args.stage, 'checkpoint')):
-        raise RuntimeError('Could not load stage %d (no checkpoint in %s)' % (args.stage, os.path.join(cfg.CHECKPOINT_DIR, 'stage%d' % args.stage)))
-    dev = torch.device('cuda')
-    dataset = load_stage_dataset(cfg, args.stage, dev)
-    m = stage_model(cfg, args.stage, 64, dataset, dev, resample_filter=taps, **widths)
+    reader.need_checkpoint(cfg, args.stage)
+    dataset, m = reader.open(cfg, args.stage, 64)
     return PGGANVisualizer(None, m, dataset, cfg, ema=args.ema).visualize(args.interp)
 
 

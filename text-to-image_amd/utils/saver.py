@@ -161,21 +161,30 @@ def save(saver, sess, checkpoint_dir, step):
     return path
 
 
+def latest_checkpoint(checkpoint_dir):
+    """The archive `load` reads: the one the directory's `checkpoint` state file names, if both exist (a newer archive the state file
+    does not name is not it); else None."""
+    state = os.path.join(checkpoint_dir, 'checkpoint')
+    if os.path.isfile(state):
+        m = re.search(r'model_checkpoint_path: "([^"]+)"', open(state).read())
+        if m and os.path.isfile(os.path.join(checkpoint_dir, m.group(1))):
+            return os.path.join(checkpoint_dir, os.path.basename(m.group(1)))
+    return None
+
+
 def load(saver, sess, checkpoint_dir, ema=False):
     """reference utils/saver.py:13-25 -> (could_load, counter).  ema: Saver.restore's."""
     print(' [*] Reading checkpoints from %s...' % checkpoint_dir)
-    state = os.path.join(checkpoint_dir, 'checkpoint')
-    if os.path.exists(state):
-        m = re.search(r'model_checkpoint_path: "([^"]+)"', open(state).read())
-        if m and os.path.exists(os.path.join(checkpoint_dir, m.group(1))):
-            ckpt_name = os.path.basename(m.group(1))
-            saver.restore(os.path.join(checkpoint_dir, ckpt_name), ema=ema)
-            saver._kept = _existing(checkpoint_dir)          # pruning continues across the resume
-            counter = int(next(re.finditer(r'(\d+)(?!.*\d)', ckpt_name)).group(0))
-            print(' [*] Success to read {}'.format(ckpt_name))
-            return True, counter
-    print(' [*] Failed to find checkpoints')
-    return False, 0
+    path = latest_checkpoint(checkpoint_dir)
+    if path is None:
+        print(' [*] Failed to find checkpoints')
+        return False, 0
+    ckpt_name = os.path.basename(path)
+    saver.restore(path, ema=ema)
+    saver._kept = _existing(checkpoint_dir)          # pruning continues across the resume
+    counter = int(next(re.finditer(r'(\d+)(?!.*\d)', ckpt_name)).group(0))
+    print(' [*] Success to read {}'.format(ckpt_name))
+    return True, counter
 
 
 def restore_scopes(store, pairs, create=None, error=RuntimeError, verbose=True, ema=False, extra=None):
