@@ -139,19 +139,38 @@ __global__ __launch_bounds__(256) void thin_deconv_k4s2_kernel(const void* __res
 // channels at a time: 0.11 instead of 0.33 LDS reads per FMA).  35 -> 47-48 us at B = 64, 88 -> 98-135 us at B = 192: the kernel is
 // bound by STAGING the dy patch (global -> registers -> LDS with per-element index arithmetic, one workgroup per CU, passes separated
 // by barriers), not by the LDS reads of the inner loop; four times fewer, four times larger workgroups made that worse.
+constexpr size_t kLdsBytesPerCU = 160 * 1024;      // gfx950: one workgroup may take all of it, no more (this file is gfx950 only)
+
+// The passes over the channels and the LDS bytes of one workgroup, for eligibility and launch alike (host arithmetic only).
+// A split into `parts` passes is legal when every pass stages a whole number of float4 and, beyond one pass, at least 32 channels.
+// The tuning value is the starting point (halved until it is legal, as ever); where its patch does not fit a CU the passes are
+// doubled while that stays legal.  0: no legal split fits (e.g. Cin = 4 with Cout = 252: one pass only, 166 912 bytes).
+static int thin_deconv_passes(int Cin, int Cout, size_t* lds_bytes) {
+  auto legal = [&](int parts) { return parts == 1 || ((Cout % (4 * parts)) == 0 && Cout / parts >= 32); };
+  auto bytes = [&](int parts) { const int CH = Cout / parts; return ((size_t)100 * (CH + 4) + (size_t)16 * Cin * CH) * sizeof(float); };
+  int parts = tuning().thin_parts;                  // 1, 2 or 4: Co / parts channels are staged at a time
+  if (parts < 1) parts = 1;
+  while (!legal(parts)) parts >>= 1;
+  while (bytes(parts) > kLdsBytesPerCU) {
+    if (!legal(2 * parts)) return 0;
+    parts *= 2;
+  }
+  if (lds_bytes) *lds_bytes = bytes(parts);
+  return parts;
+}
+
 bool thin_deconv_eligible(const t2i_conv_desc& d) {
   return d.KH == 4 && d.KW == 4 && d.SH == 2 && d.SW == 2 && d.pad_t == 1 && d.pad_l == 1 && d.Cin >= 1 && d.Cin <= 4 &&
          (d.Cout % 4) == 0 && d.Cout >= 16 && d.Cout <= 512 && (d.H % 16) == 0 && (d.W % 16) == 0 && d.Ho * 2 == d.H &&
-         d.Wo * 2 == d.W;
+         d.Wo * 2 == d.W && thin_deconv_passes(d.Cin, d.Cout, nullptr) > 0;
 }
 
 hipError_t thin_deconv_launch(const t2i_conv_desc& d, const void* dy, const float* w, const float* bias, float* dx,
                               int act, float alpha, hipStream_t stream, bool dy_bf16) {
-  int parts = tuning().thin_parts;                  // passes over the channels (1, 2 or 4): Co / parts are staged at a time
-  if (parts < 1) parts = 1;
-  while (parts > 1 && ((d.Cout % (4 * parts)) != 0 || d.Cout / parts < 32)) parts >>= 1;
+  size_t lds = 0;
+  const int parts = thin_deconv_passes(d.Cin, d.Cout, &lds);
+  if (parts < 1) return hipErrorInvalidValue;       // not eligible: the callers ask thin_deconv_eligible first
   const int CH = d.Cout / parts;
-  const size_t lds = ((size_t)100 * (CH + 4) + (size_t)16 * d.Cin * CH) * sizeof(float);
   dim3 grid(d.W / 16, d.H / 16, d.B);
 #define T2I_THIN(CI)                                                                                              \
   case CI: {                                                                                                      \
