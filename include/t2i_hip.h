@@ -72,6 +72,7 @@ typedef struct t2i_conv_desc {
 enum { T2I_MATH_F32 = 0, T2I_MATH_BF16 = 1 };
 
 /* ---- library ------------------------------------------------------------------------------------------------ */
+#define T2I_ABI_VERSION 13        /* what t2i_version() returns and what the Python binding, which reads this header, expects */
 int t2i_version(void);            /* ABI version, currently 13 (v13: t2i_cosine_distance added, then t2i_bn_infer and t2i_bytescale_nearest (+ workspace query) — no existing signature changed; v12: t2i_pool_dropout, t2i_softmax_ce_head (+ workspace query), t2i_pooled_grad_scatter and t2i_rmsprop_tf added — no existing signature changed; v11: t2i_resample_bilinear, t2i_pool2d, t2i_channel_slice_copy, t2i_gram_accumulate and their workspace queries added — no existing signature changed; v10: t2i_nearest_images and t2i_nearest_images_workspace_bytes added — no existing signature changed; v9: t2i_conv_opts gained xform_valid_rows / xform_plane_rows, t2i_bn_train_fwd_grouped gained moving_groups, t2i_trunc_normal and t2i_zero_ranges added; v8: t2i_sigmoid_ce_head, t2i_bn_train_fwd_grouped, t2i_bn_bwd_grouped, t2i_bn_grouped_workspace_bytes added — no existing signature changed; v7: v7: t2i_conv2d_bwd_pair, t2i_row_scale_div, t2i_stat, t2i_filter_cache_assume added, t2i_adam_tf takes m == NULL at beta1 == 0 — no existing signature changed; v2: t2i_conv_desc.math; v3: caller-owned filter-cache arena,
                                    * t2i_tuning_set, t2i_kt_sgd; v4: t2i_filter_cache_refresh, bf16 operand images; v5: t2i_conv_opts
                                    * and explicit image arguments instead of thread-local one-shot hand-overs; v6: bf16 STORAGE —

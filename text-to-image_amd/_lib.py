@@ -1,7 +1,11 @@
-"""ctypes binding of libt2i_hip.so (C ABI: include/t2i_hip.h).  There is NO fallback: if the shared library is
-missing or a symbol is absent, importing this module raises — the product path never silently computes elsewhere."""
+"""ctypes binding of libt2i_hip.so, READ from the one declaration of its C ABI: include/t2i_hip.h.  At import this module parses
+the header's function prototypes, struct bodies, `#define`s and enums into SIGNATURES, the three Structure classes and CONSTANTS
+(tests/test_abi.py holds the reader to the header), so an entry point or a constant is written once, in C.  There is NO fallback:
+if the shared library is missing, a symbol is absent or a declaration cannot be read, importing this module raises — the product
+path never silently computes elsewhere."""
 import ctypes
 import os
+import re
 
 # The HIP runtime must come into the process through PyTorch first: libt2i_hip.so links against libamdhip64.so.7 by SONAME, and
 # PyTorch ships its own copy.  Loaded in the other order (`from t2i_amd import _lib` before anything imported torch) the loader binds
@@ -11,187 +15,122 @@ import torch  # noqa: F401,E402
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('T2I_HIP_LIB', os.path.join(_HERE, 'lib', 'libt2i_hip.so'))
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 't2i_hip.h')
+
+# ---- reading the header: the ONE rule set that turns a C type of include/t2i_hip.h into a ctypes type -----------------------------
+_SCALARS = {'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'uint64_t': ctypes.c_uint64, 'float': ctypes.c_float,
+            'double': ctypes.c_double, 'size_t': ctypes.c_size_t, 'long long': ctypes.c_longlong, 't2i_stream_t': ctypes.c_void_p}
+
+
+def _code(text):
+    """The header without comments and with runs of white space folded: declarations may span lines."""
+    return re.sub(r'[ \t]+', ' ', re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S))
+
+
+def _ctype(decl, where, pointers=(), named=True):
+    """ctypes type of one parameter, struct field (`named`: the last word is its name) or return type, written as in C."""
+    words = [w for w in decl.replace('*', ' * ').split() if w != 'const']
+    if not words or words[0] == '*' or re.search(r'[^\w\s*]', decl):
+        raise ValueError('%s: cannot read `%s`' % (where, decl.strip()))
+    if '*' in words:
+        base = ' '.join(words[:words.index('*')])
+        if words.count('*') > 1:
+            return ctypes.c_void_p
+        return ctypes.c_char_p if base == 'char' else dict(pointers).get(base, ctypes.c_void_p)
+    for base in (' '.join(words), ' '.join(words[:-1])) if named else (' '.join(words),):
+        if base in _SCALARS:
+            return _SCALARS[base]
+    raise ValueError('%s: no ctypes mapping for `%s`' % (where, decl.strip()))
+
+
+_INT_EXPR = r'(?=.*\d)(?:0[xX][0-9a-fA-F]+|\d+|<<|>>|[\s()+\-*|&~])+'     # integer literals, parentheses and integer operators: safe to eval
+_ENUM = r'\benum\b[^{;]*\{([^}]*)\}'
+_STRUCT = r'\btypedef struct \w*\s*\{([^}]*)\}\s*(\w+)\s*;'
+
+
+def header_constants(text):
+    """name -> int for every `#define T2I_* <integer expression>` and every enum member, in header order."""
+    found = []
+    for define, expr, members in re.findall(r'^ ?# ?define (T2I_\w+) ([^\n]+)$|' + _ENUM, _code(text), re.M):
+        if define and re.fullmatch(_INT_EXPR, expr):
+            found.append((define, int(eval(expr))))
+        nxt = 0
+        for item in filter(None, (i.strip() for i in members.split(','))):
+            name, eq, expr = (p.strip() for p in item.partition('='))
+            if eq and not re.fullmatch(_INT_EXPR, expr):
+                raise ValueError('include/t2i_hip.h: enum member %s = `%s` is not an integer expression' % (name, expr))
+            nxt = int(eval(expr)) if eq else nxt
+            found.append((name, nxt))
+            nxt += 1
+    return dict(found)
+
+
+def header_structs(text):
+    """typedef name -> ctypes `_fields_` list, from the header's `typedef struct { ... } name;` bodies, fields in declared order."""
+    out = {}
+    for body, name in re.findall(_STRUCT, _code(text)):
+        out[name] = fields = []
+        for decl in filter(None, (d.strip() for d in body.split(';'))):
+            first, *more = decl.split(',')         # `int32_t B, H, W, Cin`: the type is written with the first name
+            if more and '*' in decl:
+                raise ValueError('%s: one pointer field per declaration, not `%s`' % (name, decl))
+            kind = _ctype(first, name)
+            fields += [(n.strip(), kind) for n in [first.replace('*', ' ').split()[-1]] + more]
+    return out
+
+
+def header_signatures(text, pointers=()):
+    """name -> (restype, [argtypes]) for every function the header declares, in header order.  `pointers`: struct typedef name ->
+    what a single pointer to it maps to.  Whatever is left of the header besides the preprocessor lines, the `extern "C"` braces,
+    the typedefs and the enums must be a function declaration this module can read: anything else raises, naming it."""
+    code = re.sub(_STRUCT + '|' + _ENUM + r'\s*;|\btypedef void ?\* ?t2i_stream_t\s*;|extern "C" \{|^ ?#[^\n]*$|^ ?\}\s*$', ' ',
+                  _code(text), flags=re.M)
+    out = {}
+    for stmt in filter(None, (' '.join(s.split()) for s in code.split(';'))):
+        m = re.fullmatch(r'(.+?)\b(\w+) ?\(([^()]*)\)', stmt)
+        if not m:
+            raise ValueError('include/t2i_hip.h: cannot read the declaration `%s`' % stmt)
+        ret, name, args = m.groups()
+        out[name] = (None if ret.strip() == 'void' else _ctype(ret, name, pointers, named=False),
+                     [] if args.strip() in ('void', '') else [_ctype(a, '%s, argument %d' % (name, i + 1), pointers) for i, a in enumerate(args.split(','))])
+    return out
+
+
+with open(HEADER_PATH) as _f:
+    _HEADER = _f.read()
+CONSTANTS = header_constants(_HEADER)            # every T2I_* value of the header; kernels.py names its own from here too
+_FIELDS = header_structs(_HEADER)
 
 
 class ConvDesc(ctypes.Structure):
     """t2i_conv_desc"""
-    _fields_ = [(n, ctypes.c_int32) for n in
-                ('B', 'H', 'W', 'Cin', 'Ho', 'Wo', 'Cout', 'KH', 'KW', 'SH', 'SW', 'pad_t', 'pad_l', 'math')]
+    _fields_ = _FIELDS['t2i_conv_desc']
 
 
 class ConvOpts(ctypes.Structure):
-    """t2i_conv_opts: optional side inputs / outputs of one conv call (include/t2i_hip.h)"""
-    _fields_ = [('a_image', ctypes.c_void_p), ('b_image', ctypes.c_void_p), ('out_image', ctypes.c_void_p), ('xform', ctypes.c_void_p),
-                ('xform_bytes', ctypes.c_size_t), ('xform_mode', ctypes.c_int32), ('out_image_written', ctypes.c_int32),
-                ('xform_kept', ctypes.c_int32), ('in_dtype', ctypes.c_int32), ('out_dtype', ctypes.c_int32), ('xform_valid_rows', ctypes.c_int32), ('xform_plane_rows', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+    """t2i_conv_opts: optional side inputs / outputs of one conv call"""
+    _fields_ = _FIELDS['t2i_conv_opts']
 
 
 class ImageDesc(ctypes.Structure):
     """t2i_image_desc: one image of t2i_preprocess_images' ragged batch"""
-    _fields_ = [('offset', ctypes.c_int64)] + [(n, ctypes.c_int32) for n in
-                                               ('height', 'width', 'channels', 'y1', 'y2', 'x1', 'x2', 'reserved')]
+    _fields_ = _FIELDS['t2i_image_desc']
 
 
-XFORM_NONE, XFORM_KEEP, XFORM_HAVE = 0, 1, 2
-DT_F32, DT_BF16 = 0, 1           # t2i_dtype: element type of the activation tensors of a call
+def header_values(*names):
+    """(T2I_<name>, ...) as the header defines them: how this module and kernels.py give their public constants their values."""
+    return tuple(CONSTANTS['T2I_' + n] for n in names)
 
-_p = ctypes.c_void_p
-_i32, _i64, _f, _sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
-_dp = ctypes.POINTER(ConvDesc)
-_op = ctypes.POINTER(ConvOpts)
 
-# name -> (restype, argtypes); must list every symbol include/t2i_hip.h declares (tests/test_abi.py checks that)
-SIGNATURES = {
-    't2i_version': (ctypes.c_int, []),
-    't2i_last_error': (ctypes.c_char_p, []),
-    't2i_device_info': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.c_char_p, _sz]),
-    't2i_conv2d_workspace_bytes': (_sz, [_dp]),
-    't2i_conv2d_fwd': (ctypes.c_int, [_dp, _p, _p, _p, _p, ctypes.c_int, _f, _op, _p, _sz, _p]),
-    't2i_conv2d_bwd_data': (ctypes.c_int, [_dp, _p, _p, _p, _p, ctypes.c_int, _f, _op, _p, _sz, _p]),
-    't2i_conv2d_bwd_filter': (ctypes.c_int, [_dp, _p, _p, _p, ctypes.c_int, _op, _p, _sz, _p]),
-    't2i_col_reduce_workspace_bytes': (_sz, [_i64, _i32]),
-    't2i_col_reduce': (ctypes.c_int, [_p, _p, _p, _i64, _i32, _p, _p, ctypes.c_int, _p, _sz, _i32, _p]),
-    't2i_bn_stats': (ctypes.c_int, [_p, _i64, _i32, _p, _p, _p, _sz, _p]),
-    't2i_bn_stats_tiles': (ctypes.c_int, [_p, _p, _i32, _i32, _i64, _i32, _p, _p, _p]),
-    't2i_bn_train_fwd_stats': (ctypes.c_int, [_p, _p, _p, _i32, _i32, _i64, _i32, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p, _sz, _i32, _p]),
-    't2i_bn_bwd_fused_workspace_bytes': (_sz, [_i64, _i32]),
-    't2i_bn_bwd_fused': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, ctypes.c_int, _f, _p, _p, _p, _p, _p, ctypes.c_int, _p, _sz, _i32, _p]),
-    't2i_bn_finalize': (ctypes.c_int, [_p, _p, _i64, _i32, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p]),
-    't2i_bn_apply': (ctypes.c_int, [_p, _p, _p, _i64, _i32, ctypes.c_int, _f, _p, _p, _i32, _p]),
-    't2i_bn_infer': (ctypes.c_int, [_p, _p, _p, _p, _p, _f, _i64, _i32, ctypes.c_int, _f, _p, ctypes.c_int, _f, _p, _i32, _p]),
-    't2i_bn_bwd': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i32, _p, _p, _p, ctypes.c_int, _p, _sz, _p]),
-    't2i_act_fwd': (ctypes.c_int, [_p, _i64, ctypes.c_int, _f, _p, _p, _i32, _p]),
-    't2i_act_bwd': (ctypes.c_int, [_p, _p, _i64, ctypes.c_int, _f, _p, _p, _i32, _p]),
-    't2i_act_bwd_colsum': (ctypes.c_int, [_p, _p, _p, _p, _i64, _i32, ctypes.c_int, _f, _p, _p, _p, _p, ctypes.c_int, _p, _sz, _i32, _p]),
-    't2i_add_act': (ctypes.c_int, [_p, _p, _i64, ctypes.c_int, _f, _p, _p, _i32, _p]),
-    't2i_axpby': (ctypes.c_int, [_p, _f, _p, _f, _i64, _p, _i32, _p]),
-    't2i_interp': (ctypes.c_int, [_p, _p, _p, _i32, _i64, _p, _p]),
-    't2i_concat_tile_fwd': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _p, _i32, _p]),
-    't2i_concat_tile_bwd': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _p, _i32, _p]),
-    't2i_nchw_to_nhwc': (ctypes.c_int, [_p, _i32, _i32, _i32, _p, _i32, _p]),
-    't2i_nhwc_to_nchw': (ctypes.c_int, [_p, _i32, _i32, _i32, _p, _i32, _p]),
-    't2i_gp_slopes': (ctypes.c_int, [_p, _i32, _i64, _p, _i32, _p]),
-    't2i_row_scale': (ctypes.c_int, [_p, _p, _i32, _i64, _p, _i32, _p]),
-    't2i_row_scale_div': (ctypes.c_int, [_p, _p, _p, _i32, _i64, _p, _i32, _p]),
-    't2i_adam_tf': (ctypes.c_int, [_p, _p, _p, _p, _i64, _f, _p, _f, _f, _f, _f, _p]),
-    't2i_adam_tf_ema': (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _f, _p, _f, _f, _f, _f, _f, _p, _p]),
-    't2i_adam_tf_slots': (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _i32, _f, _p, _f, _f, _f, _f, _f, _p, _p]),
-    't2i_wgan_d_head': (ctypes.c_int, [_p, _p, _p, _p, _i32, _f, _p, _p, _p, _p, _p]),
-    't2i_bn_grouped_workspace_bytes': (_sz, [_i64, _i32, _i32]),
-    't2i_bn_train_fwd_grouped': (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, ctypes.c_int, _f, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _sz, _i32, _p]),
-    't2i_bn_bwd_grouped': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _i32, ctypes.c_int, _f, _p, _p, _p, _p, _p, ctypes.c_int, _p, _sz, _i32, _p]),
-    't2i_sigmoid_ce_head': (ctypes.c_int, [_p, _p, _p, _f, _f, _f, _f, _f, _f, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
-    't2i_ca_kl_fwd': (ctypes.c_int, [_p, _p, _p, _i64, _p, _p, _p]),
-    't2i_ca_kl_bwd': (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _p]),
-    't2i_lerp_dev': (ctypes.c_int, [_p, _p, _p, _i32, _i64, _p, _p]),
-    't2i_conv2d_algo': (ctypes.c_int, [_p, _i32]),
-    't2i_stat': (ctypes.c_longlong, [ctypes.c_char_p]),
-    't2i_conv2d_bwd_pair': (ctypes.c_int, [_dp, ctypes.c_int, _p, _p, _p, _op, _p, _p, _p, ctypes.c_int, _op, _p, _sz, _p, _sz, _p]),
-    't2i_filter_cache_attach': (ctypes.c_int, [_p, _sz]),
-    't2i_filter_cache_enable': (ctypes.c_int, [ctypes.c_int]),
-    't2i_tuning_set': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_double]),
-    't2i_kt_sgd': (ctypes.c_int, [_p, _p, _f, _f, _p]),
-    't2i_zero_ranges': (ctypes.c_int, [_p, _p, _i32, _p]),
-    't2i_trunc_normal': (ctypes.c_int, [_p, _i64, ctypes.c_uint64, ctypes.c_uint64, _f, _f, _f, _f, _p]),
-    't2i_filter_cache_invalidate': (None, [_p, ctypes.c_size_t]),
-    't2i_filter_cache_bytes': (ctypes.c_size_t, []),
-    't2i_filter_cache_refresh': (ctypes.c_int, [_p, _sz, _p]),
-    't2i_filter_cache_assume': (ctypes.c_int, [_p, _sz, _p]),
-    't2i_cast_bf16': (ctypes.c_int, [_p, _i64, _p, _p]),
-    't2i_cast_f32': (ctypes.c_int, [_p, _i64, _p, _p]),
-    't2i_conv2d_input_transform_bytes': (ctypes.c_size_t, [_dp]),
-    't2i_capture_id': (ctypes.c_uint64, [_p]),
-    't2i_conv2d_stats_bytes': (ctypes.c_size_t, [_dp]),
-    't2i_conv2d_fwd_stats': (ctypes.c_int, [_dp, _p, _p, _p, _p, ctypes.c_int, _f, _p, _sz, ctypes.POINTER(ctypes.c_int32),
-                                            ctypes.POINTER(ctypes.c_int32), _op, _p, _sz, _p]),
-    't2i_col_reduce_partials': (ctypes.c_int, [_p, _p, _i32, _i32, _p, _p, ctypes.c_int, _p]),
-    't2i_pool2_sum': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _f, _p, _p]),
-    't2i_upscale2': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _f, _p, _p]),
-    't2i_row_moments_workspace_bytes': (ctypes.c_size_t, [_i32]),
-    't2i_row_moments': (ctypes.c_int, [_p, _p, _i32, _i64, _p, _p, _p, _sz, _p]),
-    't2i_row_fma2': (ctypes.c_int, [_p, _p, _p, _p, _p, _i32, _i64, _p, _p]),
-    't2i_crop_flip_normalize': (ctypes.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p]),
-    't2i_gather_mean': (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _p, _i32, _i32, _p, _p]),
-    't2i_nearest_images_workspace_bytes': (_sz, [_i32, _i64]),
-    't2i_nearest_images': (ctypes.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _i32, _i32, _f, _f, _p, _p, _p, _sz, _p]),
-    't2i_resample_bilinear_workspace_bytes': (_sz, [_i32, _i32, _i32]),
-    't2i_resample_bilinear': (ctypes.c_int, [_p, _i32, _i64, _i32, _i32, _p, _i32, _i32, _i32, _p, _p, _i32, _p, _p, _i32, _p, _i32,
-                                             _p, _sz, _p]),
-    't2i_pool2d': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _p]),
-    't2i_channel_slice_copy': (ctypes.c_int, [_p, _i64, _i32, _p, _i32, _i32, _p]),
-    't2i_gram_accumulate_workspace_bytes': (_sz, [_i64, _i32]),
-    't2i_gram_accumulate': (ctypes.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _sz, _p]),
-    't2i_cosine_distance': (ctypes.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p]),
-    't2i_bytescale_nearest_workspace_bytes': (_sz, [_i64, _i32, _i32, _i32]),
-    't2i_bytescale_nearest': (ctypes.c_int, [_p, _i64, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),
-    't2i_pillow_tables': (ctypes.c_int, [_i32, _p, _i64, _i32, _p, _p, _i32, _p]),
-    't2i_preprocess_images_workspace_bytes': (_sz, [_i64, _i64, _i32, _i32]),
-    't2i_preprocess_images': (ctypes.c_int, [_p, _sz, _p, _i64, _i32, _p, _p, _sz, _p]),
-    't2i_pool_dropout':(ctypes.c_int, [_p, _i32, _i32, _i32, _f, ctypes.c_uint64, ctypes.c_uint64, _p, _p, _p, _p]),
-    't2i_softmax_ce_head_workspace_bytes': (_sz, [_i32, _i32]),
-    't2i_softmax_ce_head': (ctypes.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _sz, _p]),
-    't2i_pooled_grad_scatter': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _f, _i32, ctypes.POINTER(ctypes.c_void_p),
-                                               ctypes.POINTER(_i32), ctypes.POINTER(_i32), _p]),
-    't2i_rmsprop_tf': (ctypes.c_int, [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _p]),
-    't2i_pixel_norm_fwd': (ctypes.c_int, [_p, _i64, _i32, _f, ctypes.c_int, _f, _p, _p, _p]),
-    't2i_pixel_norm_bwd': (ctypes.c_int, [_p, _p, _p, _i64, _i32, ctypes.c_int, _f, _p, _p]),
-    't2i_pixel_norm_bwd2': (ctypes.c_int, [_p, _p, _p, _p, _i64, _i32, ctypes.c_int, _f, _p, _p, _p]),
-    't2i_layer_norm_bwd2_workspace_bytes': (_sz, [_i32]),
-    't2i_layer_norm_bwd2_sums': (ctypes.c_int, [_p, _p, _p, _p, _p, _i32, _i64, _i32, ctypes.c_int, _f, _p, _p, _sz, _p]),
-    't2i_layer_norm_bwd2_apply': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i32, _i64, _i32, ctypes.c_int, _f, _p, _p, _p, _p]),
-    't2i_minibatch_stddev_workspace_bytes': (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
-    't2i_minibatch_stddev_fwd': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _f, _p, _p, _sz, _p]),
-    't2i_minibatch_stddev_bwd': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _f, _p, _p]),
-    't2i_minibatch_stddev_bwd2': (ctypes.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _f, _p, _p, _p, _sz, _p]),
-    't2i_resize_nearest': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p]),
-    't2i_resize_nearest_adj': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p]),
-    't2i_pool_same_fwd': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p]),
-    't2i_pool_same_bwd': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p]),
-    't2i_pool_same_take': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p]),
-    't2i_gn_fwd': (ctypes.c_int, [_p, _i64, _f, ctypes.c_uint64, ctypes.c_uint64, _p, _p, _p]),
-    't2i_mul': (ctypes.c_int, [_p, _p, _i64, _p, _p]),
-    't2i_laplacian_pyramid_workspace_bytes': (_sz, [_i64, _i32, _i32, _i32, _i32]),
-    't2i_laplacian_pyramid': (ctypes.c_int, [_p, _i64, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),
-    't2i_swd_descriptors': (ctypes.c_int, [_p, _i64, _i32, _i32, _i32, _p, _i32, _p, _i64, _i64, _p]),
-    't2i_swd_channel_stats_workspace_bytes': (_sz, [_i64, _i32]),
-    't2i_swd_channel_stats': (ctypes.c_int, [_p, _i64, _i32, _p, _p, _p, _sz, _p]),
-    't2i_swd_project': (ctypes.c_int, [_p, _i64, _i32, _p, _p, _p, _i32, _p, _i64, _p]),
-    't2i_segmented_sort_chunk': (_i32, []),
-    't2i_segmented_sort_f32': (ctypes.c_int, [_p, _i32, _i64, _p]),
-    't2i_sorted_l1_mean_workspace_bytes': (_sz, [_i32, _i64]),
-    't2i_sorted_l1_mean': (ctypes.c_int, [_p, _p, _i32, _i64, _i64, _p, _p, _sz, _p]),
-    't2i_ssim_scale_workspace_bytes': (_sz, [_i64, _i32, _i32, _i32]),
-    't2i_ssim_scale': (ctypes.c_int, [_p, _p, _i64, _i32, _i32, _i32, _p, _i32, ctypes.c_double, ctypes.c_double, _p, _p, _p, _p, _p, _sz, _p]),
-    't2i_knn_dist2_workspace_bytes': (_sz, [_i64, _i64, _i32, _i32, _i32]),
-    't2i_knn_dist2': (ctypes.c_int, [_p, _i64, _p, _i64, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),
-    't2i_ball_counts_workspace_bytes': (_sz, [_i64, _i64, _i32, _i32]),
-    't2i_ball_counts': (ctypes.c_int, [_p, _i64, _p, _i64, _i32, _p, _i32, _p, _p, _p, _sz, _p]),
-    't2i_poly_mmd_sums_workspace_bytes': (_sz, [_i64, _i64, _i32, _i32, _i32]),
-    't2i_poly_mmd_sums': (ctypes.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _i32, _i32, _i32, ctypes.c_double, ctypes.c_double, _p, _p, _sz, _p]),
-    't2i_diff_augment_workspace_bytes': (_sz, [_i32, _i32, _i32, _i32, _i32]),
-    't2i_diff_augment_fwd': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),
-    't2i_diff_augment_adj': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),
-    't2i_diff_augment_draw': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _p]),
-    't2i_diffaug_observe': (ctypes.c_int, [_p, _p, _p, _i32, _i32, _f, _i32, _f, _p]),
-    't2i_spectral_workspace_bytes': (_sz, [_i64]),
-    't2i_spectral_grad': (ctypes.c_int, [_p, _p, _i64, _p, _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p, _sz, _p]),
-    't2i_spectral_normalize': (ctypes.c_int, [_p, _p, _i64, _p, _i32, _i32, _i32, _p, _i64, _p, _i64, _p, _i32, _i64, _p, _sz, _p]),
-    't2i_upfirdn2d_extent': (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
-    't2i_upfirdn2d': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p]),
-    't2i_upfirdn2d_axes': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p]),
-    't2i_adain_chunk_rows': (_i32, []),
-    't2i_adain_workspace_bytes': (_sz, [_i32, _i64, _i32]),
-    't2i_adain_stats': (ctypes.c_int, [_p, _p, _p, _i32, _i64, _i32, ctypes.c_int, _f, _f, _p, _p, _p, _sz, _p]),
-    't2i_adain_apply': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, ctypes.c_int, _f, _p, _p]),
-    't2i_adain_bwd_sums': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i64, _i32, ctypes.c_int, _f, _p, _p, _p, _sz, _p]),
-    't2i_adain_bwd_apply': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _i32, _i64, _i32, ctypes.c_int, _f, _p, _p, _p, _sz, _p]),
-}
+XFORM_NONE, XFORM_KEEP, XFORM_HAVE = header_values('XFORM_NONE', 'XFORM_KEEP', 'XFORM_HAVE')
+DT_F32, DT_BF16 = header_values('DT_F32', 'DT_BF16')      # t2i_dtype: element type of the activation tensors of a call
+SIGNATURES = header_signatures(_HEADER, {'t2i_conv_desc': ctypes.POINTER(ConvDesc), 't2i_conv_opts': ctypes.POINTER(ConvOpts)})
 
 if not os.path.exists(LIB_PATH):
     raise ImportError('libt2i_hip.so not found at %s — build it with text-to-image_amd/csrc/build.sh '
                       '(or `python -c "import __graft_entry__ as g; g.build()"`); there is no CPU fallback' % LIB_PATH)
 
-ABI_VERSION = 13         # include/t2i_hip.h T2I_ABI_VERSION: argument lists changed in v5, v6 and v7 — symbols alone do not tell
+ABI_VERSION = CONSTANTS['T2I_ABI_VERSION']       # argument lists changed in v5, v6 and v7 — symbols alone do not tell
 
 lib = ctypes.CDLL(LIB_PATH)
 try:

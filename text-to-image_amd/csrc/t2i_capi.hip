@@ -732,7 +732,7 @@ using namespace t2i;
 
 extern "C" {
 
-int t2i_version(void) { return 13; }
+int t2i_version(void) { return T2I_ABI_VERSION; }
 
 const char* t2i_last_error(void) { return g_err; }
 

@@ -13,9 +13,9 @@ import os
 import numpy as np
 import torch
 
-from ._lib import DT_BF16, DT_F32, XFORM_HAVE, XFORM_KEEP, ConvDesc, ConvOpts, ImageDesc, check, lib
+from ._lib import CONSTANTS, DT_BF16, DT_F32, XFORM_HAVE, XFORM_KEEP, ConvDesc, ConvOpts, ImageDesc, check, header_values, lib
 
-ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH = 0, 1, 2, 3
+ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH = header_values('ACT_NONE', 'ACT_LRELU', 'ACT_RELU', 'ACT_TANH')
 
 _DRY = [False]
 
@@ -128,7 +128,7 @@ _DESC_CACHE = {}
 
 # Arithmetic of the conv family (t2i_conv_desc.math): 'f32' = exact fp32 matrix pipe (default, BASELINE config 2);
 # 'bf16' = operands rounded to bf16 inside the kernel, bf16 MFMA with fp32 accumulation, fp32 tensors (config 3).
-MATH_F32, MATH_BF16 = 0, 1
+MATH_F32, MATH_BF16 = header_values('MATH_F32', 'MATH_BF16')
 _MATH = [MATH_F32]
 
 
@@ -722,7 +722,7 @@ def conv_bwd_filter(x, dy, d, ws_bytes, out=None, xform=None, xform_valid_rows=0
     return dw
 
 
-PAIR_FWD, PAIR_BWD_DATA = 0, 1
+PAIR_FWD, PAIR_BWD_DATA = header_values('PAIR_FWD', 'PAIR_BWD_DATA')
 
 
 def conv_bwd_pair(first, g, w, fx, fdy, d, ws_bytes, dw_out, out_dtype=None, accumulate=True):
@@ -1106,7 +1106,7 @@ def adam_tf_ema(w, g, m, v, ema, lr_t, beta1, beta2, eps=1e-8, grad_scale=1.0, e
               't2i_adam_tf_ema')
 
 
-ADAM_MAX_SLOTS = 2048      # T2I_ADAM_MAX_SLOTS (include/t2i_hip.h)
+ADAM_MAX_SLOTS = CONSTANTS['T2I_ADAM_MAX_SLOTS']
 
 
 def adam_tf_slots(w, g, m, v, slot_end, slot_mult, lr_t, beta1, beta2, eps=1e-8, grad_scale=1.0, ema=None, ema_decay=0.999, lr_t_dev=None,
@@ -1129,7 +1129,8 @@ def adam_tf_slots(w, g, m, v, slot_end, slot_mult, lr_t, beta1, beta2, eps=1e-8,
 
 
 # ---- spectral normalisation of the matrices of an arena (csrc/t2i_spectral.hip) -----------------------------
-SPECTRAL_MAX_SLOTS, SPECTRAL_MAX_ITEMS, SPECTRAL_MAX_ITERATIONS, SPECTRAL_COLS = 2048, 1 << 22, 64, 7    # T2I_SPECTRAL_* (include/t2i_hip.h)
+SPECTRAL_MAX_SLOTS, SPECTRAL_MAX_ITEMS, SPECTRAL_MAX_ITERATIONS, SPECTRAL_COLS = header_values(
+    'SPECTRAL_MAX_SLOTS', 'SPECTRAL_MAX_ITEMS', 'SPECTRAL_MAX_ITERATIONS', 'SPECTRAL_COLS')
 
 
 def spectral_items(R, C):
@@ -1409,7 +1410,7 @@ def preprocess_images(packed, descs, size):
     return y
 
 
-POOL_MAX, POOL_AVG = 0, 1
+POOL_MAX, POOL_AVG = header_values('POOL_MAX', 'POOL_AVG')
 
 
 def pool_out_size(n, k, s, padding):
@@ -1616,7 +1617,7 @@ def ca_kl_bwd(mean, log_sigma, eps, dcode, dkl):
     return dmean, dls
 
 
-ALGO_NAMES = ('implicit_gemm', 'winograd_f2x2_3x3', 'winograd_f2x2_2x2', 'direct_small', 'implicit_gemm_bf16_operands')
+ALGO_NAMES = tuple(k[len('T2I_ALGO_'):].lower() for k in sorted((k for k in CONSTANTS if k.startswith('T2I_ALGO_')), key=CONSTANTS.get))
 ALGO_MAC_RATIO = (1.0, 1.0 / 2.25, 9.0 / 16.0, 1.0, 1.0)       # executed / direct-convolution multiply-adds
 
 
@@ -1815,7 +1816,7 @@ def pooled_grad_scatter(g, mask, keep, outs, c0s, HW):
     return outs
 
 
-MAX_SCATTER_BRANCHES = 8          # T2I_MAX_SCATTER_BRANCHES
+MAX_SCATTER_BRANCHES = CONSTANTS['T2I_MAX_SCATTER_BRANCHES']
 
 
 def rmsprop_tf(w, g, ms, mom, lr, rho=0.9, momentum=0.0, eps=1e-10):
@@ -1829,7 +1830,6 @@ def rmsprop_tf(w, g, ms, mom, lr, rho=0.9, momentum=0.0, eps=1e-10):
 
 
 # ---- the rest of the operator surface (reference utils/ops.py:94-116,145-148; csrc/t2i_ops.hip) --------------------------
-POOL_MAX, POOL_AVG = 0, 1         # T2I_POOL_MAX / T2I_POOL_AVG
 
 
 def pixel_norm_fwd(x, eps, act=ACT_NONE, alpha=0.2):
@@ -1958,7 +1958,7 @@ def minibatch_stddev_bwd2(v, x, gs, G, F, eps=1e-8):
     return dxx, dgs
 
 
-DIFFAUG_COLOR, DIFFAUG_TRANSLATION, DIFFAUG_CUTOUT = 1, 2, 4            # T2I_DIFFAUG_*: the policy mask of diff_augment_fwd / _adj
+DIFFAUG_COLOR, DIFFAUG_TRANSLATION, DIFFAUG_CUTOUT = header_values('DIFFAUG_COLOR', 'DIFFAUG_TRANSLATION', 'DIFFAUG_CUTOUT')  # the policy mask of diff_augment_fwd / _adj
 
 
 def _diffaug_args(x, P, policy):
@@ -1997,7 +1997,7 @@ def diff_augment_adj(g, P, policy):
     return dx
 
 
-ADA_LOGIT, ADA_MIDPOINT = 0, 1                                          # T2I_ADA_*: the threshold of diffaug_observe's statistic
+ADA_LOGIT, ADA_MIDPOINT = header_values('ADA_LOGIT', 'ADA_MIDPOINT')      # the threshold of diffaug_observe's statistic
 
 
 def _diffaug_state(state, op):
@@ -2128,7 +2128,8 @@ def mul(a, b):
 
 
 # anti-aliased resampling (csrc/t2i_resample.hip)
-UPFIRDN_TILE, UPFIRDN_MAX_TAPS, UPFIRDN_MAX_PAD = 8, 8, 32768          # T2I_UPFIRDN_TILE / _MAX_TAPS (include/t2i_hip.h): outputs per tile and axis
+UPFIRDN_TILE, UPFIRDN_MAX_TAPS = header_values('UPFIRDN_TILE', 'UPFIRDN_MAX_TAPS')      # outputs per tile and axis
+UPFIRDN_MAX_PAD = 32768
 
 
 def upfirdn2d_extent(H, u, d, p0, p1, n):
@@ -2383,7 +2384,7 @@ def sorted_l1_mean(a, b, rows):
 
 
 # ---- multi-scale structural similarity (csrc/t2i_msssim.hip; evaluation/msssim.py is the caller) ------------------------------
-SSIM_MAX_WINDOW = 11                                    # include/t2i_hip.h T2I_SSIM_MAX_WINDOW
+SSIM_MAX_WINDOW = CONSTANTS['T2I_SSIM_MAX_WINDOW']
 
 
 def msssim_window(h, w, filter_size=11, sigma=1.5):
@@ -2430,7 +2431,7 @@ def ssim_scale(a, b, window, c1, c2, downsample=True):
 
 
 # ---- k-nearest-neighbour distances and ball counts in fp64 (csrc/t2i_knn.hip; evaluation/prdc.py is the caller) ----------------
-KNN_MAX_K = 8                                           # include/t2i_hip.h T2I_KNN_MAX_K
+KNN_MAX_K = CONSTANTS['T2I_KNN_MAX_K']
 KNN_MAX_SEGMENTS = 65536
 
 
