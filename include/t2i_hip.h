@@ -993,6 +993,50 @@ int t2i_adain_bwd_apply(const float* g, const float* x, const float* noise, cons
                         const float* ys, int32_t style_stride, const float* dys, const float* dyb, int32_t B, int64_t R, int32_t C,
                         int act, float alpha, float* dx, float* dstrength, void* ws, size_t ws_bytes, t2i_stream_t stream);
 
+/* ---- weight-demodulated convolutions (Karras et al., CVPR 2020): what surrounds the convolution.  csrc/t2i_modconv.hip, DESIGN.md section
+ * 4.45.  Added within ABI v13: no existing argument list changed. -------------------------------------------------------------------------
+ * With s [B,Cin] (rows style_stride >= Cin floats apart) and W [T,Cin,Cout] (T = KH KW taps of an HWIO filter), the modulated layer
+ *   y[b] = conv(x[b], W s[b,:] d[b,:]),  d[b,o] = rsqrt(sum_{t,i} (W[t,i,o] s[b,i])^2 + eps)
+ * equals d[b,o] conv(x[b] s[b,:], W)[.,.,o] exactly, and d = rsqrt(sum_i s[b,i]^2 q[i,o] + eps) with q[i,o] = sum_t W[t,i,o]^2.  The
+ * convolution is t2i_conv2d_fwd as it is; these calls are the rest.  fp32 only.  R = H W rows per sample.
+ * t2i_demod_coef (2 launches): q [Cin,Cout] (t ascending) and d [B,Cout] (input channels in 4 fixed lanes, merged in ascending order).
+ * t2i_demod_coef_bwd (a launch per wanted output): for the cotangent gd of d, with e = -d^3 gd / 2:  ds [B,Cin] (dense; or NULL; needs q)
+ *         = 2 s sum_o q[i,o] e[b,o];  dW [T,Cin,Cout] (or NULL; needs W) = 2 W[t,i,o] sum_b s[b,i]^2 e[b,o], b ascending;
+ *         accumulate != 0 adds that to what dW holds (a gradient arena slot that the convolution's filter gradient shares).
+ * t2i_modulate (1 launch): xs[b,r,c] = x[b,r,c] s[b,c]; with the cotangent of xs in place of x it is its own adjoint for dx.
+ * t2i_modulate_bwd_scale (2 launches): ds [B,C] = sum_r g[b,r,c] x[b,r,c]: partials per chunk of T2I_MODCONV_CHUNK_ROWS rows in the
+ *         workspace, then their sum in a fixed order.
+ * t2i_demod_act (1 launch): out = act(p), p = fmaf(strength[c], noise[b,r], fmaf(d[b,c], c[b,r,c], bias[c])).  d NULL: coefficient 1; bias
+ *         NULL: 0; noise [B,R] and strength [C] both or neither (without them the outer fmaf is not taken).  act: T2I_ACT_NONE, T2I_ACT_RELU
+ *         or T2I_ACT_LRELU with alpha >= 0.
+ * t2i_demod_act_bwd (1 launch, 2 with any of the sums): recomputes p by the same sequence; gp = act'(p) g; dc (or NULL) = gp d;
+ *         dd [B,C] (or NULL; needs d) = sum_r gp c;  dbias [C] (or NULL) = sum_{b,r} gp;  dstrength [C] (or NULL; needs noise) = sum_{b,r} gp
+ *         noise.  Per-item partials in the workspace (read only when a sum is wanted), summed in a fixed order.  noise gets no gradient.
+ * A 16-byte form when C % 4 == 0 and the [B,R,C] tensors of the call are 16-byte aligned, a scalar form otherwise.  A grid of at most 65535
+ * workgroups walks the items with a stride.  No atomics; every split depends on the shape without B: a sample's d, xs, out, dc, dd and ds
+ * do not depend on its batch, and calls repeat bit for bit.  Graph-capturable: no allocation, no synchronisation, nothing read back.
+ * Refused with T2I_ERR_INVALID before any launch: a NULL pointer (the optional ones above apart; _act_bwd with no output at all); a size < 1;
+ * 2^31 elements or more; style_stride below the channel count; eps negative or not finite; another activation or a negative slope; noise
+ * without strength or the reverse; dstrength without noise; dd without d; an output overlapping an input or another output.  A workspace
+ * that is NULL, not 16-byte aligned or smaller than the call's *_workspace_bytes (0 for a refused shape) returns T2I_ERR_WORKSPACE.
+ * t2i_demod_coef, its backward, t2i_modulate and t2i_demod_act need no workspace and take none. */
+#define T2I_MODCONV_CHUNK_ROWS 64
+int32_t t2i_modconv_chunk_rows(void);
+int t2i_demod_coef(const float* W, const float* s, int32_t style_stride, int32_t T, int32_t Cin, int32_t Cout, int32_t B, float eps, float* q,
+                   float* d, t2i_stream_t stream);
+int t2i_demod_coef_bwd(const float* gd, const float* d, const float* s, int32_t style_stride, const float* W, const float* q, int32_t T,
+                       int32_t Cin, int32_t Cout, int32_t B, float* ds, float* dW, int32_t accumulate, t2i_stream_t stream);
+int t2i_modulate(const float* x, const float* s, int32_t style_stride, int32_t B, int64_t R, int32_t C, float* xs, t2i_stream_t stream);
+size_t t2i_modulate_bwd_scale_workspace_bytes(int32_t B, int64_t R, int32_t C);
+int t2i_modulate_bwd_scale(const float* g, const float* x, int32_t B, int64_t R, int32_t C, float* ds, void* ws, size_t ws_bytes,
+                           t2i_stream_t stream);
+int t2i_demod_act(const float* c, const float* d, const float* bias, const float* noise, const float* strength, int32_t B, int64_t R, int32_t C,
+                  int act, float alpha, float* out, t2i_stream_t stream);
+size_t t2i_demod_act_bwd_workspace_bytes(int32_t B, int64_t R, int32_t C);
+int t2i_demod_act_bwd(const float* g, const float* c, const float* d, const float* bias, const float* noise, const float* strength, int32_t B,
+                      int64_t R, int32_t C, int act, float alpha, float* dc, float* dd, float* dbias, float* dstrength, void* ws,
+                      size_t ws_bytes, t2i_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

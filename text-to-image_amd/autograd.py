@@ -1113,3 +1113,113 @@ class AdaINBwdFn(Function):
         raise NotImplementedError('adain: a second differentiation is not implemented - the layer belongs to the generator, which no '
                                   'gradient penalty differentiates (the penalty is a gradient of the critic with respect to images); '
                                   'a critic that needs a twice-differentiable norm has layer_norm and pixel_norm')
+
+
+_MODCONV_SECOND = ('%s: a second differentiation is not implemented - the layer belongs to the generator, which no '
+                   'gradient penalty differentiates (the penalty is a gradient of the critic with respect to images); '
+                   'a critic that needs a twice-differentiable norm has layer_norm and pixel_norm')
+
+
+class _FirstOrder(Function):
+    """The backward piece of a weight-demodulated convolution's functions: runs `fn(*args)` (tensors and plain values), not differentiable."""
+
+    @staticmethod
+    def forward(ctx, op, fn, *args):
+        ctx.op = op
+        ctx.set_materialize_grads(False)
+        return fn(*args)
+
+    @staticmethod
+    def backward(ctx, *v):
+        raise NotImplementedError(_MODCONV_SECOND % ctx.op)
+
+
+class ModulateFn(Function):
+    """xs[b,h,w,c] = x[b,h,w,c] s[b,c]: the per-sample channel scale in front of a weight-demodulated convolution (Karras et al. 2020; not
+    in the reference).  Saves x and s.  dx is the same launch on the cotangent; ds [B,C] = sum over (h, w) of g x,
+    two launches.  First order, like AdaINFn."""
+
+    @staticmethod
+    def forward(ctx, x, s):
+        x = _c(x)
+        ctx.save_for_backward(x, s)
+        ctx.set_materialize_grads(False)
+        return K.modulate(x, s)
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None
+        x, s = ctx.saved_tensors
+        need = ctx.needs_input_grad
+
+        def piece(g, x, s):
+            g = _c(g)
+            return (K.modulate(g, s) if need[0] else None), (K.modulate_bwd_scale(g, x) if need[1] else None)
+        return _FirstOrder.apply('modulate', piece, g, x, s)
+
+
+class DemodCoefFn(Function):
+    """d[b,o] = rsqrt(sum_i s[b,i]^2 q[i,o] + eps), q[i,o] = the sum over the taps of w[.,.,i,o]^2: the demodulation coefficients of a
+    modulated filter w [kh,kw,Cin,Cout] under the style scales s [B,Cin].  Two launches; saves w, s, q and d.
+    Backward: ds (one launch) and dw (one launch; not under input_grads_only).  In the final backward dw goes straight into the
+    weight's gradient-arena slot, which the convolution's filter gradient shares: added, or stored when it is the slot's first
+    contribution of the step, on the filter-gradient stream when there is one (the slot's contributions keep their order)."""
+
+    @staticmethod
+    def forward(ctx, w, s, eps):
+        d, q = K.demod_coef(w, s, eps)
+        ctx.save_for_backward(w, s, q, d)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(q)
+        return d, q
+
+    @staticmethod
+    def backward(ctx, gd, _gq):
+        if gd is None:
+            return None, None, None
+        w, s, q, d = ctx.saved_tensors
+        want_w = ctx.needs_input_grad[0] and not _INPUTS_ONLY[0]
+        want_s = ctx.needs_input_grad[1]
+        sink = _sink_of(w) if want_w else None
+
+        def piece(gd, d, w, s, q):
+            gd = _c(gd)
+            if sink is None:
+                return K.demod_coef_bwd(gd, d, w, s, q, want_s, want_w)
+            ds = K.demod_coef_bwd(gd, d, w, s, q, want_s, False)[0]
+            acc = sink_accumulate(w.data_ptr())
+            sunk_launch(lambda: K.demod_coef_bwd(gd, d, w, s, q, False, True, out=sink, accumulate=acc), (gd, d, w, s, q))
+            _notify(w)
+            return ds, None
+        ds, dw = _FirstOrder.apply('modulated_conv2d', piece, gd, d, w, s, q)
+        return dw, ds, None
+
+
+class DemodActFn(Function):
+    """out = act(d[b,o] c + bias[o] + strength[o] noise[b,h,w]): the epilogue behind a weight-demodulated convolution's plain convolution
+    c; d, bias and the noise pair are each optional.  One launch.  Saves c, d, bias, noise and strength: the
+    backward recomputes the pre-activation, no plane of it or of a mask is kept.  Backward: dc and, unless under input_grads_only, dbias
+    and dstrength, with dd in one or two launches; noise gets no gradient.  First order, like AdaINFn."""
+
+    @staticmethod
+    def forward(ctx, c, d, bias, noise, strength, act, alpha):
+        c = _c(c)
+        ctx.save_for_backward(c, d, bias, noise, strength)
+        ctx.act, ctx.alpha = act, alpha
+        ctx.set_materialize_grads(False)
+        return K.demod_act(c, d, bias, noise, strength, act, alpha)
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return (None,) * 7
+        c, d, bias, noise, strength = ctx.saved_tensors
+        need, params = ctx.needs_input_grad, not _INPUTS_ONLY[0]
+        want = (d is not None and need[1], bias is not None and need[2] and params, strength is not None and need[4] and params)
+        act, alpha = ctx.act, ctx.alpha
+
+        def piece(g, c, d, bias, noise, strength):
+            return K.demod_act_bwd(_c(g), c, d, bias, noise, strength, act, alpha, *want)
+        dc, dd, dbias, dstrength = _FirstOrder.apply('modulated_conv2d', piece, g, c, d, bias, noise, strength)
+        return dc, dd, dbias, None, dstrength, None, None

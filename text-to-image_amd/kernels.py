@@ -2258,6 +2258,126 @@ def adain_bwd(g, x, ys, mean, rstd, noise=None, strength=None, act=ACT_NONE, alp
     return dx, dstrength, dys, dyb
 
 
+# ---- weight-demodulated convolutions: what surrounds the convolution (csrc/t2i_modconv.hip) -------------------------
+MODCONV_CHUNK_ROWS = int(lib.t2i_modconv_chunk_rows())  # rows of a sample per work item (include/t2i_hip.h T2I_MODCONV_CHUNK_ROWS)
+
+
+def _scale_rows(op, t, name, B, C):
+    """s: float32 [B,C] with unit stride along C and rows any stride >= C apart (a slice of a wider dense output needs no copy)."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (B, C) or t.stride(1) != 1 or (B > 1 and t.stride(0) < C):
+        raise ValueError('%s: %s must be a float32 [%d, %d] with unit stride along the channels, got %s' % (
+            op, name, B, C, '%s %s strides %s' % (t.dtype, tuple(t.shape), t.stride()) if isinstance(t, torch.Tensor) else type(t).__name__))
+    return t.stride(0) if B > 1 else C
+
+
+def _brc(op, x, name='x'):
+    _chk(x, name, f32=True)
+    if x.dim() != 4 or min(x.shape) < 1 or x.numel() >= 1 << 31:
+        raise ValueError('%s: %s must be [B,H,W,C] with every size at least 1 and fewer than 2^31 elements, got %s' % (op, name, tuple(x.shape)))
+    B, H, W, C = x.shape
+    return B, H * W, C
+
+
+def _filter_taps(op, w, s):
+    _chk(w, 'w', f32=True)
+    if w.dim() != 4 or min(w.shape) < 1 or w.numel() >= 1 << 31:
+        raise ValueError('%s: w must be an HWIO filter [kh,kw,Cin,Cout] with every size at least 1, got %s' % (op, tuple(w.shape)))
+    kh, kw, Cin, Cout = w.shape
+    if not isinstance(s, torch.Tensor) or s.dim() != 2 or s.shape[0] < 1:
+        raise ValueError('%s: s must be [B, %d], got %s' % (op, Cin, tuple(s.shape) if isinstance(s, torch.Tensor) else type(s).__name__))
+    B = s.shape[0]
+    return kh * kw, Cin, Cout, B, _scale_rows(op, s, 's', B, Cin)
+
+
+def demod_coef(w, s, eps=1e-8):
+    """w [kh,kw,Cin,Cout], s [B,Cin] -> (d [B,Cout] = rsqrt(sum_i s^2 q + eps), q [Cin,Cout] = sum over the taps of w^2).  Two launches."""
+    T, Cin, Cout, B, sstride = _filter_taps('demod_coef', w, s)
+    q = torch.empty((Cin, Cout), dtype=torch.float32, device=w.device)
+    d = torch.empty((B, Cout), dtype=torch.float32, device=w.device)
+    if _live(w):
+        check(lib.t2i_demod_coef(_ptr(w), _ptr(s), sstride, T, Cin, Cout, B, float(eps), _ptr(q), _ptr(d), _stream()), 't2i_demod_coef')
+    return d, q
+
+
+def demod_coef_bwd(gd, d, w, s, q, want_s=True, want_w=True, out=None, accumulate=False):
+    """The backward of demod_coef for the cotangent gd of d -> (ds [B,Cin] or None, dw like w or None): a launch per wanted output.
+    out: where dw goes (a flat float32 tensor of w's size: a gradient arena slot); with accumulate it is added to what out holds."""
+    T, Cin, Cout, B, sstride = _filter_taps('demod_coef_bwd', w, s)
+    _chk(gd, 'gd', f32=True); _chk(d, 'd', f32=True); _chk(q, 'q', f32=True)
+    assert tuple(gd.shape) == (B, Cout) and tuple(d.shape) == (B, Cout) and tuple(q.shape) == (Cin, Cout)
+    ds = torch.empty((B, Cin), dtype=torch.float32, device=w.device) if want_s else None
+    dw = (torch.empty_like(w) if out is None else out) if want_w else None
+    if dw is not None and (dw.dtype != torch.float32 or dw.numel() != w.numel() or not dw.is_contiguous()):
+        raise ValueError('demod_coef_bwd: out must be a contiguous float32 tensor of %d elements' % w.numel())
+    if _live(w) and (want_s or want_w):
+        check(lib.t2i_demod_coef_bwd(_ptr(gd), _ptr(d), _ptr(s), sstride, _ptr(w), _ptr(q), T, Cin, Cout, B, _ptr(ds), _ptr(dw),
+                                     1 if (accumulate and out is not None) else 0, _stream()), 't2i_demod_coef_bwd')
+    return ds, dw
+
+
+def modulate(x, s):
+    """x [B,H,W,C] * s [B,C] (rows any stride >= C apart) per sample and channel.  One launch; with a cotangent in place of x, the adjoint."""
+    B, R, C = _brc('modulate', x)
+    sstride = _scale_rows('modulate', s, 's', B, C)
+    xs = torch.empty_like(x)
+    if _live(x):
+        check(lib.t2i_modulate(_ptr(x), _ptr(s), sstride, B, R, C, _ptr(xs), _stream()), 't2i_modulate')
+    return xs
+
+
+def modulate_bwd_scale(g, x):
+    """ds [B,C] = the sum over (h, w) of g * x.  Two launches: per-chunk partials, their fixed-order sum."""
+    B, R, C = _brc('modulate_bwd_scale', x)
+    _chk(g, 'g', f32=True)
+    assert g.shape == x.shape
+    ds = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    if _live(x):
+        wsp, wsn = _ws_args(x, int(lib.t2i_modulate_bwd_scale_workspace_bytes(B, R, C)))
+        check(lib.t2i_modulate_bwd_scale(_ptr(g), _ptr(x), B, R, C, _ptr(ds), wsp, wsn, _stream()), 't2i_modulate_bwd_scale')
+    return ds
+
+
+def _demod_act_args(op, c, d, bias, noise, strength):
+    B, R, C = _brc(op, c, 'c')
+    H, W = c.shape[1], c.shape[2]
+    if (noise is None) != (strength is None):
+        raise ValueError('%s: noise and strength come together or not at all' % op)
+    for name, t, shape in (('d', d, (B, C)), ('bias', bias, (C,)), ('noise', noise, (B, H, W)), ('strength', strength, (C,))):
+        if t is not None:
+            _chk(t, name, f32=True)
+            if tuple(t.shape) != shape:
+                raise ValueError('%s: %s must be %s, got %s' % (op, name, list(shape), tuple(t.shape)))
+    return B, R, C
+
+
+def demod_act(c, d=None, bias=None, noise=None, strength=None, act=ACT_NONE, alpha=0.2):
+    """act(d[b,o] c + bias[o] + strength[o] noise[b,h,w]) for c [B,H,W,C]; d, bias and the noise pair are each optional.  One launch."""
+    B, R, C = _demod_act_args('demod_act', c, d, bias, noise, strength)
+    out = torch.empty_like(c)
+    if _live(c):
+        check(lib.t2i_demod_act(_ptr(c), _ptr(d), _ptr(bias), _ptr(noise), _ptr(strength), B, R, C, act, alpha, _ptr(out), _stream()), 't2i_demod_act')
+    return out
+
+
+def demod_act_bwd(g, c, d=None, bias=None, noise=None, strength=None, act=ACT_NONE, alpha=0.2, want_d=True, want_bias=True, want_strength=True):
+    """The backward of demod_act for the cotangent g -> (dc, dd [B,C] or None, dbias [C] or None, dstrength [C] or None); the pre-activation is
+    recomputed.  One launch, two with any of the three sums."""
+    B, R, C = _demod_act_args('demod_act_bwd', c, d, bias, noise, strength)
+    _chk(g, 'g', f32=True)
+    assert g.shape == c.shape
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=c.device)
+    dc = torch.empty_like(c)
+    dd = new(B, C) if (d is not None and want_d) else None
+    dbias = new(C) if (bias is not None and want_bias) else None
+    dstrength = new(C) if (noise is not None and want_strength) else None
+    if _live(c):
+        sums = dd is not None or dbias is not None or dstrength is not None
+        wsp, wsn = _ws_args(c, int(lib.t2i_demod_act_bwd_workspace_bytes(B, R, C))) if sums else (None, 0)
+        check(lib.t2i_demod_act_bwd(_ptr(g), _ptr(c), _ptr(d), _ptr(bias), _ptr(noise), _ptr(strength), B, R, C, act, alpha, _ptr(dc), _ptr(dd),
+                                    _ptr(dbias), _ptr(dstrength), wsp, wsn, _stream()), 't2i_demod_act_bwd')
+    return dc, dd, dbias, dstrength
+
+
 # ---- sliced Wasserstein distance (csrc/t2i_swd.hip; evaluation/swd.py is the caller) -----------------------------------------
 def _f32_nd(t, name, dim):
     if t.dtype != torch.float32 or t.dim() != dim or not t.is_contiguous():

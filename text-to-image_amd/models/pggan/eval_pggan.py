@@ -2,7 +2,7 @@
 
     python text-to-image_amd/models/pggan/eval_pggan.py --cfg models/pggan/cfg/flowers.yml --eval is|fid|swd|msssim|prdc|mmd [--stage 7] [--batch 64]
                                                         [--msssim-pairs random|caption] [--prdc-k K] [--mmd-subsets S] [--mmd-subset-size M]
-                                                        [--style-dim D [--mapping-layers N] [--no-style-noise] [--truncation-psi PSI]]
+                                                        [--style-dim D [--mapping-layers N] [--no-style-noise] [--modulated-conv] [--truncation-psi PSI]]
 
 The generator's variables (`g_net`) are restored from CHECKPOINT_DIR/stage%d/; a failed load raises with the reference's
 message.  The dataset is `TextDataset(DATASET_DIR, MODEL.SIZES[stage - 1])` (256 at stage 7, as the reference reads).  Per batch
@@ -70,7 +70,7 @@ def stage_model(cfg, stage, batch_size, dataset, device, **kw):
 def restore_generator(m, ema=False):
     """ema=True: the moving average of the weights that `train_pggan.py --g-ema` keeps in the checkpoint, as the weights.
     The checkpoint's generator must be the model's, or its weights would be sampled through another function: a checkpoint built with
-    another --style-dim, --mapping-layers or --no-style-noise (`train_pggan.py --style-dim`), or trained with other resampling taps
+    another --style-dim, --mapping-layers, --no-style-noise or --modulated-conv (`train_pggan.py --style-dim`), or trained with other resampling taps
     (`g_net/resample_filter`, written by `train_pggan.py --resample-filter`; the key present in a model without taps and the taps given
     for a checkpoint without the key included), raises RuntimeError naming both sides, before any variable is read."""
     arch = options.checkpoint_architecture(m.check_dir_read)
@@ -81,6 +81,10 @@ def restore_generator(m, ema=False):
             raise RuntimeError('the checkpoint in %s holds %s, but this model was built with %s: pass the same --style-dim / --mapping-layers / '
                                '--no-style-noise (style_dim=, mapping_layers=, style_noise=) the trainer was given' % (
                                    m.check_dir_read, options.describe_style(ckpt_style), options.describe_style(model_style)))
+        if options.modulated_of_names(arch[0]) != m.modulated_conv:
+            raise RuntimeError('the checkpoint in %s holds a generator with %s, but this model was built with %s: pass --modulated-conv '
+                               '(modulated_conv=True) exactly when the trainer was given it' % (
+                                   m.check_dir_read, options.describe_modulated(not m.modulated_conv), options.describe_modulated(m.modulated_conv)))
         if not options.same_taps(arch[1], m.resample_taps):
             raise RuntimeError('the checkpoint in %s was trained with %s, but this model resamples with %s: pass the same --resample-filter '
                                '(resample_filter=) the trainer was given' % (

@@ -43,7 +43,7 @@ def normalised_taps(resample_filter, name='resample_filter'):
 
 def validated(batch_size, critic_norm=None, critic_mbstd=None, g_ema=None, equalized_lr=False, adam_lr=None, diffaug=None, diffaug_p=None,
               diffaug_adapt=False, diffaug_sampler=None, critic_sn=False, resample_filter=None, style_dim=None, mapping_layers=4,
-              style_noise=True, truncation_psi=None, label=str):
+              style_noise=True, truncation_psi=None, modulated_conv=False, label=str):
     """The optional keywords of PGGAN, checked -> {attribute: value} as the constructor keeps them (numbers cast to float, the taps also
     normalised, the group of critic_mbstd picked); a bad value is a ValueError that names the keyword through `label` (the identity; an
     entry point passes `flag`, and the same sentence speaks of `--diffaug-p`)."""
@@ -53,7 +53,11 @@ def validated(batch_size, critic_norm=None, critic_mbstd=None, g_ema=None, equal
     # generator becomes conv -> utils.ops.style_block (per-pixel noise unless style_noise=False, relu, instance norm, an affine map of w:
     # csrc/t2i_style.hip).  `feed['style_noise_{d,g}_<k>']` carry the noise images (drawn when missing); truncation_psi makes the sampler use
     # w_avg + psi (w - w_avg), training never truncates; the readers refuse a checkpoint built otherwise.  Style mixing, a learned constant
-    # input, bf16 tensors and modulated convolutions are out of scope.
+    # input and bf16 tensors are out of scope.
+    # modulated_conv=True (needs style_dim; Karras et al. 2020): every such conv -> style block pair becomes one
+    # utils.ops.modulated_conv2d instead: the style scales the convolution's input channels, the filter is demodulated per sample, and bias,
+    # noise and relu follow in one epilogue (csrc/t2i_modconv.hip); no instance norm.  Variables `ModConv[_k]/...` in place of `Conv[_k]/...`
+    # and `StyleMod[_k]/...`; the readers refuse a checkpoint of the other kind.
     if style_dim is not None and not _count(style_dim):
         raise ValueError('%s must be None (the reference\'s generator) or an integer >= 1 (the width of the style vector w), got %r' % (L('style_dim'), style_dim))
     if not _count(mapping_layers):
@@ -64,6 +68,10 @@ def validated(batch_size, critic_norm=None, critic_mbstd=None, g_ema=None, equal
         raise ValueError('%s must be None or a finite number (the sampler uses w_avg + psi (w - w_avg)), got %r' % (L('truncation_psi'), truncation_psi))
     if style_dim is None and truncation_psi is not None:
         raise ValueError('%s needs %s (the style-based generator whose w it truncates), which is None' % (L('truncation_psi'), L('style_dim')))
+    if not isinstance(modulated_conv, bool):
+        raise ValueError('%s must be True or False, got %r' % (L('modulated_conv'), modulated_conv))
+    if modulated_conv and style_dim is None:
+        raise ValueError('%s needs %s (the style-based generator whose convolutions it modulates), which is None' % (L('modulated_conv'), L('style_dim')))
     # resample_filter=(1, 3, 3, 1): utils.ops.upsample_2d for the generator's nearest x2 `upscale` and utils.ops.downsample_2d for the critic's
     # 2x2 `pool`, in the blocks and in both fade-in branches (Karras et al. 2019, Zhang 2019): one launch of
     # csrc/t2i_resample.hip each, differentiable to any order.  This changes the generator's function, so checkpoints carry the normalised
@@ -125,7 +133,7 @@ def validated(batch_size, critic_norm=None, critic_mbstd=None, g_ema=None, equal
     if critic_mbstd is not None and not _count(batch_size):
         raise ValueError('%s needs an integer batch_size >= 1 to pick its group size from, got %r' % (L('critic_mbstd'), batch_size))
     group = None if critic_mbstd is None else max(g for g in range(1, min(critic_mbstd, 16) + 1) if batch_size % g == 0)
-    return dict(style_dim=style_dim, mapping_layers=mapping_layers, style_noise=style_noise,
+    return dict(style_dim=style_dim, mapping_layers=mapping_layers, style_noise=style_noise, modulated_conv=modulated_conv,
                 truncation_psi=None if truncation_psi is None else float(truncation_psi),
                 resample_filter=None if taps is None else taps[0],        # the taps as given; None: nearest x2 and the 2x2 mean
                 resample_taps=None if taps is None else taps[1],          # ... divided by their sum, float32: what checkpoints carry
@@ -150,7 +158,7 @@ def add_resample_filter_argument(ap, reader=True):
 
 
 def add_style_arguments(ap, reader=True):
-    """PGGAN's style-based generator: --style-dim, --mapping-layers, --no-style-noise, and for the readers --truncation-psi."""
+    """PGGAN's style-based generator: --style-dim, --mapping-layers, --no-style-noise, --modulated-conv, and for the readers --truncation-psi."""
     ap.add_argument('--style-dim', type=int, default=None, metavar='D',
                     help="the style-based generator (Karras et al. 2019): a mapping network turns [z, c] into a style vector w of D units, and "
                          "every generator convolution is followed by per-pixel noise, instance norm and an affine map of w%s (default: the "
@@ -158,6 +166,10 @@ def add_style_arguments(ap, reader=True):
                                                      '; the evaluators and visualisers must be given the same'))
     ap.add_argument('--mapping-layers', type=int, default=None, metavar='N', help='--style-dim: dense layers of the mapping network (default 4)')
     ap.add_argument('--no-style-noise', action='store_true', help='--style-dim: build the style blocks without the per-pixel noise and its strengths')
+    ap.add_argument('--modulated-conv', action='store_true',
+                    help='--style-dim: weight-demodulated convolutions (Karras et al. 2020) in place of convolution + instance norm + style%s'
+                         % (' - give it exactly when the checkpoint was trained with it: a mismatch is refused' if reader else
+                            '; the evaluators and visualisers must be given the same'))
     if reader:
         ap.add_argument('--truncation-psi', type=float, default=None, metavar='PSI',
                         help='--style-dim: sample from w_avg + PSI (w - w_avg), w_avg the running mean of w the checkpoint carries (default: w itself)')
@@ -217,6 +229,8 @@ def kwargs_of(ap, args):
             pass                                    # (left a string, which `validated` refuses by its text)
     if given('style_dim') is None and (given('mapping_layers') is not None or given('no_style_noise') or given('truncation_psi') is not None):
         ap.error('--mapping-layers / --no-style-noise / --truncation-psi need --style-dim (the generator they configure)')
+    if given('style_dim') is None and given('modulated_conv'):
+        ap.error('--modulated-conv needs --style-dim (the generator whose convolutions it modulates)')
     if given('diffaug') is None and (given('diffaug_p') is not None or given('diffaug_adapt')):
         ap.error('--diffaug-p / --diffaug-adapt need --diffaug (the policy they apply)')
     # the numbers of the run's sampler (`run_sampler`), which are no keywords of the model
@@ -232,7 +246,7 @@ def kwargs_of(ap, args):
     kw = dict(critic_norm=given('critic_norm'), critic_mbstd=given('critic_mbstd'), g_ema=given('g_ema'), adam_lr=given('lr'), diffaug=given('diffaug'),
               diffaug_p=given('diffaug_p'), resample_filter=taps, style_dim=given('style_dim'), mapping_layers=given('mapping_layers'),
               truncation_psi=given('truncation_psi'), style_noise=False if given('no_style_noise') else None,
-              **{k: True for k in ('equalized_lr', 'critic_sn', 'diffaug_adapt') if given(k)})
+              **{k: True for k in ('equalized_lr', 'critic_sn', 'diffaug_adapt', 'modulated_conv') if given(k)})
     kw = {k: v for k, v in kw.items() if v is not None}
     try:
         validated(1, label=flag, **kw)              # (batch 1: the group of --critic-mbstd is picked per entry, by the constructor)
@@ -293,12 +307,22 @@ def describe_style(sig):
     return 'a style-based generator (--style-dim %d --mapping-layers %d%s)' % (sig[0], sig[1], '' if sig[2] else ' --no-style-noise')
 
 
+def modulated_of_names(names):
+    """Whether the generator whose variables are `names` has weight-demodulated convolutions (PGGAN(modulated_conv=True)): the bit beside
+    style_of_names' triple."""
+    return any('/ModConv' in n for n in names)
+
+
+def describe_modulated(on):
+    return 'weight-demodulated convolutions (--modulated-conv)' if on else 'convolution + AdaIN layers (no --modulated-conv)'
+
+
 def checkpoint_architecture(directory):
     """What the newest checkpoint of `directory` (utils.saver.latest_checkpoint) says about its generator, in one open: ({name: shape} of
-    the mapping-network and style-block entries, which style_of_names reads; the RESAMPLE_KEY entry or None).  None without a checkpoint."""
+    the mapping-network, style-block and modulated-convolution entries, which style_of_names and modulated_of_names read; the RESAMPLE_KEY entry or None).  None without a checkpoint."""
     path = latest_checkpoint(directory)
     if path is None:
         return None
     with np.load(path) as z:
-        names = {k: tuple(z[k].shape) for k in z.files if k.startswith('g_net/mapping/') or '/StyleMod' in k}
+        names = {k: tuple(z[k].shape) for k in z.files if k.startswith('g_net/mapping/') or '/StyleMod' in k or '/ModConv' in k}
         return names, (z[RESAMPLE_KEY] if RESAMPLE_KEY in z.files else None)

@@ -31,7 +31,7 @@ from ... import scope as S
 from ...graphs import DGSchedule, StepGraphs
 from ...utils.saver import Saver, load, save
 from ...utils.ops import (DiffAugmentSampler, concat_tile, conv2d, diff_augment, diff_augment_params, downsample_2d, fc, layer_norm, lerp,
-                          lrelu_act, minibatch_stddev_stat, pixel_norm, pool, relu, style_block, upsample_2d, upscale)
+                          lrelu_act, minibatch_stddev_stat, modulated_conv2d, pixel_norm, pool, relu, style_block, upsample_2d, upscale)
 from .options import RESAMPLE_KEY, W_AVG, checkpoint_architecture, describe_taps, same_taps, validated
 from .options import normalised_taps, style_of_names  # noqa: F401  (importable from here, as before)
 
@@ -44,13 +44,14 @@ class PGGAN(object):
                  build_model=True, device=None, seed=0, store=None, fmap_base=1024, fmap_max=512, z_dim=128, embed_dim=1024,
                  compr_embed_dim=128, dp=None, critic_norm=None, critic_mbstd=None, g_ema=None, equalized_lr=False, adam_lr=None,
                  diffaug=None, diffaug_p=None, diffaug_adapt=False, diffaug_sampler=None, critic_sn=False, resample_filter=None,
-                 style_dim=None, mapping_layers=4, style_noise=True, truncation_psi=None):
-        # style_dim, mapping_layers, style_noise, truncation_psi, resample_filter, resample_taps, critic_sn, diffaug, diffaug_p, diffaug_adapt,
+                 style_dim=None, mapping_layers=4, style_noise=True, truncation_psi=None, modulated_conv=False):
+        # style_dim, mapping_layers, style_noise, truncation_psi, modulated_conv, resample_filter, resample_taps, critic_sn, diffaug, diffaug_p, diffaug_adapt,
         # aug_sampler (the model's own is made below, on the store's device), adam_lr, equalized_lr, g_ema, critic_norm, critic_mbstd, mbstd_group
         vars(self).update(validated(
             batch_size, critic_norm=critic_norm, critic_mbstd=critic_mbstd, g_ema=g_ema, equalized_lr=equalized_lr, adam_lr=adam_lr, diffaug=diffaug,
             diffaug_p=diffaug_p, diffaug_adapt=diffaug_adapt, diffaug_sampler=diffaug_sampler, critic_sn=critic_sn, resample_filter=resample_filter,
-            style_dim=style_dim, mapping_layers=mapping_layers, style_noise=style_noise, truncation_psi=truncation_psi))
+            style_dim=style_dim, mapping_layers=mapping_layers, style_noise=style_noise, truncation_psi=truncation_psi,
+            modulated_conv=modulated_conv))
         self._sn = None                           # where the style blocks take their noise from: (feed, 'd' | 'g'), a list of images, or None (drawn)
         self.resample_restored = None             # train(): the taps of the checkpoint the last restore read (None: it had none)
         self.critic_spectral = None
@@ -436,7 +437,13 @@ class PGGAN(object):
 
     def _g_conv(self, x, f):
         """A 3x3 convolution of the generator and what follows it: the reference's layer_norm(relu), or with style_dim style block k of
-        the pass: per-pixel noise scaled per channel, relu, instance norm, the style's affine map."""
+        the pass: per-pixel noise scaled per channel, relu, instance norm, the style's affine map.  With modulated_conv the pair is one
+        weight-demodulated convolution: the style scales the input channels, then bias, the same noise and relu."""
+        if self.modulated_conv:
+            k, self._block = self._block, self._block + 1
+            noise = self._style_noise_image(k, x)
+            return modulated_conv2d(x, self._w_used, f, ks=(3, 3), noise=noise, act=relu, init=self._init(3 * 3 * x.shape[-1]),
+                                    style_init=self._init(self.style_dim))
         x = self._conv2d(x, f=f, ks=(3, 3), s=(1, 1))
         if self.style_dim is None:
             return layer_norm(x, act=relu)

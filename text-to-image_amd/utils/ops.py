@@ -23,6 +23,7 @@ section 4.35) take fp32 tensors only, with the same refusals, and are differenti
 4.39) draws those tables on the device with a probability ``p`` per transform and can steer ``p`` from a critic's outputs.
 ``adain`` / ``style_block`` (not in the reference: the layer of a style-based generator) take fp32 tensors only,
 with the same refusals, and are first order: the generator is never under the gradient penalty.
+``modulated_conv2d`` (not in the reference: the weight-demodulated convolution of Karras et al. 2020) likewise.
 """
 import math
 import struct
@@ -425,6 +426,66 @@ def style_block(x, w, noise=None, act=None, name=None, init=None):
         strength = st.get_variable('noise_strength', (C,), S.constant_init(0.0)) if noise is not None else None
         s = fc(w, 2 * C, init=init, name='style')
     return adain(x, s[:, :C], s[:, C:], noise=noise, strength=strength, act=act)
+
+
+def modulated_conv2d(x, w, f, ks=(3, 3), noise=None, act=None, demodulate=True, init=None, style_init=None, name=None, eps=1e-8):
+    """A weight-demodulated convolution (Karras et al. 2020; not in the reference): x [B,H,W,Cin] (contiguous NHWC,
+    fp32), w [B, w_dim] the style vector, noise [B,H,W] a standard-normal image or None; stride 1, padding 'SAME'.
+    Variables: <scope>/ModConv[_k]/{weights [kh,kw,Cin,f] (He, or init), biases [f] zeros, noise_strength [f] zeros (only with noise),
+    style/kernel [w_dim,Cin] (fc's He default, or style_init), style/bias [Cin] zeros}.
+      s = 1 + fc(w, Cin)                                         the per-sample scale of every input channel
+      d[b,o] = rsqrt(sum_{kh,kw,i} (weights[.,.,i,o] s[b,i])^2 + eps)      (demodulate=False: 1)
+      y = act(conv(x[b], weights s[b,:] d[b,:]) + biases + noise_strength[o] noise[b,h,w])
+    computed as act(d conv(x s, weights) + ...), which is the same function: a scale pass over x, the project's convolution without bias
+    or activation, one epilogue.  act: None, relu or lrelu_act(slope >= 0), fused.  Gradients reach x, w and every variable (the
+    parameters' not under autograd.input_grads_only()); noise gets none.  First order only.  bf16 tensors, a stacked pass, another rank, a
+    non-contiguous x or noise, wrong shapes, a negative lrelu slope, tanh and an unfused activation are refused before any launch."""
+    op = 'modulated_conv2d'
+    st = S.default_store()
+    _fp32_plain(x, op)
+    kind, alpha, post = _split_act(act)
+    if post is not None or kind == K.ACT_TANH:
+        raise ValueError('%s: act must be None, relu or an lrelu_act (it is fused into the epilogue behind the convolution), got %r' % (op, act))
+    if kind == K.ACT_LRELU and alpha < 0.0:
+        raise ValueError('%s: lrelu_act(%g) has a negative slope; the backward takes the derivative from the sign, which needs a slope >= 0' % (op, alpha))
+    if not x.is_contiguous():
+        raise ValueError('%s: x must be physically NHWC; got a non-contiguous tensor (shape %s, strides %s) - convert a logical NCHW '
+                         'view with to_nhwc first' % (op, tuple(x.shape), x.stride()))
+    B, H, W, Cin = (int(v) for v in x.shape)
+    if min(B, H, W, Cin) < 1 or x.numel() >= 1 << 31:
+        raise ValueError('%s: every size of x must be at least 1 and x must have fewer than 2^31 elements, got %s' % (op, tuple(x.shape)))
+    if isinstance(w, ST.Stacked):
+        raise NotImplementedError('%s: w is a stacked pass (stacked.Stacked), which is not supported' % op)
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.dim() != 2 or w.shape[0] != B or w.shape[1] < 1 or w.device != x.device:
+        raise ValueError('%s: w must be a float32 tensor of shape [%d, w_dim] on %s, got %s' % (
+            op, B, x.device, '%s %s on %s' % (w.dtype, tuple(w.shape), w.device) if isinstance(w, torch.Tensor) else type(w).__name__))
+    if isinstance(f, bool) or not isinstance(f, int) or f < 1:
+        raise ValueError('%s: f must be an integer >= 1 (the output channels), got %r' % (op, f))
+    kh, kw = _pair(ks)
+    if kh < 1 or kw < 1:
+        raise ValueError('%s: ks must be a pair of extents >= 1, got %r' % (op, ks))
+    if noise is not None:
+        if not isinstance(noise, torch.Tensor) or noise.dtype != torch.float32 or tuple(noise.shape) != (B, H, W) or noise.device != x.device:
+            raise ValueError('%s: noise must be a float32 tensor of shape %s on %s, got %s' % (
+                op, [B, H, W], x.device, '%s %s on %s' % (noise.dtype, tuple(noise.shape), noise.device) if isinstance(noise, torch.Tensor)
+                else type(noise).__name__))
+        if not noise.is_contiguous():
+            raise ValueError('%s: noise must be contiguous (strides %s)' % (op, noise.stride()))
+        if noise.requires_grad:
+            raise ValueError('%s: noise requires a gradient, and the operator gives it none (detach it)' % op)
+    if not isinstance(demodulate, bool):
+        raise ValueError('%s: demodulate must be True or False, got %r' % (op, demodulate))
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not (math.isfinite(eps) and eps >= 0.0):
+        raise ValueError('%s: eps must be a finite number >= 0, got %r' % (op, eps))
+    with st.variable_scope(name or st.unique_op_name('ModConv'), reuse=st.reuse()):
+        weights = st.get_variable('weights', (kh, kw, Cin, f), init or S.he_init(kh * kw * Cin))
+        biases = st.get_variable('biases', (f,), S.constant_init(0.0))
+        strength = st.get_variable('noise_strength', (f,), S.constant_init(0.0)) if noise is not None else None
+        s = 1.0 + fc(w, Cin, init=style_init, name='style')
+    geom = K.conv_desc(B, H, W, Cin, f, kh, kw, 1, 1, 'SAME')
+    d = A.DemodCoefFn.apply(weights, s, float(eps))[0] if demodulate else None
+    c = A.Conv2dFn.apply(A.ModulateFn.apply(x, s), weights, None, geom, K.ACT_NONE, 0.0)
+    return A.DemodActFn.apply(c, d, biases, noise, strength, kind, alpha)
 
 
 def minibatch_stddev_stat(x, group_size=4, num_features=1, eps=1e-8):

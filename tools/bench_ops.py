@@ -5,7 +5,8 @@ without the weight EMA (`--only adam_ema`) and with per-slot multipliers (`--onl
 differentiable augmentation of csrc/t2i_augment.hip at the PGGAN trainer's shapes next to the same policy from tensor-library calls
 (`--only diff_augment`), and the critic's optimizer step with and without spectral normalisation (`--only spectral_norm`), and the
 anti-aliased resampling of csrc/t2i_resample.hip at the PGGAN trainer's full widths (`--only upfirdn`), and the style layer of
-csrc/t2i_style.hip at the generator's B = 8 shapes next to layer_norm on the same tensors (`--only adain`): one JSON line per kernel with the time per call, the bytes the algorithm moves (reads + writes, from the
+csrc/t2i_style.hip at the generator's B = 8 shapes next to layer_norm on the same tensors (`--only adain`), and the launches of a
+weight-demodulated convolution besides its convolution (csrc/t2i_modconv.hip) next to the style layer in the same run (`--only modconv`): one JSON line per kernel with the time per call, the bytes the algorithm moves (reads + writes, from the
 shapes), bytes per second, and the ratio of that rate to a device-to-device copy that moves the SAME number of bytes (half read, half
 written), timed in the same process.  Per measurement: 10 warm-up launches, then REPS rounds of 100 back-to-back launches between
 device events, kernel and copy rounds alternating; the median round is reported.  Read the ratio, not the absolute rate, as the share
@@ -349,6 +350,54 @@ def main():
                     lambda: A.LayerNormBwdFn.apply(g, x, gamma, xhat, lrstd, yl, K.ACT_RELU, 0.0, R * C, True), 5)
                 one('a separate noise add stood in for by bn_apply (r + w)', 8 * n, lambda: K.bn_apply(x, gamma, beta, K.ACT_NONE, 0.0), 1)
                 del x, g, y, dx, xhat, yl
+
+    # the weight-demodulated convolution's launches around its convolution at the same four shapes, Cin = Cout,
+    # relu + noise: each call alone, the layer's non-convolution launches together forward (coef + modulate + epilogue) and backward
+    # (epilogue + scale gradient + input adjoint + coef, as the autograd Functions issue them), and in the same run the adain forward /
+    # backward and t2i_adain_apply at the shape: the path they replace and the plain r + w pass the two new ones are compared with.
+    # Bytes: the passes over the [B,H,W,C] tensors (modulate r + w; bwd_scale 2r; demod_act r + w; its backward 2r + w); the coefficient
+    # calls are charged their passes over the filter (coef: r of W; its backward: r of W + w of dW).
+    if a.only and a.only in 'modconv':
+        from t2i_amd._lib import check, lib
+        with torch.no_grad():
+            for shape in ((8, 4, 4, 512), (8, 16, 16, 512), (8, 64, 64, 128), (8, 256, 256, 64)):
+                B, H, W, C = shape
+                R, n, nw = H * W, B * H * W * C, 9 * C * C
+                x, g, c = (torch.randn(shape, device='cuda') for _ in range(3))
+                nz, st, bias = torch.randn((B, H, W), device='cuda'), torch.rand(C, device='cuda') - 0.5, torch.randn(C, device='cuda') * 0.1
+                s, gd = 1.0 + 0.3 * torch.randn((B, C), device='cuda'), torch.randn((B, C), device='cuda')
+                w = torch.randn((3, 3, C, C), device='cuda') * (2.0 / (9 * C)) ** 0.5
+                d, q = K.demod_coef(w, s)
+                one = lambda name, nbytes, fn, launches: measure('modconv: ' + name, shape, nbytes, fn, a.reps, a.iters, extra={'launches': launches})
+                one('t2i_demod_coef (r of W)', 4 * nw, lambda: K.demod_coef(w, s), 2)
+                one('t2i_demod_coef_bwd ds + dW (r + w of W)', 8 * nw, lambda: K.demod_coef_bwd(gd, d, w, s, q), 2)
+                one('t2i_modulate (r + w)', 8 * n, lambda: K.modulate(x, s), 1)
+                one('t2i_modulate_bwd_scale (2r)', 8 * n, lambda: K.modulate_bwd_scale(g, x), 2)
+                one('t2i_demod_act relu + noise (r + w)', 8 * n, lambda: K.demod_act(c, d, bias, nz, st, K.ACT_RELU, 0.0), 1)
+                one('t2i_demod_act_bwd relu + noise, every sum (2r + w)', 12 * n, lambda: K.demod_act_bwd(g, c, d, bias, nz, st, K.ACT_RELU, 0.0), 2)
+
+                def fwd():
+                    dd, _ = K.demod_coef(w, s)
+                    K.modulate(x, s)
+                    K.demod_act(c, dd, bias, nz, st, K.ACT_RELU, 0.0)
+
+                def bwd():
+                    K.demod_act_bwd(g, c, d, bias, nz, st, K.ACT_RELU, 0.0)
+                    K.demod_coef_bwd(gd, d, w, s, q)
+                    K.modulate(g, s)
+                    K.modulate_bwd_scale(g, x)
+                one('layer forward without its convolution = coef + modulate + demod_act (2r + 2w, r of W)', 16 * n + 4 * nw, fwd, 4)
+                one('layer backward without its convolutions = demod_act_bwd + coef_bwd + modulate + bwd_scale (5r + 2w, r + w of W)',
+                    28 * n + 8 * nw, bwd, 7)
+                sty = torch.randn((B, 2 * C), device='cuda') * 0.3
+                ys, yb = sty[:, :C], sty[:, C:]
+                y, mean, rstd = K.adain_fwd(x, ys, yb, nz, st, K.ACT_RELU, 0.0)
+                p, sm = K._ptr, K._stream
+                one('t2i_adain_apply relu + noise, same run (r + w)', 8 * n, lambda: check(lib.t2i_adain_apply(p(x), p(nz), p(st), p(mean), p(rstd),
+                    p(ys), p(yb), 2 * C, B, R, C, K.ACT_RELU, 0.0, p(y), sm())), 1)
+                one('adain forward, same run (2r + w)', 12 * n, lambda: K.adain_fwd(x, ys, yb, nz, st, K.ACT_RELU, 0.0), 3)
+                one('adain backward, same run (4r + w)', 20 * n, lambda: K.adain_bwd(g, x, ys, mean, rstd, nz, st, K.ACT_RELU, 0.0), 4)
+                del x, g, c, y
 
 
 if __name__ == '__main__':
