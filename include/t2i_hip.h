@@ -1037,6 +1037,30 @@ int t2i_demod_act_bwd(const float* g, const float* c, const float* d, const floa
                       int64_t R, int32_t C, int act, float alpha, float* dc, float* dd, float* dbias, float* dstrength, void* ws,
                       size_t ws_bytes, t2i_stream_t stream);
 
+/* ---- the backward of that backward (path-length regularisation differentiates the generator twice).  csrc/t2i_modconv.hip, DESIGN.md
+ * section 4.46.  Added within ABI v13: no existing argument list changed.  Same items, forms, grid, order of sums and refusals as above.
+ * t2i_demod_act_bwd2 (1 launch, 2 with gd): with m = act'(p), p recomputed by the forward's sequence, the first backward gave dc = m g d
+ *         and dd = sum_r m g c.  For the cotangents vc [B,R,C] of dc and vd [B,C] of dd (each may be NULL, not both; vd needs d):
+ *           gg [B,R,C] (or NULL) = m (d vc + c vd)     gc [B,R,C] (or NULL; needs vd) = m g vd     gd [B,C] (or NULL; needs vc and d) = sum_r m g vc
+ *         g is read only for gc and gd (it may be NULL without them).  bias, strength and noise get nothing: act'' is zero almost everywhere.
+ * t2i_modulate2 (1 launch): the first backward gave dx = g s and ds = sum_r g x.  For the cotangents vx [B,R,C] and vs [B,C] (dense; each
+ *         may be NULL, not both; vx comes with s, vs with x):  gg = s vx + x vs.  (g vs is t2i_modulate, sum_r vx g is t2i_modulate_bwd_scale.)
+ * t2i_demod_coef_bwd2 (a launch for gg_d / gd_d, a launch for dW): the first backward gave ds = 2 s sum_o q e, e = -d^3 gd / 2.  For the
+ *         cotangent vs [B,Cin] (dense) of ds, with r[b,o] = sum_i vs[b,i] s[b,i] q[i,o] (input channels in 4 fixed lanes, ascending):
+ *           gg_d [B,Cout] (or NULL; needs q) = -d^3 r           (to gd)
+ *           gd_d [B,Cout] (or NULL; needs q) = -3 d^2 gd r      (to d)
+ *           dW [T,Cin,Cout] (or NULL; needs W) (+)= 4 W[t,i,o] sum_b vs[b,i] s[b,i] e[b,o], b ascending; accumulate as in t2i_demod_coef_bwd
+ *         (the term to s is t2i_demod_coef_bwd's ds with vs in place of s). */
+size_t t2i_demod_act_bwd2_workspace_bytes(int32_t B, int64_t R, int32_t C);
+int t2i_demod_act_bwd2(const float* g, const float* c, const float* d, const float* bias, const float* noise, const float* strength,
+                       const float* vc, const float* vd, int32_t B, int64_t R, int32_t C, int act, float alpha, float* gg, float* gc, float* gd,
+                       void* ws, size_t ws_bytes, t2i_stream_t stream);
+int t2i_modulate2(const float* s, int32_t style_stride, const float* vx, const float* x, const float* vs, int32_t B, int64_t R, int32_t C,
+                  float* gg, t2i_stream_t stream);
+int t2i_demod_coef_bwd2(const float* vs, const float* gd, const float* d, const float* s, int32_t style_stride, const float* W, const float* q,
+                        int32_t T, int32_t Cin, int32_t Cout, int32_t B, float* gg_d, float* gd_d, float* dW, int32_t accumulate,
+                        t2i_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

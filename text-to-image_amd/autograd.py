@@ -1223,3 +1223,160 @@ class DemodActFn(Function):
             return K.demod_act_bwd(_c(g), c, d, bias, noise, strength, act, alpha, *want)
         dc, dd, dbias, dstrength = _FirstOrder.apply('modulated_conv2d', piece, g, c, d, bias, noise, strength)
         return dc, dd, dbias, None, dstrength, None, None
+
+
+# ---- the same three functions, differentiable twice (path-length regularisation) ----------------------------------
+# ops.modulated_conv2d(second_order=True) uses the subclasses below: the forward and the first-order backward are the parents' launches
+# (the values are theirs bit for bit); under create_graph the backward is a Function whose own backward is csrc/t2i_modconv.hip's second-order
+# entry points.  In a final backward (no graph is being recorded) the parents' backward runs as it is, arena sinks included.
+_MODCONV_THIRD = ('%s: a third differentiation is not implemented - second_order=True makes the layer differentiable twice (the path-length '
+                  'regulariser is the gradient of a gradient norm), and nothing in the package differentiates it again')
+_MODCONV_PARAM = ('%s: a cotangent for the gradient of %s is the gradient of a parameter gradient, which is not implemented (layer_norm '
+                  'refuses it likewise) - take the first backward under autograd.input_grads_only(), which does not form it')
+
+
+class _SecondOrder(Function):
+    """The second-order piece of a weight-demodulated convolution's functions: runs `fn(*args)`, not differentiable again."""
+
+    @staticmethod
+    def forward(ctx, op, fn, *args):
+        ctx.op = op
+        ctx.set_materialize_grads(False)
+        return fn(*args)
+
+    @staticmethod
+    def backward(ctx, *v):
+        raise NotImplementedError(_MODCONV_THIRD % ctx.op)
+
+
+class ModulateBwdFn(Function):
+    """(dx, ds) of ModulateFn from g: dx = g s, ds = sum over (h, w) of g x (the launches of ModulateFn.backward).  Backward, for the
+    cotangents vx and vs: to g, s vx + x vs (one launch, t2i_modulate2); to x, g vs (t2i_modulate); to s, sum over (h, w) of vx g
+    (t2i_modulate_bwd_scale)."""
+
+    @staticmethod
+    def forward(ctx, g, x, s, want_x, want_s):
+        g = _c(g)
+        ctx.save_for_backward(g, x, s)
+        ctx.set_materialize_grads(False)
+        return (K.modulate(g, s) if want_x else None), (K.modulate_bwd_scale(g, x) if want_s else None)
+
+    @staticmethod
+    def backward(ctx, vx, vs):
+        if vx is None and vs is None:
+            return (None,) * 5
+        g, x, s = ctx.saved_tensors
+        need = ctx.needs_input_grad
+
+        def piece(g, x, s, vx, vs):
+            vx, vs = (None if v is None else _c(v) for v in (vx, vs))
+            return (K.modulate2(s, vx, x, vs) if need[0] else None, K.modulate(g, vs) if (need[1] and vs is not None) else None,
+                    K.modulate_bwd_scale(vx, g) if (need[2] and vx is not None) else None)
+        return _SecondOrder.apply('modulated_conv2d', piece, g, x, s, vx, vs) + (None, None)
+
+
+class ModulateFn2(ModulateFn):
+    """ModulateFn, differentiable twice."""
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None or not torch.is_grad_enabled():
+            return ModulateFn.backward(ctx, g)
+        x, s = ctx.saved_tensors
+        return ModulateBwdFn.apply(g, x, s, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+
+
+class DemodCoefBwdFn(Function):
+    """(ds, dw) of DemodCoefFn from gd (the launches of DemodCoefFn.backward).  Backward, for the cotangent vs of ds, with
+    e = -d^3 gd / 2 and r = sum_i vs s q: to gd, -d^3 r and to d, -3 d^2 gd r (one launch); to s, 2 vs sum_o q e (t2i_demod_coef_bwd with vs
+    in place of s); to w, 4 w sum_b vs s e (one launch; into the weight's gradient-arena slot in a final backward, like dw).  d is
+    DemodCoefFn's output, so its cotangent runs DemodCoefFn's backward once more.  A cotangent for dw is refused."""
+
+    @staticmethod
+    def forward(ctx, gd, d, w, s, q, want_s, want_w):
+        gd = _c(gd)
+        ctx.save_for_backward(gd, d, w, s, q)
+        ctx.set_materialize_grads(False)
+        return K.demod_coef_bwd(gd, d, w, s, q, want_s, want_w)
+
+    @staticmethod
+    def backward(ctx, vs, vdw):
+        if vdw is not None:
+            raise NotImplementedError(_MODCONV_PARAM % ('modulated_conv2d', 'weights'))
+        if vs is None:
+            return (None,) * 7
+        gd, d, w, s, q = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want_w = need[2] and not _INPUTS_ONLY[0]
+        sink = _sink_of(w) if want_w else None
+
+        def piece(gd, d, w, s, q, vs):
+            vs = _c(vs)
+            gs = K.demod_coef_bwd(gd, d, w, vs, q, True, False)[0] if need[3] else None
+            if sink is None:
+                return K.demod_coef_bwd2(vs, gd, d, w, s, q, need[0], need[1], want_w) + (gs,)
+            ggd, gdd, _ = K.demod_coef_bwd2(vs, gd, d, w, s, q, need[0], need[1], False)
+            acc = sink_accumulate(w.data_ptr())
+            sunk_launch(lambda: K.demod_coef_bwd2(vs, gd, d, w, s, q, False, False, True, out=sink, accumulate=acc), (vs, gd, d, w, s, q))
+            _notify(w)
+            return ggd, gdd, None, gs
+        ggd, gdd, gw, gs = _SecondOrder.apply('modulated_conv2d', piece, gd, d, w, s, q, vs)
+        return ggd, gdd, gw, gs, None, None, None
+
+
+class DemodCoefFn2(DemodCoefFn):
+    """DemodCoefFn, differentiable twice."""
+
+    @staticmethod
+    def backward(ctx, gd, _gq):
+        if gd is None or not torch.is_grad_enabled():
+            return DemodCoefFn.backward(ctx, gd, _gq)
+        w, s, q, d = ctx.saved_tensors
+        want_w = ctx.needs_input_grad[0] and not _INPUTS_ONLY[0]
+        ds, dw = DemodCoefBwdFn.apply(gd, d, w, s, q, ctx.needs_input_grad[1], want_w)
+        return dw, ds, None
+
+
+class DemodActBwdFn(Function):
+    """(dc, dd, dbias, dstrength) of DemodActFn from g (the launch pair of DemodActFn.backward).  Backward, for the cotangents vc of dc and
+    vd of dd, with m = act'(the recomputed pre-activation): to g, m (d vc + c vd); to c, m g vd; to d, sum over (h, w) of m g vc - one
+    launch, two with the last (t2i_demod_act_bwd2).  bias, strength and noise get nothing: act'' is zero almost everywhere.  A cotangent
+    for dbias or dstrength is refused."""
+
+    @staticmethod
+    def forward(ctx, g, c, d, bias, noise, strength, act, alpha, want):
+        g = _c(g)
+        ctx.save_for_backward(g, c, d, bias, noise, strength)
+        ctx.act, ctx.alpha = act, alpha
+        ctx.set_materialize_grads(False)
+        return K.demod_act_bwd(g, c, d, bias, noise, strength, act, alpha, *want)
+
+    @staticmethod
+    def backward(ctx, vc, vd, vbias, vstrength):
+        for v, name in ((vbias, 'biases'), (vstrength, 'noise_strength')):
+            if v is not None:
+                raise NotImplementedError(_MODCONV_PARAM % ('modulated_conv2d', name))
+        if vc is None and vd is None:
+            return (None,) * 9
+        g, c, d, bias, noise, strength = ctx.saved_tensors
+        need, act, alpha = ctx.needs_input_grad, ctx.act, ctx.alpha
+
+        def piece(g, c, d, bias, noise, strength, vc, vd):
+            vc, vd = (None if v is None else _c(v) for v in (vc, vd))
+            return K.demod_act_bwd2(g, c, d, bias, noise, strength, vc, vd, act, alpha, need[0], need[1], d is not None and need[2])
+        gg, gc, gd = _SecondOrder.apply('modulated_conv2d', piece, g, c, d, bias, noise, strength, vc, vd)
+        return gg, gc, gd, None, None, None, None, None, None
+
+
+class DemodActFn2(DemodActFn):
+    """DemodActFn, differentiable twice."""
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None or not torch.is_grad_enabled():
+            return DemodActFn.backward(ctx, g)
+        c, d, bias, noise, strength = ctx.saved_tensors
+        need, params = ctx.needs_input_grad, not _INPUTS_ONLY[0]
+        want = (d is not None and need[1], bias is not None and need[2] and params, strength is not None and need[4] and params)
+        dc, dd, dbias, dstrength = DemodActBwdFn.apply(g, c, d, bias, noise, strength, ctx.act, ctx.alpha, want)
+        return dc, dd, dbias, None, dstrength, None, None

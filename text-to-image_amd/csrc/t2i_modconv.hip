@@ -21,6 +21,14 @@
 //   modconv_sum_kernel      fixed-order sums of such partials: job b < B: component 0 over the chunks of sample b -> [B,C]; job B: component
 //                           1 over all B chunks partials -> [C]; job B + 1: component 2 likewise -> [C]
 //
+// and the backward of that backward (path-length regularisation differentiates the generator twice):
+//
+//   demod_act_bwd2_kernel<V> m = act'(p), p recomputed as above; gg = m (d vc + c vd), gc = m g vd, per-item sums of m g vc -> workspace
+//                           [B chunks][1][C] (finished by modconv_sum_kernel -> gd [B,C]); every plane is read once
+//   modulate2_kernel<V>     gg = s vx + x vs in one pass
+//   demod_r_kernel          per (b, 64 outputs), demod_d_kernel's lanes: r = sum_i vs s q -> -d^3 r (to gd) and -3 d^2 gd r (to d)
+//   demod_dw2_kernel        a thread per (i, o): dW[t,i,o] (+)= 4 W[t,i,o] sum_b vs[b,i] s[b,i] e[b,o], b ascending
+//
 // The tensor kernels use t2i_style.hip's item: (sample, chunk of 64 rows, tile of 64 channels), numbered tile-fastest, walked by a grid of at
 // most 65535 workgroups of 256 threads with a stride; 16-byte accesses (V = 4) when C % 4 == 0 and the [B,R,C] tensors are 16-byte aligned,
 // scalar ones otherwise.  No atomics; every sum's order depends on the shape alone and never on B, so a sample's results do not depend on its
@@ -62,6 +70,9 @@ struct ModParams {
   const float* strength;   // [C] or NULL, with noise
   float* out;              // xs, out or dc (dc may be NULL)
   float* part;             // workspace partials
+  const float* v;          // second order: the plane cotangent (vc of dc, vx of dx) or NULL
+  const float* vrow;       // second order: the [B,C] cotangent (vd of dd, vs of ds), dense, or NULL
+  float* out2;             // second order: gc or NULL
   long long R, items;
   int B, C, chunks, ctiles, act, sstride;
   int want_dd, want_dbias, want_dstrength;
@@ -382,6 +393,135 @@ __global__ __launch_bounds__(kThreads) void modconv_sum_kernel(const float* part
   }
 }
 
+// ---- the backward of the backward ------------------------------------------------------------------------------
+// The epilogue: dc = m g d and dd = sum_r m g c are linear in g, c-and-d apart from m = act'(p), whose own derivative is zero almost
+// everywhere.  Absent cotangents stand as zeros (exact: a product with 0 adds nothing), absent planes are not read.
+template <int V>
+__global__ __launch_bounds__(kThreads) void demod_act_bwd2_kernel(const ModParams P) {
+  typedef Lay<V> L;
+  __shared__ float s_a[L::TY][kTileC];
+  const int tid = threadIdx.x, tx = tid % L::LX, ty = tid / L::LX;
+  const bool noisy = P.noise != nullptr;
+  for (long long id = blockIdx.x; id < P.items; id += gridDim.x) {
+    const Item it = item_of<V>(P, id, tx);
+    float sd[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) sd[j] = 0.f;
+    if (it.c0 < P.C) {
+      float d[V], bi[V], s[V], vd[V];
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        const int c = it.c0 + j;
+        d[j] = P.s ? P.s[(size_t)it.b * P.C + c] : 1.0f;
+        bi[j] = P.bias ? P.bias[c] : 0.f;
+        s[j] = noisy ? P.strength[c] : 0.f;
+        vd[j] = P.vrow ? P.vrow[(size_t)it.b * P.C + c] : 0.f;
+      }
+#pragma unroll
+      for (int k = 0; k < L::RPT; ++k) {
+        const int lr = ty + k * L::TY;
+        if (lr < it.nrows) {
+          const long long row = it.row0 + lr;
+          float v[V], g[V], vc[V], gc[V];
+          load_v<V>(P.x + row * P.C + it.c0, v);
+          if (P.g) load_v<V>(P.g + row * P.C + it.c0, g);
+          if (P.v) load_v<V>(P.v + row * P.C + it.c0, vc);
+          const float nz = noisy ? P.noise[row] : 0.f;
+#pragma unroll
+          for (int j = 0; j < V; ++j) {
+            const float m = dact_of(pre_act(v[j], d[j], bi[j], noisy, s[j], nz), P.act, P.alpha);
+            const float mg = P.g ? m * g[j] : 0.f;
+            const float vcj = P.v ? vc[j] : 0.f;
+            sd[j] = fmaf(mg, vcj, sd[j]);
+            gc[j] = mg * vd[j];
+            v[j] = m * fmaf(d[j], vcj, v[j] * vd[j]);
+          }
+          if (P.out) store_v<V>(P.out + row * P.C + it.c0, v);
+          if (P.out2) store_v<V>(P.out2 + row * P.C + it.c0, gc);
+        }
+      }
+    }
+    if (P.part) {                                        // (uniform over the launch)
+#pragma unroll
+      for (int j = 0; j < V; ++j) s_a[ty][tx * V + j] = sd[j];
+      __syncthreads();
+      const int c = it.c0 - tx * V + tid;
+      item_sum<L::TY>(s_a, tid, c, P.C, P.part + ((size_t)it.b * P.chunks + it.ch) * P.C + c);
+      __syncthreads();
+    }
+  }
+}
+
+template <int V>
+__global__ __launch_bounds__(kThreads) void modulate2_kernel(const ModParams P) {
+  typedef Lay<V> L;
+  const int tid = threadIdx.x, tx = tid % L::LX, ty = tid / L::LX;
+  for (long long id = blockIdx.x; id < P.items; id += gridDim.x) {
+    const Item it = item_of<V>(P, id, tx);
+    if (it.c0 >= P.C) continue;
+    float s[V], vs[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      s[j] = P.v ? P.s[(size_t)it.b * P.sstride + it.c0 + j] : 0.f;
+      vs[j] = P.vrow ? P.vrow[(size_t)it.b * P.C + it.c0 + j] : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < L::RPT; ++k) {
+      const int lr = ty + k * L::TY;
+      if (lr < it.nrows) {
+        const long long row = it.row0 + lr;
+        float x[V], vx[V];
+        if (P.vrow) load_v<V>(P.x + row * P.C + it.c0, x);
+        if (P.v) load_v<V>(P.v + row * P.C + it.c0, vx);
+#pragma unroll
+        for (int j = 0; j < V; ++j) x[j] = fmaf(s[j], P.v ? vx[j] : 0.f, (P.vrow ? x[j] : 0.f) * vs[j]);
+        store_v<V>(P.out + row * P.C + it.c0, x);
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void demod_r_kernel(const float* vs, const float* s, int sstride, const float* q, const float* d,
+                                                         const float* gd, int B, int Cin, int Cout, float* gg_d, float* gd_d) {
+  __shared__ float s_a[kDL][kTileC];
+  const int tid = threadIdx.x, tx = tid % kTileC, ty = tid / kTileC;
+  const int otiles = (Cout + kTileC - 1) / kTileC;
+  const long long items = (long long)B * otiles;
+  for (long long id = blockIdx.x; id < items; id += gridDim.x) {
+    const int b = (int)(id / otiles), o = (int)(id % otiles) * kTileC + tx;
+    float a = 0.f;
+    if (o < Cout) {
+      for (int i = ty; i < Cin; i += kDL) a = fmaf(vs[(size_t)b * Cin + i] * s[(size_t)b * sstride + i], q[(size_t)i * Cout + o], a);
+    }
+    s_a[ty][tx] = a;
+    __syncthreads();
+    if (ty == 0 && o < Cout) {
+      a = 0.f;
+      for (int t = 0; t < kDL; ++t) a += s_a[t][tx];
+      const float dv = d[(size_t)b * Cout + o], d2 = dv * dv;
+      if (gg_d) gg_d[(size_t)b * Cout + o] = -(d2 * dv) * a;
+      if (gd_d) gd_d[(size_t)b * Cout + o] = -3.0f * d2 * gd[(size_t)b * Cout + o] * a;
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void demod_dw2_kernel(const float* vs, const float* gd, const float* d, const float* s, int sstride,
+                                                           const float* W, int T, int B, int Cin, int Cout, int accumulate, float* dW) {
+  const long long IO = (long long)Cin * Cout;
+  for (long long e = (long long)blockIdx.x * kThreads + threadIdx.x; e < IO; e += (long long)gridDim.x * kThreads) {
+    const int i = (int)(e / Cout), o = (int)(e % Cout);
+    float dq = 0.f;
+    for (int b = 0; b < B; ++b)
+      dq = fmaf(vs[(size_t)b * Cin + i] * s[(size_t)b * sstride + i], e_of(d[(size_t)b * Cout + o], gd[(size_t)b * Cout + o]), dq);
+    dq *= 4.0f;
+    for (int t = 0; t < T; ++t) {
+      const float v = W[(size_t)t * IO + e] * dq;
+      dW[(size_t)t * IO + e] = accumulate ? dW[(size_t)t * IO + e] + v : v;
+    }
+  }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
 bool overlap(const void* a, size_t na, const void* b, size_t nb) {
   const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
@@ -631,4 +771,108 @@ int t2i_demod_act_bwd(const float* g, const float* c, const float* d, const floa
   hipLaunchKernelGGL(modconv_sum_kernel, dim3(blocks_for(fin)), dim3(kThreads), 0, st, (const float*)P.part, (int)B, P.chunks, 3, (int)C, dd, dbias,
                      dstrength);
   return launched(what);
+}
+
+size_t t2i_demod_act_bwd2_workspace_bytes(int32_t B, int64_t R, int32_t C) { return partial_bytes(B, R, C, 1); }
+
+int t2i_demod_act_bwd2(const float* g, const float* c, const float* d, const float* bias, const float* noise, const float* strength,
+                       const float* vc, const float* vd, int32_t B, int64_t R, int32_t C, int act, float alpha, float* gg, float* gc, float* gd,
+                       void* ws, size_t ws_bytes, t2i_stream_t stream) {
+  const char* what = "t2i_demod_act_bwd2";
+  if (!c) { set_error("%s: bad argument (a NULL pointer)", what); return T2I_ERR_INVALID; }
+  if (!vc && !vd) { set_error("%s: bad argument (no cotangent: vc and vd are both NULL)", what); return T2I_ERR_INVALID; }
+  if (!gg && !gc && !gd) { set_error("%s: bad argument (no output is wanted)", what); return T2I_ERR_INVALID; }
+  ModParams P = {};
+  if (int rc = geometry(what, B, R, C, P)) return rc;
+  if (int rc = act_ok(what, act, alpha, noise, strength, P)) return rc;
+  if (vd && !d) { set_error("%s: bad argument (vd without d: the coefficient 1 has no gradient)", what); return T2I_ERR_INVALID; }
+  if (gc && !vd) { set_error("%s: bad argument (gc without vd)", what); return T2I_ERR_INVALID; }
+  if (gd && (!vc || !d)) { set_error("%s: bad argument (gd without vc or without d)", what); return T2I_ERR_INVALID; }
+  if ((gc || gd) && !g) { set_error("%s: bad argument (gc or gd without g)", what); return T2I_ERR_INVALID; }
+  const size_t bytes = (size_t)B * (size_t)R * (size_t)C * 4, rowb = (size_t)B * C * 4;
+  const float* ins[8] = {g, c, d, bias, noise, strength, vc, vd};
+  const size_t inb[8] = {bytes, bytes, rowb, (size_t)C * 4, (size_t)B * R * 4, (size_t)C * 4, bytes, rowb};
+  float* outs[3] = {gg, gc, gd};
+  const size_t outb[3] = {bytes, bytes, rowb};
+  for (int o = 0; o < 3; ++o) {
+    if (!outs[o]) continue;
+    for (int i = 0; i < 8; ++i)
+      if (ins[i] && overlap(outs[o], outb[o], ins[i], inb[i])) { set_error("%s: bad argument (an output overlaps an input)", what); return T2I_ERR_INVALID; }
+    for (int p = 0; p < o; ++p)
+      if (outs[p] && overlap(outs[o], outb[o], outs[p], outb[p])) { set_error("%s: bad argument (two outputs overlap)", what); return T2I_ERR_INVALID; }
+  }
+  if (gd)
+    if (int rc = workspace_ok(what, ws, ws_bytes, partial_bytes(B, R, C, 1))) return rc;
+  P.x = c; P.g = (gc || gd) ? g : nullptr; P.s = d; P.bias = bias; P.v = vc; P.vrow = vd; P.out = gg; P.out2 = gc;
+  P.part = gd ? static_cast<float*>(ws) : nullptr;
+  const hipStream_t st = (hipStream_t)stream;
+  if (C % 4 == 0 && aligned16(c, P.g, vc) && aligned16(gg, gc))
+    hipLaunchKernelGGL((demod_act_bwd2_kernel<4>), dim3(blocks_for(P.items)), dim3(kThreads), 0, st, P);
+  else hipLaunchKernelGGL((demod_act_bwd2_kernel<1>), dim3(blocks_for(P.items)), dim3(kThreads), 0, st, P);
+  if (int rc = launched(what)) return rc;
+  if (!gd) return T2I_OK;
+  const long long fin = (long long)(B + 2) * ((C + kFinC - 1) / kFinC);
+  hipLaunchKernelGGL(modconv_sum_kernel, dim3(blocks_for(fin)), dim3(kThreads), 0, st, (const float*)P.part, (int)B, P.chunks, 1, (int)C, gd,
+                     static_cast<float*>(nullptr), static_cast<float*>(nullptr));
+  return launched(what);
+}
+
+int t2i_modulate2(const float* s, int32_t style_stride, const float* vx, const float* x, const float* vs, int32_t B, int64_t R, int32_t C,
+                  float* gg, t2i_stream_t stream) {
+  const char* what = "t2i_modulate2";
+  if (!gg) { set_error("%s: bad argument (a NULL pointer)", what); return T2I_ERR_INVALID; }
+  if (!vx && !vs) { set_error("%s: bad argument (no cotangent: vx and vs are both NULL)", what); return T2I_ERR_INVALID; }
+  if ((vx && !s) || (vs && !x)) { set_error("%s: bad argument (vx comes with s, vs with x)", what); return T2I_ERR_INVALID; }
+  ModParams P = {};
+  if (int rc = geometry(what, B, R, C, P)) return rc;
+  if (vx)
+    if (int rc = stride_ok(what, style_stride, C, B)) return rc;
+  const size_t bytes = (size_t)B * (size_t)R * (size_t)C * 4;
+  if ((vx && (overlap(vx, bytes, gg, bytes) || overlap(s, ((size_t)(B - 1) * style_stride + C) * 4, gg, bytes))) ||
+      (vs && (overlap(x, bytes, gg, bytes) || overlap(vs, (size_t)B * C * 4, gg, bytes)))) {
+    set_error("%s: bad argument (gg overlaps an input)", what);
+    return T2I_ERR_INVALID;
+  }
+  P.s = s; P.sstride = vx ? style_stride : C; P.v = vx; P.x = vs ? x : nullptr; P.vrow = vs; P.out = gg;
+  const hipStream_t st = (hipStream_t)stream;
+  if (C % 4 == 0 && aligned16(P.x, vx, gg)) hipLaunchKernelGGL((modulate2_kernel<4>), dim3(blocks_for(P.items)), dim3(kThreads), 0, st, P);
+  else hipLaunchKernelGGL((modulate2_kernel<1>), dim3(blocks_for(P.items)), dim3(kThreads), 0, st, P);
+  return launched(what);
+}
+
+int t2i_demod_coef_bwd2(const float* vs, const float* gd, const float* d, const float* s, int32_t style_stride, const float* W, const float* q,
+                        int32_t T, int32_t Cin, int32_t Cout, int32_t B, float* gg_d, float* gd_d, float* dW, int32_t accumulate,
+                        t2i_stream_t stream) {
+  const char* what = "t2i_demod_coef_bwd2";
+  if (!vs || !gd || !d || !s || ((gg_d || gd_d) && !q) || (dW && !W)) { set_error("%s: bad argument (a NULL pointer)", what); return T2I_ERR_INVALID; }
+  if (!gg_d && !gd_d && !dW) { set_error("%s: bad argument (no output is wanted)", what); return T2I_ERR_INVALID; }
+  if (int rc = coef_shape_ok(what, T, Cin, Cout, B, style_stride)) return rc;
+  if ((long long)B * Cin >= kMaxElems) { set_error("%s: bad argument (vs [%d, %d] has 2^31 elements or more)", what, (int)B, (int)Cin); return T2I_ERR_INVALID; }
+  const size_t wb = (size_t)T * Cin * Cout * 4, qb = (size_t)Cin * Cout * 4, db = (size_t)B * Cout * 4, vb = (size_t)B * Cin * 4;
+  const size_t sb = ((size_t)(B - 1) * style_stride + Cin) * 4;
+  const float* ins[6] = {vs, gd, d, s, W, q};
+  const size_t inb[6] = {vb, db, db, sb, wb, qb};
+  float* outs[3] = {gg_d, gd_d, dW};
+  const size_t outb[3] = {db, db, wb};
+  for (int o = 0; o < 3; ++o) {
+    if (!outs[o]) continue;
+    for (int i = 0; i < 6; ++i)
+      if (ins[i] && overlap(outs[o], outb[o], ins[i], inb[i])) { set_error("%s: bad argument (an output overlaps an input)", what); return T2I_ERR_INVALID; }
+    for (int p = 0; p < o; ++p)
+      if (outs[p] && overlap(outs[o], outb[o], outs[p], outb[p])) { set_error("%s: bad argument (two outputs overlap)", what); return T2I_ERR_INVALID; }
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  if (gg_d || gd_d) {
+    const long long items = (long long)B * ((Cout + kTileC - 1) / kTileC);
+    hipLaunchKernelGGL(demod_r_kernel, dim3(blocks_for(items)), dim3(kThreads), 0, st, vs, s, (int)style_stride, q, d, gd, (int)B, (int)Cin,
+                       (int)Cout, gg_d, gd_d);
+    if (int rc = launched(what)) return rc;
+  }
+  if (dW) {
+    const long long IO = (long long)Cin * Cout;
+    hipLaunchKernelGGL(demod_dw2_kernel, dim3(blocks_for((IO + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, vs, gd, d, s,
+                       (int)style_stride, W, (int)T, (int)B, (int)Cin, (int)Cout, (int)accumulate, dW);
+    if (int rc = launched(what)) return rc;
+  }
+  return T2I_OK;
 }

@@ -115,16 +115,21 @@ class DGSchedule(object):
         half.optim.apply(grad_scale=scale, refresh=refresh)
         return out
 
-    def capture(self, graphs, joint=None):
+    def capture(self, graphs, joint=None, g_forms=None):
         """Capture the iteration into `graphs` (a StepGraphs; call after one eager iteration).  Single process: 'dg' from `joint`, a
         body of both halves, if one is given, else 'd' and 'g'.  Data parallelism: the four cut segments, in thread-local capture
-        mode because the process group's watchdog thread polls events meanwhile; the update segments run no convolution."""
+        mode because the process group's watchdog thread polls events meanwhile; the update segments run no convolution.
+        g_forms (single process, no joint body): {graph name: keywords of the generator's losses} when the generator half has more than
+        one form (PGGAN's path-length step); run(g_form=) says which one an iteration replays.  None: the one form 'g'."""
+        if g_forms is not None and (self.dp is not None or joint is not None):
+            raise ValueError('g_forms: several forms of the generator half are captured in a single process and without a joint body only')
         if self.dp is None:
             if joint is not None:
                 graphs.capture('dg', joint)
             else:
                 graphs.capture('d', lambda f: self.step(self.d, f))
-                graphs.capture('g', lambda f: self.step(self.g, f))
+                for name, kw in ({'g': {}} if g_forms is None else g_forms).items():
+                    graphs.capture(name, lambda f, kw=kw: self.step(self.g, f, **kw))
             return
         scale = 1.0 / self.dp.world
         self.capturing = True
@@ -136,9 +141,12 @@ class DGSchedule(object):
         finally:
             self.capturing = False
 
-    def run(self, feed, lr_d, lr_g, graphs=None, joint=None):
+    def run(self, feed, lr_d, lr_g, graphs=None, joint=None, g_form=None):
         """One iteration -> {'d': ..., 'g': ...}: replayed from `graphs` if given, else eager (from `joint` if given).  prepare(lr)
-        publishes each step size on the host, outside any graph: both up front for a one-body iteration, else before its half."""
+        publishes each step size on the host, outside any graph: both up front for a one-body iteration, else before its half.
+        g_form: (graph name, keywords of the generator's losses) of the form of the generator half this iteration takes (capture's
+        g_forms); None: 'g' and no keywords."""
+        g_name, g_kw = ('g', {}) if g_form is None else g_form
         if graphs is not None:
             graphs.load(feed)
         one_body = 'dg' in graphs.graphs if graphs is not None else joint is not None
@@ -151,9 +159,9 @@ class DGSchedule(object):
         for name, half, lr in (('d', self.d, lr_d), ('g', self.g, lr_g)):
             half.optim.prepare(lr)
             if graphs is None:
-                out[name] = self.step(half, feed)
+                out[name] = self.step(half, feed, **(g_kw if name == 'g' else {}))
                 continue
-            out[name] = graphs.replay(name)
+            out[name] = graphs.replay(g_name if name == 'g' else name)
             if self.dp is not None:
                 self.dp.allreduce_arena(half.arena)
                 graphs.replay(name + '_upd')

@@ -2378,6 +2378,76 @@ def demod_act_bwd(g, c, d=None, bias=None, noise=None, strength=None, act=ACT_NO
     return dc, dd, dbias, dstrength
 
 
+# ---- ... and the backward of that backward -----------------------------------------------------------------------
+def _dense_rows(op, t, name, B, C):
+    _chk(t, name, f32=True)
+    if tuple(t.shape) != (B, C):
+        raise ValueError('%s: %s must be [%d, %d], got %s' % (op, name, B, C, tuple(t.shape)))
+
+
+def modulate2(s, vx, x, vs):
+    """The cotangent of g in the scale pass's backward (dx = g s, ds = sum over (h, w) of g x): s vx + x vs for the cotangents vx [B,H,W,C] of
+    dx and vs [B,C] of ds, either of which may be None (vx comes with s, vs with x).  One launch."""
+    ref = vx if vx is not None else x
+    if ref is None or (vs is not None and x is None) or (vx is not None and s is None) or (vx is None and vs is None):
+        raise ValueError('modulate2: vx (with s) or vs (with x) must be given')
+    B, R, C = _brc('modulate2', ref, 'vx' if vx is not None else 'x')
+    sstride = _scale_rows('modulate2', s, 's', B, C) if vx is not None else C
+    if vs is not None:
+        _dense_rows('modulate2', vs, 'vs', B, C)
+        _chk(x, 'x', f32=True)
+        assert x.shape == ref.shape
+    gg = torch.empty_like(ref)
+    if _live(ref):
+        check(lib.t2i_modulate2(_ptr(s) if vx is not None else None, sstride, _ptr(vx), _ptr(x) if vs is not None else None, _ptr(vs), B, R, C,
+                                _ptr(gg), _stream()), 't2i_modulate2')
+    return gg
+
+
+def demod_act_bwd2(g, c, d, bias, noise, strength, vc, vd, act=ACT_NONE, alpha=0.2, want_g=True, want_c=True, want_d=True):
+    """The backward of demod_act_bwd for the cotangents vc [B,H,W,C] of dc and vd [B,C] of dd (either may be None) ->
+    (gg = m (d vc + c vd), gc = m g vd or None, gd [B,C] = sum over (h, w) of m g vc or None), m = act'(the recomputed pre-activation).
+    One launch, two with gd."""
+    B, R, C = _demod_act_args('demod_act_bwd2', c, d, bias, noise, strength)
+    _chk(g, 'g', f32=True)
+    assert g.shape == c.shape
+    if vc is None and vd is None:
+        raise ValueError('demod_act_bwd2: vc or vd must be given')
+    if vc is not None:
+        _chk(vc, 'vc', f32=True)
+        assert vc.shape == c.shape
+    if vd is not None:
+        if d is None:
+            raise ValueError('demod_act_bwd2: vd without d')
+        _dense_rows('demod_act_bwd2', vd, 'vd', B, C)
+    gg = torch.empty_like(c) if want_g else None
+    gc = torch.empty_like(c) if (want_c and vd is not None) else None
+    gd = torch.empty((B, C), dtype=torch.float32, device=c.device) if (want_d and vc is not None and d is not None) else None
+    if _live(c) and (gg is not None or gc is not None or gd is not None):
+        wsp, wsn = _ws_args(c, int(lib.t2i_demod_act_bwd2_workspace_bytes(B, R, C))) if gd is not None else (None, 0)
+        check(lib.t2i_demod_act_bwd2(_ptr(g), _ptr(c), _ptr(d), _ptr(bias), _ptr(noise), _ptr(strength), _ptr(vc), _ptr(vd), B, R, C, act, alpha,
+                                     _ptr(gg), _ptr(gc), _ptr(gd), wsp, wsn, _stream()), 't2i_demod_act_bwd2')
+    return gg, gc, gd
+
+
+def demod_coef_bwd2(vs, gd, d, w, s, q, want_gd=True, want_d=True, want_w=True, out=None, accumulate=False):
+    """The backward of demod_coef_bwd's ds for its cotangent vs [B,Cin] -> (-d^3 r to gd or None, -3 d^2 gd r to d or None, the term
+    4 w sum_b vs s e to w or None), r = sum_i vs s q.  A launch for the first two, a launch for the third; out / accumulate as in demod_coef_bwd."""
+    T, Cin, Cout, B, sstride = _filter_taps('demod_coef_bwd2', w, s)
+    _chk(gd, 'gd', f32=True); _chk(d, 'd', f32=True); _chk(q, 'q', f32=True)
+    _dense_rows('demod_coef_bwd2', vs, 'vs', B, Cin)
+    assert tuple(gd.shape) == (B, Cout) and tuple(d.shape) == (B, Cout) and tuple(q.shape) == (Cin, Cout)
+    gg_d = torch.empty_like(d) if want_gd else None
+    gd_d = torch.empty_like(d) if want_d else None
+    dw = (torch.empty_like(w) if out is None else out) if want_w else None
+    if dw is not None and (dw.dtype != torch.float32 or dw.numel() != w.numel() or not dw.is_contiguous()):
+        raise ValueError('demod_coef_bwd2: out must be a contiguous float32 tensor of %d elements' % w.numel())
+    if _live(w) and (want_gd or want_d or want_w):
+        check(lib.t2i_demod_coef_bwd2(_ptr(vs), _ptr(gd), _ptr(d), _ptr(s), sstride, _ptr(w), _ptr(q), T, Cin, Cout, B, _ptr(gg_d), _ptr(gd_d),
+                                      _ptr(dw), 1 if (accumulate and out is not None) else 0, _stream()), 't2i_demod_coef_bwd2')
+    return gg_d, gd_d, dw
+
+
 # ---- sliced Wasserstein distance (csrc/t2i_swd.hip; evaluation/swd.py is the caller) -----------------------------------------
 def _f32_nd(t, name, dim):
     if t.dtype != torch.float32 or t.dim() != dim or not t.is_contiguous():

@@ -12,6 +12,7 @@ from ...utils.saver import latest_checkpoint
 
 W_AVG = 'g_net/mapping/w_avg'                   # PGGAN(style_dim=D): the running mean of the style vector, [D], not trainable
 RESAMPLE_KEY = 'g_net/resample_filter'          # the checkpoint entry of PGGAN(resample_filter=...): the taps divided by their sum, float32
+PL_MEAN_KEY = 'pl_reg/pl_mean'                  # the checkpoint entry of PGGAN(pl_weight=...): the moving average of the path length, a float32 scalar
 
 
 def _number(v, ok):
@@ -43,7 +44,8 @@ def normalised_taps(resample_filter, name='resample_filter'):
 
 def validated(batch_size, critic_norm=None, critic_mbstd=None, g_ema=None, equalized_lr=False, adam_lr=None, diffaug=None, diffaug_p=None,
               diffaug_adapt=False, diffaug_sampler=None, critic_sn=False, resample_filter=None, style_dim=None, mapping_layers=4,
-              style_noise=True, truncation_psi=None, modulated_conv=False, label=str):
+              style_noise=True, truncation_psi=None, modulated_conv=False, pl_weight=None, pl_interval=4, pl_shrink=2, pl_decay=0.01,
+              data_parallel=False, label=str):
     """The optional keywords of PGGAN, checked -> {attribute: value} as the constructor keeps them (numbers cast to float, the taps also
     normalised, the group of critic_mbstd picked); a bad value is a ValueError that names the keyword through `label` (the identity; an
     entry point passes `flag`, and the same sentence speaks of `--diffaug-p`)."""
@@ -72,6 +74,23 @@ def validated(batch_size, critic_norm=None, critic_mbstd=None, g_ema=None, equal
         raise ValueError('%s must be True or False, got %r' % (L('modulated_conv'), modulated_conv))
     if modulated_conv and style_dim is None:
         raise ValueError('%s needs %s (the style-based generator whose convolutions it modulates), which is None' % (L('modulated_conv'), L('style_dim')))
+    # pl_weight=W (needs modulated_conv; Karras et al. 2020, section 3.2): path-length regularisation.  On every
+    # pl_interval-th generator step a second generator pass over the first max(1, B // pl_shrink) rows is differentiated to w against a
+    # random image y, and W pl_interval mean((|J| - a)^2) joins G_loss in the same Adam step; a, the moving average of |J| with decay
+    # pl_decay, lives on the device and in checkpoints as PL_MEAN_KEY.  The other generator steps, and the generator's function, are unchanged.
+    if pl_weight is not None and not _number(pl_weight, lambda v: math.isfinite(v) and v > 0.0):
+        raise ValueError('%s must be None or a finite weight > 0 (of the path-length penalty in the generator loss), got %r' % (L('pl_weight'), pl_weight))
+    if not _count(pl_interval):
+        raise ValueError('%s must be an integer >= 1 (the penalty joins every such generator step), got %r' % (L('pl_interval'), pl_interval))
+    if not _count(pl_shrink):
+        raise ValueError('%s must be an integer >= 1 (the penalty is taken over batch // it samples), got %r' % (L('pl_shrink'), pl_shrink))
+    if not _number(pl_decay, lambda v: 0.0 < v <= 1.0):
+        raise ValueError('%s must be a number in (0, 1] (how far the mean path length moves towards a step\'s), got %r' % (L('pl_decay'), pl_decay))
+    if pl_weight is not None and not modulated_conv:
+        raise ValueError('%s needs %s (the path-length penalty differentiates the generator twice, and the AdaIN layers of the other '
+                         'generators have no second derivative)' % (L('pl_weight'), L('modulated_conv')))
+    if pl_weight is not None and data_parallel:
+        raise ValueError('%s under data parallelism is not done (the penalty and its mean path length are formed per process)' % L('pl_weight'))
     # resample_filter=(1, 3, 3, 1): utils.ops.upsample_2d for the generator's nearest x2 `upscale` and utils.ops.downsample_2d for the critic's
     # 2x2 `pool`, in the blocks and in both fade-in branches (Karras et al. 2019, Zhang 2019): one launch of
     # csrc/t2i_resample.hip each, differentiable to any order.  This changes the generator's function, so checkpoints carry the normalised
@@ -134,6 +153,7 @@ def validated(batch_size, critic_norm=None, critic_mbstd=None, g_ema=None, equal
         raise ValueError('%s needs an integer batch_size >= 1 to pick its group size from, got %r' % (L('critic_mbstd'), batch_size))
     group = None if critic_mbstd is None else max(g for g in range(1, min(critic_mbstd, 16) + 1) if batch_size % g == 0)
     return dict(style_dim=style_dim, mapping_layers=mapping_layers, style_noise=style_noise, modulated_conv=modulated_conv,
+                pl_weight=None if pl_weight is None else float(pl_weight), pl_interval=pl_interval, pl_shrink=pl_shrink, pl_decay=float(pl_decay),
                 truncation_psi=None if truncation_psi is None else float(truncation_psi),
                 resample_filter=None if taps is None else taps[0],        # the taps as given; None: nearest x2 and the 2x2 mean
                 resample_taps=None if taps is None else taps[1],          # ... divided by their sum, float32: what checkpoints carry
@@ -200,6 +220,13 @@ def add_trainer_arguments(ap):
                          "critic step next to the Adam launch; checkpoints carry the raw weights, u, v and sigma (default: none)")
     add_resample_filter_argument(ap, reader=False)
     add_style_arguments(ap, reader=False)
+    ap.add_argument('--pl-weight', type=float, default=None, metavar='W',
+                    help='--modulated-conv: path-length regularisation of the generator (Karras et al. 2020) with weight W > 0 (the '
+                         'publication: 2); checkpoints carry the mean path length; the readers need no flag (default: none)')
+    ap.add_argument('--pl-interval', type=int, default=None, metavar='N', help='--pl-weight: the penalty joins every N-th generator step (default 4)')
+    ap.add_argument('--pl-shrink', type=int, default=None, metavar='K', help='--pl-weight: the penalty is taken over batch // K samples (default 2)')
+    ap.add_argument('--pl-decay', type=float, default=None, metavar='D',
+                    help="--pl-weight: the mean path length moves by D in (0, 1] of its distance to each step's (default 0.01)")
     ap.add_argument('--diffaug', default=None, metavar='POLICY',
                     help="differentiable augmentation of every image the critic sees (Zhao et al. 2020): a comma-separated subset of "
                          "color,translation,cutout (default: none)")
@@ -231,6 +258,8 @@ def kwargs_of(ap, args):
         ap.error('--mapping-layers / --no-style-noise / --truncation-psi need --style-dim (the generator they configure)')
     if given('style_dim') is None and given('modulated_conv'):
         ap.error('--modulated-conv needs --style-dim (the generator whose convolutions it modulates)')
+    if given('pl_weight') is None and any(given(k) is not None for k in ('pl_interval', 'pl_shrink', 'pl_decay')):
+        ap.error('--pl-interval / --pl-shrink / --pl-decay are the numbers of --pl-weight, which is not given')
     if given('diffaug') is None and (given('diffaug_p') is not None or given('diffaug_adapt')):
         ap.error('--diffaug-p / --diffaug-adapt need --diffaug (the policy they apply)')
     # the numbers of the run's sampler (`run_sampler`), which are no keywords of the model
@@ -246,6 +275,7 @@ def kwargs_of(ap, args):
     kw = dict(critic_norm=given('critic_norm'), critic_mbstd=given('critic_mbstd'), g_ema=given('g_ema'), adam_lr=given('lr'), diffaug=given('diffaug'),
               diffaug_p=given('diffaug_p'), resample_filter=taps, style_dim=given('style_dim'), mapping_layers=given('mapping_layers'),
               truncation_psi=given('truncation_psi'), style_noise=False if given('no_style_noise') else None,
+              pl_weight=given('pl_weight'), pl_interval=given('pl_interval'), pl_shrink=given('pl_shrink'), pl_decay=given('pl_decay'),
               **{k: True for k in ('equalized_lr', 'critic_sn', 'diffaug_adapt', 'modulated_conv') if given(k)})
     kw = {k: v for k, v in kw.items() if v is not None}
     try:

@@ -32,7 +32,7 @@ from ...graphs import DGSchedule, StepGraphs
 from ...utils.saver import Saver, load, save
 from ...utils.ops import (DiffAugmentSampler, concat_tile, conv2d, diff_augment, diff_augment_params, downsample_2d, fc, layer_norm, lerp,
                           lrelu_act, minibatch_stddev_stat, modulated_conv2d, pixel_norm, pool, relu, style_block, upsample_2d, upscale)
-from .options import RESAMPLE_KEY, W_AVG, checkpoint_architecture, describe_taps, same_taps, validated
+from .options import PL_MEAN_KEY, RESAMPLE_KEY, W_AVG, checkpoint_architecture, describe_taps, same_taps, validated
 from .options import normalised_taps, style_of_names  # noqa: F401  (importable from here, as before)
 
 W_AVG_DECAY = 0.995
@@ -44,14 +44,17 @@ class PGGAN(object):
                  build_model=True, device=None, seed=0, store=None, fmap_base=1024, fmap_max=512, z_dim=128, embed_dim=1024,
                  compr_embed_dim=128, dp=None, critic_norm=None, critic_mbstd=None, g_ema=None, equalized_lr=False, adam_lr=None,
                  diffaug=None, diffaug_p=None, diffaug_adapt=False, diffaug_sampler=None, critic_sn=False, resample_filter=None,
-                 style_dim=None, mapping_layers=4, style_noise=True, truncation_psi=None, modulated_conv=False):
-        # style_dim, mapping_layers, style_noise, truncation_psi, modulated_conv, resample_filter, resample_taps, critic_sn, diffaug, diffaug_p, diffaug_adapt,
+                 style_dim=None, mapping_layers=4, style_noise=True, truncation_psi=None, modulated_conv=False, pl_weight=None, pl_interval=4,
+                 pl_shrink=2, pl_decay=0.01):
+        # pl_weight, pl_interval, pl_shrink, pl_decay, style_dim, mapping_layers, style_noise, truncation_psi, modulated_conv, resample_filter, resample_taps, critic_sn, diffaug, diffaug_p, diffaug_adapt,
         # aug_sampler (the model's own is made below, on the store's device), adam_lr, equalized_lr, g_ema, critic_norm, critic_mbstd, mbstd_group
         vars(self).update(validated(
             batch_size, critic_norm=critic_norm, critic_mbstd=critic_mbstd, g_ema=g_ema, equalized_lr=equalized_lr, adam_lr=adam_lr, diffaug=diffaug,
             diffaug_p=diffaug_p, diffaug_adapt=diffaug_adapt, diffaug_sampler=diffaug_sampler, critic_sn=critic_sn, resample_filter=resample_filter,
             style_dim=style_dim, mapping_layers=mapping_layers, style_noise=style_noise, truncation_psi=truncation_psi,
-            modulated_conv=modulated_conv))
+            modulated_conv=modulated_conv, pl_weight=pl_weight, pl_interval=pl_interval, pl_shrink=pl_shrink, pl_decay=pl_decay,
+            data_parallel=dp is not None))
+        self._second_order = False                # the generator pass of the path-length penalty builds its modulated convolutions twice differentiable
         self._sn = None                           # where the style blocks take their noise from: (feed, 'd' | 'g'), a list of images, or None (drawn)
         self.resample_restored = None             # train(): the taps of the checkpoint the last restore read (None: it had none)
         self.critic_spectral = None
@@ -71,6 +74,8 @@ class PGGAN(object):
         self.device = self.store.device
         self.alpha_tra = 0.0                      # tf.Variable(0.0, trainable=False, name='alpha_tra')
         self._alpha_dev = torch.zeros(1, device=self.device)      # ... kept in device memory: graph-replayable fade-in
+        # pl_weight: the moving average of the path length, a device scalar updated in place on due generator steps (graph-replayable, like w_avg)
+        self.pl_mean = torch.zeros((), device=self.device) if self.pl_weight is not None else None
         self._graphs = None
         self.restored = None
         # data parallelism (BASELINE config 5 "DP=8"; the reference is single-device): an optional dp.DataParallel — replicas
@@ -219,7 +224,10 @@ class PGGAN(object):
             out['aug_p'] = self.aug_sampler.p_tensor().clone()
         return out
 
-    def g_losses(self, feed):
+    def g_losses(self, feed, pl=False):
+        """pl (pl_weight only): this generator step is due for the path-length penalty (iteration: idx % pl_interval == 0)."""
+        if pl:
+            return self._g_losses_pl(feed)
         cond, z = feed['cond'], feed['z']
         aug = None
         if self.aug_sampler is not None:          # the first launch, as in d_losses: call k + 1
@@ -239,6 +247,73 @@ class PGGAN(object):
         G_loss = -Dg_logit.mean() + self.kl_coeff * G_kl_loss
         self.schedule.backward(self.g_arena, [G_loss], None, self.g_vars.values())
         return dict(G_loss=G_loss.detach(), G_kl_loss=G_kl_loss.detach(), G=G.detach(), D_loss_fake=Dg_logit.detach().mean())
+
+    def pl_due(self, idx):
+        """Whether generator step `idx` (the argument of iteration) carries the path-length penalty."""
+        return self.pl_weight is not None and idx % self.pl_interval == 0
+
+    def _g_losses_pl(self, feed):
+        """g_losses on a due step of the path-length regulariser (Karras et al. 2020, section 3.2): the generator
+        step as it is, plus a second generator pass over rows [:Bp], Bp = max(1, B // pl_shrink), of the same z, cond, conditioning noise and
+        style-noise images (a sample's bits do not depend on its batch: the pass equals the main pass on those rows) with twice-differentiable
+        modulated convolutions; J = d sum(G y) / dw under input_grads_only, L = |J| per sample, a' = a + pl_decay (mean(L) - a) written back
+        to pl_mean in place, pen = mean((L - a')^2) with a' a constant, and one backward of G_loss + pl_weight pl_interval pen.  y is
+        feed['pl_noise'] [Bp,H,W,3] (independent N(0,1) / sqrt(H W) values) or a fresh draw."""
+        if self.pl_weight is None:
+            raise ValueError('g_losses(pl=True) needs a model built with pl_weight')
+        cond, z = feed['cond'], feed['z']
+        B = z.shape[0]
+        Bp = max(1, B // self.pl_shrink)
+        aug = None
+        if self.aug_sampler is not None:
+            aug = self._aug_table(feed, 'aug_g', B, (self.out_size, self.out_size))
+        self._ca = self._noise(feed, 'ca_noise_g', cond[:, :self.compr_embed_dim])
+        noise = {}                                # both passes see the same style-noise images: the fed ones, or one draw
+        for k, size in self.style_noise_keys():
+            if k.startswith('style_noise_g_'):
+                n = feed.get(k)
+                noise[k] = n if n is not None else K.trunc_normal_(torch.empty((B, size, size), device=self.device), a=-STYLE_NOISE_CUT, b=STYLE_NOISE_CUT)
+        self._sn = (noise, 'g')
+        G, mean, log_sigma = self.generator(z, cond, stages=self.stage, t=self.trans, reuse=True)
+        with torch.no_grad():
+            self.store.vars[W_AVG].lerp_(self._w.detach().mean(0), 1.0 - W_AVG_DECAY)
+        if self.diffaug is not None and aug is None:
+            aug = self._aug_table(feed, 'aug_g', G.shape[0], G.shape[1:3])
+        G_seen = G if self.diffaug is None else diff_augment(G, aug, self.diffaug)
+        with self.store.frozen('d_net'):
+            Dg_logit = self.discriminator(G_seen, cond, reuse=True, stages=self.stage, t=self.trans)
+        G_kl_loss = self.kl_std_normal_loss(mean, log_sigma)
+        G_loss = -Dg_logit.mean() + self.kl_coeff * G_kl_loss
+        # ---- the regulariser
+        y = feed.get('pl_noise')
+        if y is None:
+            y = self.draw_pl_noise(torch.empty((Bp, self.out_size, self.out_size, self.channel), device=self.device))
+        if tuple(y.shape) != (Bp, self.out_size, self.out_size, self.channel):
+            raise ValueError('pl_noise must be %s, got %s' % ((Bp, self.out_size, self.out_size, self.channel), tuple(y.shape)))
+        self._ca = self._ca[:Bp].contiguous()
+        self._sn = ({k: n[:Bp].contiguous() for k, n in noise.items()}, 'g')
+        self._second_order = True
+        try:
+            Gp, _, _ = self.generator(z[:Bp].contiguous(), cond[:Bp].contiguous(), stages=self.stage, t=self.trans, reuse=True)
+        finally:
+            self._second_order = False
+        w = self._w
+        with A.input_grads_only():
+            J, = torch.autograd.grad((Gp * y).sum(), [w], create_graph=True)
+        length = torch.sqrt((J * J).sum(1))
+        with torch.no_grad():
+            self.pl_mean.add_(self.pl_decay * (length.detach().mean() - self.pl_mean))       # a' = a + decay (mean(L) - a), in place
+        penalty = ((length - self.pl_mean.detach()) ** 2).mean()
+        total = G_loss + (self.pl_weight * self.pl_interval) * penalty
+        self.schedule.backward(self.g_arena, [total], None, self.g_vars.values())
+        return dict(G_loss=G_loss.detach(), G_kl_loss=G_kl_loss.detach(), G=G.detach(), D_loss_fake=Dg_logit.detach().mean(),
+                    pl_penalty=penalty.detach(), pl_length=length.detach().mean(), pl_mean=self.pl_mean.clone())
+
+    @staticmethod
+    def draw_pl_noise(out):
+        """The regulariser's random image y, in place: independent standard normals (cut at +-6 sigma like the style noise) / sqrt(H W)."""
+        K.trunc_normal_(out, a=-STYLE_NOISE_CUT, b=STYLE_NOISE_CUT)
+        return out.mul_(1.0 / math.sqrt(out.shape[1] * out.shape[2]))
 
     def set_alpha(self, value):
         self.alpha_tra = float(value)
@@ -260,6 +335,8 @@ class PGGAN(object):
         if self.diffaug is not None and self.aug_sampler is None:      # the two parameter tables of the augmentation: static buffers, re-drawn like eps_graph
             drawn += (('aug_d', (4 * B, 9)), ('aug_g', (B, 9)))
         drawn += tuple((k, (B, size, size)) for k, size in self.style_noise_keys())      # one image per style block and step, re-drawn like ca_noise_*
+        if self.pl_weight is not None:            # the regulariser's image y: a static buffer, re-drawn before every due replay
+            drawn += (('pl_noise', (max(1, B // self.pl_shrink), self.out_size, self.out_size, self.channel)),)
         for k, shape in drawn:
             if feed.get(k) is None:
                 feed[k] = torch.empty(shape, device=dev)
@@ -269,9 +346,10 @@ class PGGAN(object):
                                   filters=(self.d_arena.flat, self.g_arena.flat))
         self._redraw(feed)
         self._graphs.load(feed)
-        self.schedule.capture(self._graphs)
+        # pl_weight: both forms of the generator half; iteration picks one by idx, on the host
+        self.schedule.capture(self._graphs, g_forms=None if self.pl_weight is None else {'g': {}, 'g_pl': {'pl': True}})
 
-    def _redraw(self, feed):
+    def _redraw(self, feed, pl=False):
         st = self._graphs.static
         if feed.get('eps_graph') is None or feed['eps_graph'] is st['eps_graph']:
             st['eps_graph'].uniform_(0.0, 1.0)
@@ -286,6 +364,8 @@ class PGGAN(object):
             for k in ('aug_d', 'aug_g'):
                 if feed.get(k) is None or feed[k] is st[k]:
                     diff_augment_params(st[k].shape[0], size[0], size[1], self.diffaug, out=st[k])
+        if pl and (feed.get('pl_noise') is None or feed['pl_noise'] is st['pl_noise']):      # last, and on due steps only: the other draws keep their order
+            self.draw_pl_noise(st['pl_noise'])
 
     def iteration(self, idx, feed):
         """One D update then one G update (pggan.py:196-197)."""
@@ -293,7 +373,9 @@ class PGGAN(object):
         if self._graphs is not None:
             if self.aug_sampler is not None and any(feed.get(k) is not None and k not in self._graphs.static for k in ('aug_d', 'aug_g')):
                 raise ValueError('a parameter table is fed, but the graphs were captured drawing it: feed aug_d / aug_g to enable_graphs too')
-            self._redraw(feed)
+            self._redraw(feed, pl=self.pl_due(idx))
+        if self.pl_due(idx):                      # the generator half with the path-length penalty: picked here, no host value enters a graph
+            return self.schedule.run(feed, self.adam_lr, self.adam_lr, graphs=self._graphs, g_form=('g_pl', {'pl': True}))
         return self.schedule.run(feed, self.adam_lr, self.adam_lr, graphs=self._graphs)
 
     @contextlib.contextmanager
@@ -443,7 +525,7 @@ class PGGAN(object):
             k, self._block = self._block, self._block + 1
             noise = self._style_noise_image(k, x)
             return modulated_conv2d(x, self._w_used, f, ks=(3, 3), noise=noise, act=relu, init=self._init(3 * 3 * x.shape[-1]),
-                                    style_init=self._init(self.style_dim))
+                                    style_init=self._init(self.style_dim), **({'second_order': True} if self._second_order else {}))
         x = self._conv2d(x, f=f, ks=(3, 3), s=(1, 1))
         if self.style_dim is None:
             return layer_norm(x, act=relu)
@@ -551,6 +633,8 @@ class PGGAN(object):
                          ('reg_loss', 'reg_loss'), ('wdist', 'wdist'), ('wdist2', 'wdist2'), ('d_loss_mismatch', 'D_loss_mismatch'),
                          ('real_gp2', 'real_gp2')):
             vals.append(S.scalar(tag, float(d[key])))
+        if 'pl_penalty' in g:                     # a due step of the path-length regulariser
+            vals += [S.scalar('pl_penalty', float(g['pl_penalty'])), S.scalar('pl_length', float(g['pl_length'])), S.scalar('pl_mean', float(g['pl_mean']))]
         if self.aug_sampler is not None:          # the augmentation's probability after this step, and the controller's last statistic
             vals += [S.scalar('aug_p', float(d['aug_p'])), S.scalar('aug_r', self.aug_sampler.last_r)]
         self.writer.add_summary(vals, idx)
@@ -568,6 +652,9 @@ class PGGAN(object):
         for key in () if sn is None else [k for n in sn.names for k in sn.keys(n)]:
             # the raw weights, u, v and sigma of every normalised kernel; the variable itself is saved as the normalised weights every reader expects
             extra[key] = ((lambda key=key: sn.state_tensor(key).numpy()), (lambda a, key=key: loaded.__setitem__(key, a)))
+        if self.pl_weight is not None:            # the mean path length, under a name outside g_net/ and d_net/: no reader's name checks see it
+            extra[PL_MEAN_KEY] = ((lambda: self.pl_mean.detach().cpu().numpy()),
+                                  lambda a: (loaded.__setitem__(PL_MEAN_KEY, a), self.pl_mean.copy_(torch.as_tensor(a, dtype=torch.float32).reshape(()))))
         if self.resample_filter is not None:
             # the normalised taps, so that a reader built with other taps, or none, can refuse the generator instead of sampling another
             # function from its weights (what a restore found is read from the file: _after_restore)
@@ -595,6 +682,12 @@ class PGGAN(object):
             self.spectral_synced = len(synced)
             log('spectral normalisation: %d of %d kernels restored with their state, %d synced from their weights' % (
                 len(whole), len(sn.names), len(synced)))
+        if self.pl_weight is not None:
+            if PL_MEAN_KEY not in self._loaded:
+                self.pl_mean.zero_()
+                log('the checkpoint in %s carries no mean path length (it was trained without pl_weight): pl_mean starts at 0' % self.check_dir_read)
+            else:
+                log('path-length regularisation: pl_mean %.6f restored' % float(self.pl_mean))
         if self.aug_sampler is not None and 'diffaug/state' not in self._loaded:
             log('the checkpoint in %s carries no augmentation state: p stays %.6f, call counter %d' % (
                 self.check_dir_read, self.aug_sampler.p, self.aug_sampler.counter))

@@ -2,7 +2,7 @@
 1, 2t, 2, 3t, 3, ... (t = fade-in transition), batch 16 (8 from stage 6 on), 600000 images per stage, checkpoints
 written under `<CHECKPOINT_DIR>/stage<k>/` and read from the previous stage's directory.  `--iters` bounds the iterations
 per stage (the full 600000 // batch when omitted).  The model's options are options.py's flags (`--critic-norm`, `--critic-mbstd`,
-`--g-ema`, `--equalized-lr`, `--critic-sn`, `--resample-filter`, `--style-dim`, `--modulated-conv`, `--diffaug`, `--diffaug-p`, `--diffaug-adapt`, `--lr`).
+`--g-ema`, `--equalized-lr`, `--critic-sn`, `--resample-filter`, `--style-dim`, `--modulated-conv`, `--pl-weight`, `--diffaug`, `--diffaug-p`, `--diffaug-adapt`, `--lr`).
 
 Without `--cfg`, synthetic data stands in for the pickled datasets and everything goes under `--out`.  With `--cfg <yml>`
 (models/pggan/cfg/flowers.yml, birds.yml) the entry runs on the real dataset as the reference does: `TextDataset(DATASET_DIR,

@@ -428,7 +428,7 @@ def style_block(x, w, noise=None, act=None, name=None, init=None):
     return adain(x, s[:, :C], s[:, C:], noise=noise, strength=strength, act=act)
 
 
-def modulated_conv2d(x, w, f, ks=(3, 3), noise=None, act=None, demodulate=True, init=None, style_init=None, name=None, eps=1e-8):
+def modulated_conv2d(x, w, f, ks=(3, 3), noise=None, act=None, demodulate=True, init=None, style_init=None, name=None, eps=1e-8, second_order=False):
     """A weight-demodulated convolution (Karras et al. 2020; not in the reference): x [B,H,W,Cin] (contiguous NHWC,
     fp32), w [B, w_dim] the style vector, noise [B,H,W] a standard-normal image or None; stride 1, padding 'SAME'.
     Variables: <scope>/ModConv[_k]/{weights [kh,kw,Cin,f] (He, or init), biases [f] zeros, noise_strength [f] zeros (only with noise),
@@ -438,8 +438,11 @@ def modulated_conv2d(x, w, f, ks=(3, 3), noise=None, act=None, demodulate=True, 
       y = act(conv(x[b], weights s[b,:] d[b,:]) + biases + noise_strength[o] noise[b,h,w])
     computed as act(d conv(x s, weights) + ...), which is the same function: a scale pass over x, the project's convolution without bias
     or activation, one epilogue.  act: None, relu or lrelu_act(slope >= 0), fused.  Gradients reach x, w and every variable (the
-    parameters' not under autograd.input_grads_only()); noise gets none.  First order only.  bf16 tensors, a stacked pass, another rank, a
-    non-contiguous x or noise, wrong shapes, a negative lrelu slope, tanh and an unfused activation are refused before any launch."""
+    parameters' not under autograd.input_grads_only()); noise gets none.  First order only, unless second_order=True (DESIGN.md section
+    4.46): then the same launches run forward and in the first backward, the values are the same bit for bit, and a gradient taken with
+    create_graph=True under autograd.input_grads_only() can be differentiated once more to x, w and every variable (path-length
+    regularisation); a cotangent for a parameter's gradient and a third differentiation are refused.  bf16 tensors, a stacked pass, another
+    rank, a non-contiguous x or noise, wrong shapes, a negative lrelu slope, tanh and an unfused activation are refused before any launch."""
     op = 'modulated_conv2d'
     st = S.default_store()
     _fp32_plain(x, op)
@@ -475,6 +478,8 @@ def modulated_conv2d(x, w, f, ks=(3, 3), noise=None, act=None, demodulate=True, 
             raise ValueError('%s: noise requires a gradient, and the operator gives it none (detach it)' % op)
     if not isinstance(demodulate, bool):
         raise ValueError('%s: demodulate must be True or False, got %r' % (op, demodulate))
+    if not isinstance(second_order, bool):
+        raise ValueError('%s: second_order must be True or False, got %r' % (op, second_order))
     if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not (math.isfinite(eps) and eps >= 0.0):
         raise ValueError('%s: eps must be a finite number >= 0, got %r' % (op, eps))
     with st.variable_scope(name or st.unique_op_name('ModConv'), reuse=st.reuse()):
@@ -483,9 +488,10 @@ def modulated_conv2d(x, w, f, ks=(3, 3), noise=None, act=None, demodulate=True, 
         strength = st.get_variable('noise_strength', (f,), S.constant_init(0.0)) if noise is not None else None
         s = 1.0 + fc(w, Cin, init=style_init, name='style')
     geom = K.conv_desc(B, H, W, Cin, f, kh, kw, 1, 1, 'SAME')
-    d = A.DemodCoefFn.apply(weights, s, float(eps))[0] if demodulate else None
-    c = A.Conv2dFn.apply(A.ModulateFn.apply(x, s), weights, None, geom, K.ACT_NONE, 0.0)
-    return A.DemodActFn.apply(c, d, biases, noise, strength, kind, alpha)
+    coef, scale, epilogue = (A.DemodCoefFn2, A.ModulateFn2, A.DemodActFn2) if second_order else (A.DemodCoefFn, A.ModulateFn, A.DemodActFn)
+    d = coef.apply(weights, s, float(eps))[0] if demodulate else None
+    c = A.Conv2dFn.apply(scale.apply(x, s), weights, None, geom, K.ACT_NONE, 0.0)
+    return epilogue.apply(c, d, biases, noise, strength, kind, alpha)
 
 
 def minibatch_stddev_stat(x, group_size=4, num_features=1, eps=1e-8):

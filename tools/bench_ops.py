@@ -6,7 +6,7 @@ differentiable augmentation of csrc/t2i_augment.hip at the PGGAN trainer's shape
 (`--only diff_augment`), and the critic's optimizer step with and without spectral normalisation (`--only spectral_norm`), and the
 anti-aliased resampling of csrc/t2i_resample.hip at the PGGAN trainer's full widths (`--only upfirdn`), and the style layer of
 csrc/t2i_style.hip at the generator's B = 8 shapes next to layer_norm on the same tensors (`--only adain`), and the launches of a
-weight-demodulated convolution besides its convolution (csrc/t2i_modconv.hip) next to the style layer in the same run (`--only modconv`): one JSON line per kernel with the time per call, the bytes the algorithm moves (reads + writes, from the
+weight-demodulated convolution besides its convolution (csrc/t2i_modconv.hip) next to the style layer in the same run (`--only modconv`), and that layer's second-order launches next to tensor-library calls (`--only modconv2`): one JSON line per kernel with the time per call, the bytes the algorithm moves (reads + writes, from the
 shapes), bytes per second, and the ratio of that rate to a device-to-device copy that moves the SAME number of bytes (half read, half
 written), timed in the same process.  Per measurement: 10 warm-up launches, then REPS rounds of 100 back-to-back launches between
 device events, kernel and copy rounds alternating; the median round is reported.  Read the ratio, not the absolute rate, as the share
@@ -398,6 +398,40 @@ def main():
                 one('adain forward, same run (2r + w)', 12 * n, lambda: K.adain_fwd(x, ys, yb, nz, st, K.ACT_RELU, 0.0), 3)
                 one('adain backward, same run (4r + w)', 20 * n, lambda: K.adain_bwd(g, x, ys, mean, rstd, nz, st, K.ACT_RELU, 0.0), 4)
                 del x, g, c, y
+
+    # the second-order launches of the weight-demodulated convolution at the same four shapes with B = 4 (the
+    # regulariser runs on half a batch of 8), relu + noise, every cotangent and every output: each next to a device copy of the same bytes
+    # and next to the same result from tensor-library calls, in the same alternating rounds.  Bytes: the passes over the [B,H,W,C]
+    # tensors (demod_act_bwd2: g, c, vc read, gg, gc written; modulate2: vx, x read, gg written) and over the filter (coef_bwd2: r + w).
+    if a.only == 'modconv2':
+        with torch.no_grad():
+            for shape in ((4, 4, 4, 512), (4, 16, 16, 512), (4, 64, 64, 128), (4, 256, 256, 64)):
+                B, H, W, C = shape
+                n, nw = B * H * W * C, 9 * C * C
+                x, g, c, vc, vx = (torch.randn(shape, device='cuda') for _ in range(5))
+                nz, st, bias = torch.randn((B, H, W), device='cuda'), torch.rand(C, device='cuda') - 0.5, torch.randn(C, device='cuda') * 0.1
+                s, gd, vd, vs = (torch.randn((B, C), device='cuda') for _ in range(4))
+                s = 1.0 + 0.3 * s
+                w = torch.randn((3, 3, C, C), device='cuda') * (2.0 / (9 * C)) ** 0.5
+                d, q = K.demod_coef(w, s)
+                row = lambda t: t[:, None, None, :]
+
+                def act2_composed():
+                    m = ((row(d) * c + bias + st * nz[..., None]) > 0).to(c.dtype)
+                    mg = m * g
+                    return m * (row(d) * vc + c * row(vd)), mg * row(vd), (mg * vc).sum((1, 2))
+
+                def coef2_composed():
+                    vss = vs * s
+                    r = vss @ q
+                    return -(d ** 3) * r, -3.0 * d * d * gd * r, 4.0 * w * (vss.t() @ (-0.5 * d ** 3 * gd))
+                one = lambda name, nbytes, fn, launches, composed: measure('modconv2: ' + name, shape, nbytes, fn, a.reps, a.iters, composed=composed,
+                                                                         extra={'launches': launches})
+                one('t2i_demod_act_bwd2 relu + noise, vc + vd -> gg, gc, gd (3r + 2w)', 20 * n,
+                    lambda: K.demod_act_bwd2(g, c, d, bias, nz, st, vc, vd, K.ACT_RELU, 0.0), 2, act2_composed)
+                one('t2i_modulate2 vx + vs -> gg (2r + w)', 12 * n, lambda: K.modulate2(s, vx, x, vs), 1, lambda: row(s) * vx + x * row(vs))
+                one('t2i_demod_coef_bwd2 -> gg_d, gd_d, dW (r + w of W)', 8 * nw, lambda: K.demod_coef_bwd2(vs, gd, d, w, s, q), 2, coef2_composed)
+                del x, g, c, vc, vx
 
 
 if __name__ == '__main__':
