@@ -620,7 +620,8 @@ int t2i_pool_dropout(const float* x, int32_t B, int32_t HW, int32_t D, float kee
  * (y fp32 [B, D], W [D, C], bias [C], labels int32 [B] in [0, C)), prob = softmax(logits), loss[0] = mean_b (logsumexp -
  * logit[label]), acc[0] = mean_b (argmax prob == label; the first maximum), and with dz = (prob - onehot) / B: dW = y^T dz,
  * db = colsum dz (accumulate != 0: +=), dy = dz W^T.  Each output element is summed by one thread in a fixed order: no
- * atomics, bitwise-repeatable.  Any C <= 1024 with B * C <= 16384; D <= 16384. */
+ * atomics, bitwise-repeatable.  Any C <= 1024 with B * C <= 16384 and D + C <= 16384: the forward stages (D + C) floats and
+ * the backward B * C floats in LDS, each within the 64 KiB a launch gets without asking for more. */
 size_t t2i_softmax_ce_head_workspace_bytes(int32_t B, int32_t C);
 int t2i_softmax_ce_head(const float* y, const float* W, const float* bias, const int32_t* labels, int32_t B, int32_t D, int32_t C,
                         float* logits, float* prob, float* loss, float* acc, float* dW, float* db, int32_t accumulate, float* dy,

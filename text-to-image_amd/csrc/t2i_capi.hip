@@ -1723,8 +1723,9 @@ int t2i_softmax_ce_head(const float* y, const float* W, const float* bias, const
                         float* logits, float* prob, float* loss, float* acc, float* dW, float* db, int32_t accumulate, float* dy,
                         void* ws, size_t ws_bytes, t2i_stream_t stream) {
   if (!y || !W || !bias || !labels || !logits || !prob || !loss || !acc || !dW || !db || !dy || B <= 0 || B > 65535 || D <= 0 ||
-      D > 16384 || C <= 0 || C > 1024 || (int64_t)B * C > 16384) {
-    set_error("t2i_softmax_ce_head: bad argument (B=%d D=%d C=%d; C <= 1024, B * C <= 16384, D <= 16384)", B, D, C);
+      C <= 0 || C > 1024 || (int64_t)B * C > 16384 || (int64_t)D + C > 16384) {
+    // head_fwd_kernel stages (D + C) floats and head_bwd_kernel B * C floats of dynamic LDS; neither raises the 64 KiB default
+    set_error("t2i_softmax_ce_head: bad argument (B=%d D=%d C=%d; C <= 1024, B * C <= 16384, D + C <= 16384)", B, D, C);
     return T2I_ERR_INVALID;
   }
   if (!ws || ws_bytes < softmax_ce_head_ws(B, C)) {

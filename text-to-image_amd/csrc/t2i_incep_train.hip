@@ -86,9 +86,19 @@ __global__ __launch_bounds__(kThreads) void head_fwd_kernel(const float* __restr
   if (threadIdx.x == 0) {
     float m = lg[0];
     for (int c = 1; c < C; ++c) m = fmaxf(m, lg[c]);
-    float se = 0.f;
-    for (int c = 0; c < C; ++c) se += expf(lg[c] - m);
     const int lab = labels[b];
+    int top = 0;
+    while (top < C - 1 && lg[top] != m) ++top;                 // the first class at the maximum: its term of se is exactly 1
+    // se = 1 + rest and prob[lab] - 1 = -others / se.  A confident row has se = 1 + (something far below 1): log(se) and
+    // prob[lab] - 1 formed from the rounded se are good to eps absolutely, which is no relative accuracy at all in a loss or a
+    // gradient of 1e-6; formed from the sums that leave the 1 out they are good relatively.
+    float se = 0.f, rest = 0.f, others = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float e = expf(lg[c] - m);
+      se += e;
+      if (c != top) rest += e;
+      if (c != lab) others += e;
+    }
     float* dz = ws;
     float* rowloss = ws + (int64_t)B * C;
     float* correct = rowloss + B;
@@ -99,9 +109,9 @@ __global__ __launch_bounds__(kThreads) void head_fwd_kernel(const float* __restr
       logits[(int64_t)b * C + c] = lg[c];
       prob[(int64_t)b * C + c] = p;
       if (p > best) { best = p; arg = c; }                     // first maximum
-      dz[(int64_t)b * C + c] = (p - (c == lab ? 1.f : 0.f)) / (float)B;
+      dz[(int64_t)b * C + c] = (c == lab ? -(others / se) : p) / (float)B;
     }
-    rowloss[b] = logf(se) - (lg[lab] - m);
+    rowloss[b] = log1pf(rest) - (lg[lab] - m);
     correct[b] = arg == lab ? 1.f : 0.f;
   }
 }
